@@ -63,6 +63,26 @@ def effective_cores():
     return min(n, cap) if cap > 0 else n
 
 
+DUMP_BYTES = 64 * 2 ** 20       # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(ctx, out_dir):
+    """The film as a caller of the timed path receives it, written as <name>.npy under out_dir.  The two arrays of a film too large
+    for DUMP_BYTES are cut to the same fixed, seeded sample of pixels (row-major indices in film_pixel_index)."""
+    import numpy as np
+    xyzw, rgb = ctx.film_xyzw(), ctx.film_rgb()
+    arrays = {"film_xyzw": xyzw, "film_rgb": rgb}
+    if xyzw.nbytes + rgb.nbytes > DUMP_BYTES:
+        n_px = xyzw.shape[0] * xyzw.shape[1]
+        keep = (DUMP_BYTES - 4096) // (xyzw.itemsize * 4 + rgb.itemsize * 3 + 8)      # 4096: room for the three .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n_px, keep, replace=False))
+        arrays = {"film_xyzw": xyzw.reshape(-1, 4)[idx], "film_rgb": rgb.reshape(-1, 3)[idx], "film_pixel_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,7 +104,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-spp1024", action="store_true", help="skip the secondary 1024-spp frame (N=1 only)")
     ap.add_argument("--cpu-tiles", type=int, default=0, help="tiles in the CPU sample (0 = auto, about 15 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the film of the last timed step (film_xyzw, film_rgb: what Context.film_xyzw() / film_rgb() "
+                         "return; at N > 1 the reduced film) as DIR/<name>.npy in float32; over %d MB in all, a fixed, seeded sample of pixels and their "
+                         "indices (film_pixel_index, float64)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Called without a launcher: start the N ranks ourselves (fresh children of a process that has not touched the GPU)
         # and let rank 0 of that job print the line.  n_gpus in the line is always the number of ranks that ran.
@@ -245,6 +271,8 @@ def main():
     fence()
     elapsed = time.time() - t_start
     cnt = ctx.counters()
+    if args.dump_outputs and rank == 0:       # before anything below renders into the film again
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, dump_outputs(ctx, args.dump_outputs)))
 
     film_check = None
     if use_dist and world > 1 and os.environ.get("BENCH_CHECK_FILM") != "0":      # a scaling line vouches for its own film (every rank holds the sum)

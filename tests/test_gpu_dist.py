@@ -172,6 +172,23 @@ def test_bench_library_reduce_world1():
     assert d["per_rank"][0]["tiles"] == d["tiles_total"] and d["per_rank"][0]["reduce_ms"] > 0
 
 
+def test_bench_dump_outputs_is_the_rendered_film(gpu_ctx, tmp_path):
+    """bench.py --dump-outputs DIR: the film of the last timed step, as film_xyzw() / film_rgb() return it, is the film a Context renders from
+    the same scene; the line counts the timed steps it was asked for."""
+    d = _bench_line(["--gpus", "1", "--triangles", "20000", "--res", "256", "--spp", "16", "--steps", "2", "--warmup", "1", "--no-spp1024",
+                     "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], {})
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(str(tmp_path))) == ["film_rgb.npy", "film_xyzw.npy"]
+    gpu_ctx.upload(scenes.rt1m(20000, res=256, spp=16))
+    gpu_ctx.film_clear(); gpu_ctx.render()
+    for name, want in (("film_xyzw", gpu_ctx.film_xyzw()), ("film_rgb", gpu_ctx.film_rgb())):
+        got = np.load(str(tmp_path / (name + ".npy")))
+        assert got.dtype == np.float32 and got.shape == want.shape
+        assert np.allclose(got, want, rtol=2e-6, atol=1e-7)          # two renders: edge-split samples (float atomics) may differ in the last bits
+        if name == "film_xyzw":
+            assert np.array_equal(bits(got[..., 3]), bits(want[..., 3]))
+
+
 def test_cpp_driver_eight_ranks_deal_the_full_frame(tmp_path):
     """BASELINE config 3's deal at its real size: a 1024 x 1024 film is 65 x 65 = 4 225 tiles of 16 x 16 (sampler.rs:271-289); eight ranks -- threads of
     ONE process on this one GPU (a box allows six GPU processes, so bench.py's process-per-rank flow is rehearsed with four) -- take 529 or 528
