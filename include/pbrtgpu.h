@@ -168,6 +168,22 @@ typedef struct {
                              * it: every light of the shape is estimated from sample arrays of this size (directlighting.rs:51-64) */
 } pt_area_light;
 
+/* InfiniteAreaLight (src/lights/infinite.rs:273-293; "exinfinite" is an alias, lights/create_light.rs:29).  The environment map is a
+ * pyramid of images[] built as make_mipmap does (infinite.rs:44-67): read with no gamma decoding and no y flip, negative values clamped to
+ * 0, multiplied by "L" * "scale"; a light without "mapname" has a 1 x 1 pyramid of L * scale.  Its wraps are s repeat, t clamp
+ * (create_spectrum_mipmap, core/texture/mipmap.rs:1013-1025).  Passed with pt_scene_set_infinite_lights, not in pt_scene_desc, so that
+ * descriptors of earlier callers keep their size. */
+typedef struct {
+    float light_to_world[16];   /* row-major Transform.m of the CTM at the LightSource directive */
+    float world_to_light[16];   /* its stored inverse (Transform.m_inv) */
+    int32_t image;              /* index into pt_scene_desc.images: the map's pyramid, 3 channels */
+    int32_t n_samples;          /* "samples", else "nsamples" (default 1); 0 is read as 1, at most 4096 */
+    uint32_t light_index;       /* position in the scene's light list: the LightSource directive appends the light when it is read, area
+                                 * lights are appended as their shapes are created (scene_context.rs:1178-1188, :1300-1316); an index past
+                                 * the area lights appends it */
+    uint32_t reserved;
+} pt_infinite_light;
+
 /* TriangleMesh flags (src/shapes/triangle.rs:10-22). */
 #define PT_MESH_TWO_SIDED            1u  /* "twosided" shape param, default true (triangle.rs:707) */
 #define PT_MESH_REVERSE_ORIENTATION  2u
@@ -356,6 +372,10 @@ int       pt_abi_version(void);
 pt_status pt_set_data_dir(pt_context* ctx, const char* dir);
 
 /* ---- scene ------------------------------------------------------------ */
+/* The infinite lights of the NEXT pt_scene_upload only (copied; n = 0 clears them): the upload consumes them, so every upload of a
+ * scene with infinite lights is preceded by this call.  A scene with one runs the *_env kernels of the path, directlighting and whitted
+ * integrators (escaped rays add Le, next-event estimation samples the map). */
+pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_infinite_light* lights);
 pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* desc);
 pt_status pt_scene_info_get(const pt_context* ctx, pt_scene_info* out);
 
@@ -423,6 +443,14 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
  * when sample_f returns None (f/wi/pdf are then zero). */
 pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const float* wo, const float* u,
                          uint32_t flags, float* f_out, float* wi_out, float* pdf_out, uint32_t* type_out);
+/* Light `light` (index into the uploaded scene's light list) at n reference points ref_p (3 floats each), Light::sample_li for u (2 floats
+ * each): li_out 3 floats, wi_out 3 floats, pdf_out 1 float (0 when sample_li returns None).  Infinite and area lights. */
+pt_status pt_light_sample_li(pt_context* ctx, uint32_t light, uint32_t n, const float* ref_p, const float* u, float* li_out, float* wi_out,
+                             float* pdf_out);
+/* InfiniteAreaLight::pdf_li (infinite.rs:161-180) for n world directions wi (3 floats each).  Infinite lights only. */
+pt_status pt_light_pdf_li(pt_context* ctx, uint32_t light, uint32_t n, const float* wi, float* pdf_out);
+/* InfiniteAreaLight::le (infinite.rs:111-122) for n world ray directions d (3 floats each): rgb_out 3 floats.  Infinite lights only. */
+pt_status pt_light_le(pt_context* ctx, uint32_t light, uint32_t n, const float* d, float* rgb_out);
 /* Per-sample radiance (PathIntegrator::li after validate_radiance_result) for the
  * pixels of one tile: out is 3 floats per (pixel, sample), pixel-major. */
 pt_status pt_radiance_samples(pt_context* ctx, const pt_tile* tile, float* out_rgb);

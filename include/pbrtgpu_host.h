@@ -55,6 +55,8 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
 pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** out, char* err, size_t err_cap);
 /* The flattened scene; pointers stay valid until pth_scene_free. */
 const pt_scene_desc* pth_scene_get_desc(const pth_scene* s);
+/* The scene's LightSource "infinite" lights (for pt_scene_set_infinite_lights); *n receives their count.  Valid until pth_scene_free. */
+const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n);
 /* Film "filename" parameter (default "pbrt.exr"). */
 const char* pth_scene_output_filename(const pth_scene* s);
 /* Command-line overrides of the reference CLI (src/bin/pbrt.rs:234-244). */

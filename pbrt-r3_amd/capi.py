@@ -66,6 +66,11 @@ class pt_area_light(C.Structure):
     _fields_ = [("L", C.c_float * 3), ("two_sided", C.c_int32), ("n_samples", C.c_int32)]
 
 
+class pt_infinite_light(C.Structure):
+    _fields_ = [("light_to_world", C.c_float * 16), ("world_to_light", C.c_float * 16), ("image", C.c_int32), ("n_samples", C.c_int32),
+                ("light_index", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class pt_mesh(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("material", C.c_int32), ("area_light", C.c_int32), ("object", C.c_uint32)]
 
@@ -149,6 +154,7 @@ SYMBOLS = [
     "pt_film_device_xyzw", "pt_film_commit_xyzw", "pt_film_allreduce", "pt_film_add_xyzw", "pt_film_resolve_rgb", "pt_trace_closest", "pt_trace_any", "pt_trace_wavefront",
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
+    "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le",
 ]
 
 _lib = None
@@ -212,7 +218,8 @@ def tiles_array(tiles):
 
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
-                "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody"]
+                "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
+                "pth_scene_get_infinite_lights"]
 
 
 class ParsedScene:
@@ -244,6 +251,11 @@ class ParsedScene:
             raise PtError(st, err.value.decode())
         self.desc = L.pth_scene_get_desc(self.h).contents
         self.buffers = {}
+        L.pth_scene_get_infinite_lights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.pth_scene_get_infinite_lights.restype = C.POINTER(pt_infinite_light)
+        n_inf = C.c_uint32()
+        arr = L.pth_scene_get_infinite_lights(self.h, C.byref(n_inf))
+        self.infinite_lights = [arr[i] for i in range(n_inf.value)]       # LightSource "infinite" (copies)
 
     @property
     def output_filename(self):
@@ -320,6 +332,9 @@ class Context:
     def upload(self, scene):
         """scene: scenes.SceneDesc (keeps its numpy buffers alive)."""
         self._keep = scene
+        inf = list(getattr(scene, "infinite_lights", None) or [])
+        arr = (pt_infinite_light * max(1, len(inf)))(*inf)
+        self._check(self.lib.pt_scene_set_infinite_lights(self.h, C.c_uint32(len(inf)), arr if inf else None))
         self._check(self.lib.pt_scene_upload(self.h, C.byref(scene.desc)))
         info = pt_scene_info()
         self._check(self.lib.pt_scene_info_get(self.h, C.byref(info)))
@@ -438,6 +453,30 @@ class Context:
         self._check(self.lib.pt_bsdf_sample(self.h, C.c_uint32(material), C.c_uint32(n), _ptr(wo), _ptr(u), C.c_uint32(flags), _ptr(f), _ptr(wi),
                                             _ptr(pdf), _ptr(t)))
         return f, wi, pdf, t
+
+    def light_sample_li(self, light, ref_p, u):
+        """Light::sample_li of light `light` (index into the scene's light list): (Li, wi, pdf); pdf 0 where it returns None."""
+        ref_p = np.ascontiguousarray(ref_p, np.float32).reshape(-1, 3); u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = len(u)
+        if len(ref_p) == 1 and n > 1:
+            ref_p = np.ascontiguousarray(np.repeat(ref_p, n, axis=0))
+        li = np.empty((n, 3), np.float32); wi = np.empty((n, 3), np.float32); pdf = np.empty(n, np.float32)
+        self._check(self.lib.pt_light_sample_li(self.h, C.c_uint32(light), C.c_uint32(n), _ptr(ref_p), _ptr(u), _ptr(li), _ptr(wi), _ptr(pdf)))
+        return li, wi, pdf
+
+    def light_pdf_li(self, light, wi):
+        """InfiniteAreaLight::pdf_li for world directions wi."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        pdf = np.empty(len(wi), np.float32)
+        self._check(self.lib.pt_light_pdf_li(self.h, C.c_uint32(light), C.c_uint32(len(wi)), _ptr(wi), _ptr(pdf)))
+        return pdf
+
+    def light_le(self, light, d):
+        """InfiniteAreaLight::le for world ray directions d: RGB."""
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        out = np.empty((len(d), 3), np.float32)
+        self._check(self.lib.pt_light_le(self.h, C.c_uint32(light), C.c_uint32(len(d)), _ptr(d), _ptr(out)))
+        return out
 
     def radiance_samples(self, tile):
         t = pt_tile(*[int(v) for v in tile])

@@ -138,6 +138,8 @@ public:
     std::vector<pt_texture> textures;                                   // textures that depend on the hit: evaluated on the device
     std::map<std::string, uint32_t> node_float_textures, node_spectrum_textures;   // name -> index into textures
     std::vector<pt_area_light> area_lights;
+    std::vector<pt_infinite_light> infinite_lights;
+    uint32_t n_world_lights = 0;                                        // lights appended to the scene's list so far (area lights per primitive)
     bool any_n = false, any_s = false, any_uv = false;
     pt_scene_desc desc;
     std::string out_filename = "pbrt.exr";
@@ -408,8 +410,41 @@ public:
         if (it == gstates.back().named_materials.end()) { warn("NamedMaterial \"" + name + "\" unknown."); return; }
         gstates.back().material = it->second;
     }
-    void pbrt_light_source(const std::string& name, const ParamSet&) override {
-        fail("LightSource \"" + name + "\": only diffuse area lights are on the accelerated path");
+    void pbrt_light_source(const std::string& name, const ParamSet& p) override {
+        if (name != "infinite" && name != "exinfinite") {          // create_light.rs:29: "exinfinite" is the same light
+            fail("LightSource \"" + name + "\": only infinite lights and diffuse area lights are on the accelerated path");
+            return;
+        }
+        // create_infinite_light (lights/infinite.rs:273-293): L * scale, "mapname", "samples" falling back to "nsamples"
+        float L[3] = {1.0f, 1.0f, 1.0f}, sc[3] = {1.0f, 1.0f, 1.0f};
+        spectrum_from(p, "L", L);
+        spectrum_from(p, "scale", sc);
+        if (!error.empty()) return;
+        const float Ls[3] = {L[0] * sc[0], L[1] * sc[1], L[2] * sc[2]};
+        int ns = p.find_one_int("samples", p.find_one_int("nsamples", 1));
+        // the reference reads the count `as u32` and goes on; 0 is read as 1 downstream (only directlighting "all" sizes arrays by it)
+        if (ns < 0 || ns > 4096) { fail("LightSource \"" + name + "\": \"samples\" outside [0, 4096]"); return; }
+        if (quick_render) ns = std::max(ns / 4, 1);
+        std::string file = p.find_one_string("mapname", "");
+        pyramids.emplace_back(new Pyramid());
+        if (!file.empty()) {
+            if (file[0] != '/' && !p.base_dir.empty()) file = p.base_dir + "/" + file;
+            RgbImage img;
+            std::string ierr;
+            if (!read_image_file(file, &img, &ierr)) { fail("LightSource \"" + name + "\": " + ierr); return; }
+            build_env_pyramid(&img, Ls, pyramids.back().get());
+        } else {
+            build_env_pyramid(nullptr, Ls, pyramids.back().get());
+        }
+        pt_infinite_light il;
+        std::memset(&il, 0, sizeof(il));
+        const Xf& ctm = transforms.back().t[0];                    // light_to_world: the CTM at the directive
+        std::memcpy(il.light_to_world, ctm.m.a, 64);
+        std::memcpy(il.world_to_light, ctm.inv.a, 64);
+        il.image = (int32_t)pyramids.size() - 1;
+        il.n_samples = ns;
+        il.light_index = n_world_lights++;                          // appended to scene.lights as the directive is read
+        infinite_lights.push_back(il);
     }
     void pbrt_area_light_source(const std::string& name, const ParamSet& p) override {
         gstates.back().area_light_name = name;
@@ -667,6 +702,7 @@ public:
             sp.object = cur_object;
             sp.order = n_extra++;
             if (cur_object) sp.area_light = -1;                     // "Area lights not supported with object instancing" (:1302-1304)
+            if (sp.area_light >= 0) n_world_lights++;
             spheres.push_back(sp);
             return;
         }
@@ -752,7 +788,7 @@ public:
             tri_mesh.push_back(mesh_id);
             kept++;
         }
-        (void)kept;
+        if (mesh.area_light >= 0) n_world_lights += (uint32_t)kept;
         meshes.push_back(mesh);
         size_t old_nv = P.size() / 3;
         P.insert(P.end(), wp.begin(), wp.end());
@@ -978,6 +1014,10 @@ pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** o
     return finish(s, ok, perr, out, err, err_cap);
 }
 const pt_scene_desc* pth_scene_get_desc(const pth_scene* s) { return s ? &s->ctx.desc : nullptr; }
+const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n) {
+    if (n) *n = s ? (uint32_t)s->ctx.infinite_lights.size() : 0u;
+    return (s && !s->ctx.infinite_lights.empty()) ? s->ctx.infinite_lights.data() : nullptr;
+}
 const char* pth_scene_output_filename(const pth_scene* s) { return s ? s->ctx.out_filename.c_str() : ""; }
 void pth_scene_set_pixelsamples(pth_scene* s, int spp) { if (s && spp > 0) s->ctx.desc.spp = spp; }
 const char* pth_scene_warnings(const pth_scene* s) { return s ? s->ctx.warnings.c_str() : ""; }

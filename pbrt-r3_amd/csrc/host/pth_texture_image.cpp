@@ -506,6 +506,26 @@ void build_pyramid(const RgbImage& img, int channels, float scale, bool gamma, i
                 for (int k = 0; k < 3; k++) o[k] = (gamma ? inverse_gamma_correct(p[k]) : p[k]) * scale;
             }
         }
+    make_pyramid(data, channels, w, h, swrap, twrap, out);
+}
+
+// InfiniteAreaLight's make_mipmap (lights/infinite.rs:44-67): the file's RGB as read (no inverse gamma, no y flip), negative values
+// clamped to 0, times L (per channel); no file: one texel of L.  Then create_spectrum_mipmap (mipmap.rs:1013-1025): s repeat, t clamp.
+void build_env_pyramid(const RgbImage* img, const float L[3], Pyramid* out) {
+    std::vector<float> data;
+    int w = 1, h = 1;
+    if (img) {
+        w = img->width; h = img->height;
+        data.resize((size_t)3 * w * h);
+        for (size_t i = 0; i < (size_t)w * h; i++)
+            for (int k = 0; k < 3; k++) data[3 * i + k] = std::max(img->rgb[3 * i + k], 0.0f) * L[k];
+    } else {
+        data.assign(L, L + 3);
+    }
+    make_pyramid(data, 3, w, h, PT_WRAP_REPEAT, PT_WRAP_CLAMP, out);
+}
+
+void make_pyramid(const std::vector<float>& data, int channels, int w, int h, int swrap, int twrap, Pyramid* out) {
     int cw, ch;
     std::vector<float> level;
     resample(data, channels, w, h, swrap, twrap, &cw, &ch, &level);

@@ -17,5 +17,9 @@ bool read_image_file(const std::string& path, RgbImage* out, std::string* err);
 struct Pyramid { pt_image desc; std::vector<float> texels; };
 // ImageTexture::convert_in + flip_y + MIPMap::new: `channels` 1 (float texture: luminance) or 3.
 void build_pyramid(const RgbImage& img, int channels, float scale, bool gamma, int swrap, int twrap, Pyramid* out);
+// MIPMap::new over `channels` floats per texel, rows as given (resampled to powers of two with the wraps, then box-filtered levels).
+void make_pyramid(const std::vector<float>& data, int channels, int w, int h, int swrap, int twrap, Pyramid* out);
+// The environment map of LightSource "infinite" (lights/infinite.rs:44-67); img == nullptr: the 1 x 1 map of L.
+void build_env_pyramid(const RgbImage* img, const float L[3], Pyramid* out);
 
 }  // namespace pth

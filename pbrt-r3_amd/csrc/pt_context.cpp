@@ -21,6 +21,8 @@
 #include <array>
 #include <memory>
 #include <vector>
+#include <algorithm>
+#include <thread>
 
 #include "../../include/pbrtgpu.h"
 #include "pt_bvh.h"
@@ -63,6 +65,8 @@ struct pt_context {
     bool have_scene = false;
     PtScene sc;
     pt_scene_info info;
+    std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
+    DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
     std::vector<uint32_t> sobol_m32;
     std::vector<uint64_t> sobol_vdc, sobol_inv;
@@ -440,8 +444,110 @@ static void build_spheres(const pt_scene_desc* d, std::vector<PtSphere>& sph, st
 }
 }  // namespace
 
+// ---- InfiniteAreaLight on the host: MIPMap::lookup over a pyramid of pt_image (core/texture/mipmap.rs:503-544, :620-637, :711-765, s repeat,
+// t clamp) and make_distribution (lights/infinite.rs:69-91), rows built on the host's threads.
+namespace {
+struct EnvMap {
+    const pt_image* im;
+    std::vector<size_t> off;
+    explicit EnvMap(const pt_image& i) : im(&i) {
+        size_t o = 0;
+        uint32_t w = i.width, h = i.height;
+        for (uint32_t l = 0; l < i.n_levels; l++) { off.push_back(o); o += (size_t)w * h * i.channels; if (w > 1) w /= 2; if (h > 1) h /= 2; }
+    }
+    void dims(uint32_t l, int32_t* w, int32_t* h) const { uint32_t ww = im->width >> l, hh = im->height >> l; *w = (int32_t)(ww ? ww : 1u); *h = (int32_t)(hh ? hh : 1u); }
+    void texel(uint32_t l, int32_t s, int32_t t, float out[3]) const {
+        int32_t w, h;
+        dims(l, &w, &h);
+        s &= w - 1;                                                   // repeat
+        t = t < 0 ? 0 : (t > h - 1 ? h - 1 : t);                      // clamp
+        const float* d = im->texels + off[l] + ((size_t)t * (size_t)w + (size_t)s) * im->channels;
+        for (int k = 0; k < 3; k++) out[k] = d[im->channels == 1 ? 0 : k];
+    }
+    static int32_t f2i(float f) { return std::isnan(f) ? 0 : (f >= 2147483647.0f ? 2147483647 : (f <= -2147483648.0f ? (int32_t)0x80000000 : (int32_t)f)); }
+    void triangle(uint32_t l, float st0, float st1, float out[3]) const {
+        if (l > im->n_levels - 1) l = im->n_levels - 1;
+        int32_t w, h;
+        dims(l, &w, &h);
+        const float s = st0 * (float)w - 0.5f, t = st1 * (float)h - 0.5f;
+        const int32_t s0 = f2i(std::floor(s)), t0 = f2i(std::floor(t));
+        const float ds = s - (float)s0, dt = t - (float)t0;
+        float a[3], b[3], c[3], e[3];
+        texel(l, s0, t0, a); texel(l, s0, t0 + 1, b); texel(l, s0 + 1, t0, c); texel(l, s0 + 1, t0 + 1, e);
+        for (int k = 0; k < 3; k++)
+            out[k] = a[k] * ((1.0f - ds) * (1.0f - dt)) + b[k] * ((1.0f - ds) * dt) + c[k] * (ds * (1.0f - dt)) + e[k] * (ds * dt);
+    }
+    void lookup(float st0, float st1, float width, float out[3]) const {          // MIPMap::lookup (trilinear)
+        const float max_level = (float)(im->n_levels - 1);
+        const float level = max_level + std::log2(std::max(width, 1e-8f));
+        if (level < 0.0f) { triangle(0, st0, st1, out); return; }
+        if (level >= max_level) { texel(im->n_levels - 1, 0, 0, out); return; }
+        const uint32_t il = (uint32_t)std::floor(level);
+        const float delta = std::min(std::max(level - (float)il, 0.0f), 1.0f);
+        float a[3], b[3];
+        triangle(il, st0, st1, a); triangle(il + 1, st0, st1, b);
+        for (int k = 0; k < 3; k++) out[k] = (1.0f - delta) * a[k] + delta * b[k];
+    }
+};
+float rgb_y(const float c[3]) { return 0.212671f * c[0] + 0.715160f * c[1] + 0.072169f * c[2]; }
+// Distribution1D::new (distribution.rs:34-56) over func[0..n): cdf[0..n], returns func_int
+float dist1d_build(const float* func, uint32_t n, float* cdf) {
+    cdf[0] = 0.0f;
+    for (uint32_t i = 1; i < n + 1; i++) cdf[i] = cdf[i - 1] + func[i - 1] / (float)n;
+    const float func_int = cdf[n];
+    if (func_int == 0.0f) for (uint32_t i = 1; i < n + 1; i++) cdf[i] = (float)i / (float)n;
+    else for (uint32_t i = 1; i < n + 1; i++) cdf[i] /= func_int;
+    return func_int;
+}
+// make_distribution + Distribution2D::new: tables laid out as PtEnvLight reads them -- func [nv][nu], cdf [nv][nu+1], marginal func [nv], cdf [nv+1]
+void env_distribution(const pt_image& im, uint32_t* nu_out, uint32_t* nv_out, std::vector<float>* tabs, float* m_int) {
+    const EnvMap map(im);
+    const uint32_t nu = im.width * 2, nv = im.height * 2;
+    const float fwidth = 0.5f / (float)std::min(nu, nv);
+    tabs->assign((size_t)nv * nu + (size_t)nv * (nu + 1) + nv + (nv + 1), 0.0f);
+    float* func = tabs->data();
+    float* cdf = func + (size_t)nv * nu;
+    float* mfunc = cdf + (size_t)nv * (nu + 1);
+    float* mcdf = mfunc + nv;
+    const unsigned nt = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (unsigned k = 0; k < nt; k++)
+        th.emplace_back([&, k] {
+            for (uint32_t v = k; v < nv; v += nt) {
+                const float vp = ((float)v + 0.5f) / (float)nv;
+                const float sin_theta = std::sin(3.14159265358979323846f * vp);
+                for (uint32_t u = 0; u < nu; u++) {
+                    const float up = ((float)u + 0.5f) / (float)nu;
+                    float c[3];
+                    map.lookup(up, vp, fwidth, c);
+                    func[(size_t)v * nu + u] = std::max(rgb_y(c), 0.0f) * sin_theta;
+                }
+                mfunc[v] = dist1d_build(func + (size_t)v * nu, nu, cdf + (size_t)v * (nu + 1));
+            }
+        });
+    for (auto& t : th) t.join();
+    *m_int = dist1d_build(mfunc, nv, mcdf);
+    *nu_out = nu; *nv_out = nv;
+}
+}  // namespace
+
+pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_infinite_light* lights) {
+    if (!ctx || (n && !lights)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->inf_lights.assign(lights, lights + n);
+    return PT_OK;
+}
+
+static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d);
+// The infinite lights set with pt_scene_set_infinite_lights belong to this upload alone: a later upload of another scene does not inherit
+// them (their image indices point into this descriptor's images[]).
 pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (!ctx || !d) return PT_ERR_INVALID_ARGUMENT;
+    const pt_status st = scene_upload(ctx, d);
+    ctx->inf_lights.clear();
+    return st;
+}
+
+static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     (void)hipSetDevice(ctx->device);
     ctx->have_scene = false;
     // ---- validation (the kernels index these arrays unchecked)
@@ -524,6 +630,14 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f)
                 return ctx->fail(PT_ERR_UNSUPPORTED, "sphere under a projective transform (last matrix row must be 0 0 0 1)");
         }
+    }
+    for (const pt_infinite_light& il : ctx->inf_lights) {
+        if (il.image < 0 || (uint32_t)il.image >= d->n_images || !d->images) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: image index out of range");
+        const pt_image& im = d->images[il.image];
+        if (!im.texels || im.width == 0 || im.height == 0 || (im.width & (im.width - 1)) || (im.height & (im.height - 1)) || (im.channels != 1 && im.channels != 3) ||
+            im.n_levels == 0 || im.n_levels > PT_MAX_MIP_LEVELS || im.width > (1u << 14) || im.height > (1u << 14))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: its image is not a power-of-two pyramid of 1 or 3 channels (at most 16384 wide)");
+        if (il.n_samples < 0 || il.n_samples > 4096) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: n_samples outside [0, 4096]");
     }
     // integrator-specific refusals come after the index range checks above (they dereference materials[])
     if (d->integrator == PT_INTEGRATOR_PATH && d->sampler == PT_SAMPLER_HALTON && d->max_depth > 124)
@@ -1113,13 +1227,30 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (up_n_nodes >= (1u << 25)) return ctx->fail(PT_ERR_UNSUPPORTED, "more than 2^25 BVH nodes (32-bit node offsets)");
     ctx->n_nodes_up = up_n_nodes; ctx->n_tris_up = up_n_tris;
     if ((st = upload(ctx, ctx->d_materials, mats.data(), mats.size())) != PT_OK) return st;
+    {   // infinite lights: their records at their places in the light list (scene_context.rs:1178-1188), in directive order
+        std::vector<uint32_t> order(ctx->inf_lights.size());
+        for (uint32_t k = 0; k < order.size(); k++) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ctx->inf_lights[a].light_index < ctx->inf_lights[b].light_index; });
+        for (uint32_t k : order) {
+            PtLight L;
+            std::memset(&L, 0, sizeof(L));
+            std::memcpy(&L.p0[0], &k, 4);
+            L.mesh_flags = PT_LIGHT_INFINITE;
+            L.tri_rec = 0xffffffffu;
+            L.prim = 0xffffffffu;
+            L.n_samples = (uint32_t)std::max(1, ctx->inf_lights[k].n_samples);
+            const size_t at = std::min<size_t>(ctx->inf_lights[k].light_index, lights.size());
+            lights.insert(lights.begin() + (ptrdiff_t)at, L);
+        }
+    }
     ctx->light_samples_total = 0;
     for (const PtLight& L : lights) ctx->light_samples_total += L.n_samples;
     if ((st = upload(ctx, ctx->d_lights, lights.data(), lights.size())) != PT_OK) return st;
     if (d->n_spheres) { if ((st = upload(ctx, ctx->d_spheres, sph.data(), sph.size())) != PT_OK) return st; } else ctx->d_spheres.release();
     if (d->n_instances) { if ((st = upload(ctx, ctx->d_instances, dinst.data(), dinst.size())) != PT_OK) return st; } else ctx->d_instances.release();
     std::vector<PtImage> dimages(d->n_images);
-    if (any_textured && d->n_images) {           // all pyramids in one buffer
+    const bool images_on_device = (any_textured || !ctx->inf_lights.empty()) && d->n_images;
+    if (images_on_device) {           // all pyramids in one buffer
         size_t total = 0;
         for (uint32_t i = 0; i < d->n_images; i++) {
             const pt_image& im = d->images[i];
@@ -1177,7 +1308,7 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     sc.textured = any_textured ? 1u : 0u;
     sc.textures = any_textured ? ctx->d_textures.as<pt_texture>() : nullptr;
     sc.tex_prog = any_textured ? ctx->d_tex_prog.as<uint32_t>() : nullptr;
-    sc.images = (any_textured && d->n_images) ? ctx->d_images.as<PtImage>() : nullptr;
+    sc.images = images_on_device ? ctx->d_images.as<PtImage>() : nullptr;
     sc.mat_params = any_textured ? ctx->d_mat_params.as<PtMatParams>() : nullptr;
     sc.spheres = d->n_spheres ? ctx->d_spheres.as<PtSphere>() : nullptr;
     sc.instances = d->n_instances ? ctx->d_instances.as<PtInstance>() : nullptr;
@@ -1190,6 +1321,57 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     for (int a = 0; a < 3; a++) { const float ext = up_root_hi[a] - up_root_lo[a]; sc.cell_scale[a] = ext > 0.0f ? (float)(1u << PT_SORT_CELL_BITS) / ext : 0.0f; }
     std::memcpy(sc.wb_min, up_root_lo, 12);
     std::memcpy(sc.wb_max, up_root_hi, 12);
+    std::vector<float> env_power(ctx->inf_lights.size(), 0.0f);
+    sc.n_envs = 0;
+    if (!ctx->inf_lights.empty()) {      // PtEnvLight records + their Distribution2D tables (one buffer; its bytes are gone from what the path pool may take)
+        const size_t ne = ctx->inf_lights.size();
+        std::vector<PtEnvLight> envs(ne);
+        std::vector<std::vector<float>> tabs(ne);
+        std::vector<size_t> tab_off(ne);
+        size_t total = 0;
+        // Light::preprocess: Bounds3::bounding_sphere of the world bound (bounds3.rs:173-177), half the diagonal
+        const float dx = sc.wb_max[0] - sc.wb_min[0], dy = sc.wb_max[1] - sc.wb_min[1], dz = sc.wb_max[2] - sc.wb_min[2];
+        const float radius = std::sqrt(dx * dx + dy * dy + dz * dz) * 0.5f;
+        for (size_t k = 0; k < ne; k++) {
+            const pt_infinite_light& il = ctx->inf_lights[k];
+            PtEnvLight& e = envs[k];
+            std::memset(&e, 0, sizeof(e));
+            std::memcpy(e.l2w, il.light_to_world, 48);
+            std::memcpy(e.w2l, il.world_to_light, 48);
+            e.radius = radius;
+            e.image = (uint32_t)il.image;
+            env_distribution(d->images[il.image], &e.nu, &e.nv, &tabs[k], &e.m_int);
+            tab_off[k] = total;
+            total += (tabs[k].size() + 3) & ~(size_t)3;
+            // power (infinite.rs:100-109): pi r^2 * lookup((.5, .5), .5), its y() for the power strategy
+            const EnvMap map(d->images[il.image]);
+            float c[3];
+            map.lookup(0.5f, 0.5f, 0.5f, c);
+            const float s = 3.14159265358979323846f * radius * radius;
+            const float r = c[0] * s, g = c[1] * s, b = c[2] * s;
+            env_power[k] = 0.212671f * r + 0.715160f * g + 0.072169f * b;
+        }
+        std::vector<float> all(total);
+        for (size_t k = 0; k < ne; k++) std::memcpy(all.data() + tab_off[k], tabs[k].data(), tabs[k].size() * sizeof(float));
+        if ((st = upload(ctx, ctx->d_env_tabs, all.data(), all.size())) != PT_OK) return st;
+        for (size_t k = 0; k < ne; k++) {
+            PtEnvLight& e = envs[k];
+            const float* base = ctx->d_env_tabs.as<float>() + tab_off[k];
+            e.func = base;
+            e.cdf = e.func + (size_t)e.nv * e.nu;
+            e.mfunc = e.cdf + (size_t)e.nv * (e.nu + 1);
+            e.mcdf = e.mfunc + e.nv;
+        }
+        std::vector<uint8_t> lbuf(lights.size() * sizeof(PtLight) + ne * sizeof(PtEnvLight));       // the records behind the lights (scene_envs)
+        std::memcpy(lbuf.data(), lights.data(), lights.size() * sizeof(PtLight));
+        std::memcpy(lbuf.data() + lights.size() * sizeof(PtLight), envs.data(), ne * sizeof(PtEnvLight));
+        if ((st = upload(ctx, ctx->d_lights, lbuf.data(), lbuf.size())) != PT_OK) return st;
+        sc.lights = ctx->d_lights.as<PtLight>();
+        sc.n_envs = (uint32_t)ne;
+        // the hit records were numbered over the area lights alone: give every emitter its index in the merged list
+        PT_HIP(ptk_light_renumber(ctx->stream, ctx->d_tris.as<PtTri>(), ctx->d_tri_info.p ? ctx->d_tri_info.as<PtTriInfo>() : nullptr, sc.lights, (uint32_t)lights.size()));
+        PT_HIP(hipStreamSynchronize(ctx->stream));
+    } else { ctx->d_env_tabs.release(); }
     sc.max_depth = d->max_depth;
     sc.integrator = d->integrator;
     sc.direct_strategy = d->direct_strategy;
@@ -1330,7 +1512,11 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             std::vector<float> tab(g.stride + 16);
             for (uint32_t i = 0; i < nl; i++) {
                 if (strategy == PT_LIGHTS_UNIFORM) tab[i] = 1.0f;
-                else {
+                else if (lights[i].mesh_flags & PT_LIGHT_INFINITE) {
+                    uint32_t k;
+                    std::memcpy(&k, &lights[i].p0[0], 4);
+                    tab[i] = env_power[k];
+                } else {
                     float n = lights[i].two_sided ? 2.0f : 1.0f;
                     float s = n * lights[i].area * 3.14159265358979323846f;
                     float r = lights[i].L[0] * s, gg = lights[i].L[1] * s, b = lights[i].L[2] * s;
@@ -2184,6 +2370,41 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
     PT_HIP(hipMemcpy(f_out, d_f.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     PT_HIP(hipMemcpy(pdf_out, d_pdf.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+// Light hooks (k_light_hooks): mode 0 sample_li, 1 pdf_li, 2 le
+static pt_status light_hook(pt_context* ctx, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b, float* o3a, float* o3b, float* o1) {
+    if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (light >= ctx->sc.n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "light index out of range");
+    (void)hipSetDevice(ctx->device);
+    if (mode != 0) {
+        PtLight L;
+        PT_HIP(hipMemcpy(&L, ctx->d_lights.as<PtLight>() + light, sizeof(L), hipMemcpyDeviceToHost));
+        if (!(L.mesh_flags & PT_LIGHT_INFINITE)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_light_pdf_li / pt_light_le: not an infinite light");
+    }
+    if (n == 0) return PT_OK;
+    DevBuf d_a, d_b, d_3a, d_3b, d_1;
+    PT_HIP(d_a.alloc((size_t)n * 12)); PT_HIP(d_b.alloc((size_t)n * 8)); PT_HIP(d_3a.alloc((size_t)n * 12)); PT_HIP(d_3b.alloc((size_t)n * 12)); PT_HIP(d_1.alloc((size_t)n * 4));
+    PT_HIP(hipMemcpy(d_a.p, a, (size_t)n * 12, hipMemcpyHostToDevice));
+    if (b) PT_HIP(hipMemcpy(d_b.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
+    PT_HIP(ptk_light_hooks(ctx->stream, ctx->sc, light, mode, n, d_a.as<float>(), d_b.as<float>(), d_3a.as<float>(), d_3b.as<float>(), d_1.as<float>()));
+    PT_HIP(hipStreamSynchronize(ctx->stream));
+    if (o3a) PT_HIP(hipMemcpy(o3a, d_3a.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+    if (o3b) PT_HIP(hipMemcpy(o3b, d_3b.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+    if (o1) PT_HIP(hipMemcpy(o1, d_1.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+pt_status pt_light_sample_li(pt_context* ctx, uint32_t light, uint32_t n, const float* ref_p, const float* u, float* li_out, float* wi_out, float* pdf_out) {
+    if (!ctx || !ref_p || !u || !li_out || !wi_out || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
+    return light_hook(ctx, light, 0, n, ref_p, u, li_out, wi_out, pdf_out);
+}
+pt_status pt_light_pdf_li(pt_context* ctx, uint32_t light, uint32_t n, const float* wi, float* pdf_out) {
+    if (!ctx || !wi || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
+    return light_hook(ctx, light, 1, n, wi, nullptr, nullptr, nullptr, pdf_out);
+}
+pt_status pt_light_le(pt_context* ctx, uint32_t light, uint32_t n, const float* d, float* rgb_out) {
+    if (!ctx || !d || !rgb_out) return PT_ERR_INVALID_ARGUMENT;
+    return light_hook(ctx, light, 2, n, d, nullptr, rgb_out, nullptr, nullptr);
 }
 
 pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f_out, float* wi_out,

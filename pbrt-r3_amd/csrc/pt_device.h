@@ -185,6 +185,27 @@ struct PtInstance {              // 144 bytes
     uint32_t pad[3];
 };
 #define PT_LIGHT_SPHERE 0x80000000u   // PtLight::mesh_flags: the light's shape is sphere number bits(p0[0])
+#ifdef __HIPCC__
+#define PT_HOSTDEV_ENVS __host__ __device__
+#else
+#define PT_HOSTDEV_ENVS
+#endif
+#define PT_LIGHT_INFINITE 0x40000000u // PtLight::mesh_flags: an InfiniteAreaLight, side record PtScene::envs[bits(p0[0])]; tri_rec = ~0u
+// InfiniteAreaLight (lights/infinite.rs): its transforms, the world's bounding-sphere radius and the Distribution2D over its map
+// (core/sampling/distribution.rs:109-145), all tables in HBM.
+struct PtEnvLight {
+    float l2w[12];               // rows 0..2 of light_to_world.m
+    float w2l[12];               // rows 0..2 of its stored inverse
+    float radius;                // Bounds3::bounding_sphere of the world bound: half the diagonal (bounds3.rs:173-177)
+    uint32_t image;              // index into PtScene::images: the map (s repeat, t clamp)
+    uint32_t nu, nv;             // nv conditional distributions of nu entries each
+    const float* func;           // [nv][nu]
+    const float* cdf;            // [nv][nu + 1]
+    const float* mfunc;          // [nv]: the marginal's function (the conditionals' func_int)
+    const float* mcdf;           // [nv + 1]
+    float m_int;                 // the marginal's func_int
+    uint32_t pad[3];
+};
 
 struct PtCamera {
     float raster_to_camera[16];
@@ -261,7 +282,7 @@ struct PtScene {
     const PtSphere* spheres;
     const PtInstance* instances;
     uint32_t n_instances;        // > 0: k_trace_inst / k_shade_general_inst run
-    uint32_t pad_inst;
+    uint32_t n_envs;             // infinite lights (PtLight records with PT_LIGHT_INFINITE; side records: scene_envs); > 0: the *_env kernels run
     const pt_texture* textures;  // pt_scene_desc.textures as given
     const uint32_t* tex_prog;    // texture programs (pt_texture.h)
     const PtImage* images;       // MIP pyramids of the imagemap textures
@@ -283,6 +304,8 @@ struct PtScene {
     PtSobol sobol;
     PtLightGrid grid;
 };
+// The infinite lights' PtEnvLight records follow the n_lights PtLight records in the same buffer (PtScene keeps its size and layout).
+PT_HOSTDEV_ENVS inline const PtEnvLight* scene_envs(const PtScene& sc) { return reinterpret_cast<const PtEnvLight*>(sc.lights + sc.n_lights); }
 
 // ---- wavefront path pool (SoA, one slot per in-flight camera sample)
 struct PtPaths {

@@ -12,6 +12,9 @@ hipError_t ptk_trace_batch(hipStream_t st, int grid, const PtScene& sc, uint32_t
 hipError_t ptk_gen(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const uint32_t* pixels, uint32_t n_pix,
                    uint32_t s0, uint32_t n_samples, PtCounters* cnt);
 hipError_t ptk_nee_resolve(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q);
+hipError_t ptk_light_renumber(hipStream_t st, PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n);
+hipError_t ptk_light_hooks(hipStream_t st, const PtScene& sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b, float* o3a, float* o3b,
+                           float* o1);
 hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode);
 hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nee_split, int local_sort = 0);
 int ptk_nee_split_default();

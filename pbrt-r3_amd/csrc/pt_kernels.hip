@@ -2261,6 +2261,90 @@ PT_DEV bool light_sample_any(const PtScene& sc, const PtLight& l, V3 ref_p, V3 r
     return light_sample_li(l, ref_p, u, li, wi, pdf, lp, lperr, ln);
 }
 
+// ---- InfiniteAreaLight (lights/infinite.rs:94-189).  Its map is looked up as MIPMap::lookup(st, 0) does: width 0 is below level 0, so the
+// bilinear triangle filter on level 0 (mipmap.rs:620-637), s repeat, t clamp.
+PT_DEV V3 env_lookup0(const PtScene& sc, const PtEnvLight& e, V2 st) {
+    MipRef m;
+    m.im = &sc.images[e.image]; m.swrap = PT_WRAP_REPEAT; m.twrap = PT_WRAP_CLAMP;
+    return mip_triangle(m, 0u, st);
+}
+// Distribution1D::sample_continuous (distribution.rs:58-78): (value, pdf, offset)
+PT_DEV float dist1d_sample_continuous(const float* func, const float* cdf, uint32_t n, float func_int, float u, float* pdf, uint32_t* off) {
+    uint32_t first = 0, len = n + 1;                  // find_interval_cdf
+    while (len > 0) {
+        const uint32_t half = len >> 1, middle = first + half;
+        if (cdf[middle] <= u) { first = middle + 1; len -= half + 1; }
+        else len = half;
+    }
+    uint32_t idx = first == 0 ? 0 : first - 1;
+    if (idx > n - 1) idx = n - 1;
+    const float cdf0 = cdf[idx], cdf1 = cdf[idx + 1];
+    float du = u - cdf0;
+    const float span = cdf1 - cdf0;
+    if (span > 0.0f) du /= span;
+    *pdf = func_int > 0.0f ? func[idx] / func_int : 0.0f;
+    *off = idx;
+    return ((float)idx + du) * (1.0f / (float)n);
+}
+PT_DEV float spherical_theta_dev(V3 v) { return pt_acosf(clampf(v.z, -1.0f, 1.0f)); }         // geometry/misc.rs:96-104
+PT_DEV float spherical_phi_dev(V3 v) { const float p = pt_atan2f(v.y, v.x); return p < 0.0f ? p + 2.0f * PT_PI : p; }
+#define PT_INV_2PI (PT_INV_PI * 0.5f)
+// sample_li (infinite.rs:124-159) without the visibility tester: false where it returns None (map pdf <= 0); pdf 0 where sin(theta) == 0
+PT_DEV bool env_sample_li(const PtScene& sc, const PtEnvLight& e, V2 u, V3* li, V3* wi, float* pdf) {
+    float pdf0, pdf1;
+    uint32_t v, u_off;
+    const float d1 = dist1d_sample_continuous(e.mfunc, e.mcdf, e.nv, e.m_int, u.y, &pdf1, &v);          // Distribution2D::sample_continuous
+    const float d0 = dist1d_sample_continuous(e.func + (size_t)v * e.nu, e.cdf + (size_t)v * (e.nu + 1u), e.nu, e.mfunc[v], u.x, &pdf0, &u_off);
+    const float map_pdf = pdf0 * pdf1;
+    if (map_pdf <= 0.0f) return false;
+    const float theta = d1 * PT_PI, phi = d0 * 2.0f * PT_PI;
+    float sin_t, cos_t, sin_p, cos_p;
+    pt_sincosf(theta, &sin_t, &cos_t);
+    pt_sincosf(phi, &sin_p, &cos_p);
+    sin_t = clampf(sin_t, 0.0f, 1.0f);                                   // Q29
+    *wi = sph_vector(e.l2w, mk3(sin_t * cos_p, sin_t * sin_p, cos_t));
+    *pdf = sin_t == 0.0f ? 0.0f : map_pdf / (2.0f * PT_PI * PT_PI * sin_t);
+    *li = env_lookup0(sc, e, mk2(d0, d1));
+    return true;
+}
+// Distribution2D::pdf (distribution.rs:139-145): `as usize` saturates (NaN -> 0), then the clamp
+PT_DEV uint32_t dist_cell(float x, uint32_t n) { return !(x > 0.0f) ? 0u : (x >= (float)n ? n - 1u : min((uint32_t)x, n - 1u)); }
+PT_DEV float env_pdf_li(const PtEnvLight& e, V3 w) {                // pdf_li (infinite.rs:161-180)
+    const V3 wl = sph_vector(e.w2l, w);
+    const float theta = spherical_theta_dev(wl), phi = spherical_phi_dev(wl);
+    float sin_t, cos_t;
+    pt_sincosf(theta, &sin_t, &cos_t);
+    sin_t = clampf(sin_t, 0.0f, 1.0f);
+    if (sin_t == 0.0f) return 0.0f;
+    const uint32_t iu = dist_cell(phi * PT_INV_2PI * (float)e.nu, e.nu), iv = dist_cell(theta * PT_INV_PI * (float)e.nv, e.nv);
+    return e.func[(size_t)iv * e.nu + iu] / e.m_int / (2.0f * PT_PI * PT_PI * sin_t);
+}
+PT_DEV V3 env_le(const PtScene& sc, const PtEnvLight& e, V3 d) {     // le (infinite.rs:111-122)
+    const V3 w = normalize(sph_vector(e.w2l, d));
+    return env_lookup0(sc, e, mk2(spherical_phi_dev(w) * PT_INV_2PI, spherical_theta_dev(w) * PT_INV_PI));
+}
+// What every infinite light of the scene returns for a ray that leaves it (path.rs:86-98, directlighting.rs:112-122)
+PT_DEV V3 env_le_all(const PtScene& sc, V3 d) {
+    V3 r = mk3(0.0f, 0.0f, 0.0f);
+    for (uint32_t k = 0; k < sc.n_envs; k++) r = r + env_le(sc, scene_envs(sc)[k], d);
+    return r;
+}
+// Light::sample_li of any light kind; an infinite light's visibility target is p + wi * 2r, an interaction without error or normal
+template <bool SPH, bool ENV>
+PT_DEV bool light_sample_kind(const PtScene& sc, const PtLight& l, V3 ref_p, V3 ref_pe, V3 ref_n, V2 u, V3* li, V3* wi, float* pdf, V3* lp, V3* lperr,
+                              V3* ln) {
+    if constexpr (ENV) {
+        if (l.mesh_flags & PT_LIGHT_INFINITE) {
+            const PtEnvLight& e = scene_envs(sc)[__float_as_uint(l.p0[0])];
+            if (!env_sample_li(sc, e, u, li, wi, pdf)) return false;
+            *lp = ref_p + *wi * (2.0f * e.radius);
+            *lperr = mk3(0.0f, 0.0f, 0.0f); *ln = mk3(0.0f, 0.0f, 0.0f);
+            return true;
+        }
+    }
+    return light_sample_any<SPH>(sc, l, ref_p, ref_pe, ref_n, u, li, wi, pdf, lp, lperr, ln);
+}
+
 // ---- light distribution lookup (spatial.rs:84-111 + distribution.rs:12-31, :88-106)
 PT_DEV const float* grid_lookup(const PtLightGrid& g, V3 p) {
     if (g.single) return g.data;   // uniform / power: one table for every point
@@ -2334,6 +2418,29 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_nee_resolve(PtScene sc,
         if (nee & PT_NEE_PROBE) {
             const int32_t best = P.probe_rec[p];
             if (best >= 0 && (uint32_t)best == sc.lights[nee >> 8].tri_rec) { float4 B = P.pendB[p]; ld = ld + mk3(B.x, B.y, B.z); }
+        }
+        V3 ldn = ld / A.w;
+        float4 pb = P.pbeta[p];
+        float4 L = P.L[p];
+        V3 add = mk3(pb.x, pb.y, pb.z) * ldn;
+        L.x += add.x; L.y += add.y; L.z += add.z;
+        P.L[p] = L;
+    }
+}
+// Scenes with an infinite light: for that light B counts when the probe ray escaped (sample_lights.rs:444-446).
+extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_nee_resolve_env(PtScene sc, PtPaths P, PtQueues Q) {
+    const uint32_t n = Q.counts[PT_Q_NEE];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t p = Q.nee[i];
+        const uint32_t nee = P.nee[p];
+        const float4 A = P.pendA[p];
+        V3 ld = mk3(0.0f, 0.0f, 0.0f);
+        if ((nee & PT_NEE_SHADOW) && P.occluded[p] == 0) ld = ld + mk3(A.x, A.y, A.z);
+        if (nee & PT_NEE_PROBE) {
+            const int32_t best = P.probe_rec[p];
+            const PtLight& lt = sc.lights[nee >> 8];
+            const bool take = (lt.mesh_flags & PT_LIGHT_INFINITE) ? best < 0 : (best >= 0 && (uint32_t)best == lt.tri_rec);
+            if (take) { float4 B = P.pendB[p]; ld = ld + mk3(B.x, B.y, B.z); }
         }
         V3 ldn = ld / A.w;
         float4 pb = P.pbeta[p];
@@ -2619,7 +2726,8 @@ PT_DEV float opaque_zero() { float z = 0.0f; asm volatile("" : "+v"(z)); return 
 // shadow / probe rays, the pending terms and -- for every vertex with a BSDF -- the nee word, whose PT_NEE_DIMS bits tell part 2 how many
 // sample dimensions were drawn); 2 = everything else (emission, pass-through, continuation, Russian roulette), run AFTER part 1 on the same
 // list because it overwrites the ray.  Both halves rebuild the interaction from (ray, record): the split trades that for register room.
-template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0>
+// ENV: the scene has an infinite light (the *_env kernels): escaped rays add its Le, next-event estimation samples it.
+template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false>
 PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, const uint32_t* list, uint32_t begin, uint32_t end,
                        uint32_t* ticket) {
     __shared__ unsigned long long s_vert;
@@ -2799,6 +2907,14 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 pf_st = P.state[pf_p]; pf_idx = P.sobol_index[pf_p]; pf_pk = P.pixel[pf_p];
                 if constexpr (DEEP) { pf_ro = P.ray_o[pf_p]; pf_rd = P.ray_d[pf_p]; pf_beta = P.beta[pf_p]; }
             }
+            if constexpr (ENV && PART != 1) {         // a ray that left the scene: every infinite light's Le (path.rs:86-98)
+                if (rec < 0 && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
+                    const V3 add = beta * env_le_all(sc, rd);
+                    float4 L = P.L[p];
+                    L.x += add.x; L.y += add.y; L.z += add.z;
+                    P.L[p] = L;
+                }
+            }
             // emitted radiance at the first vertex / after a specular bounce (path.rs:87-98)
             if (PART != 1 && found && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
                 int32_t li = s.light;
@@ -2950,7 +3066,10 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             V3 A = mk3(0.0f, 0.0f, 0.0f), B = mk3(0.0f, 0.0f, 0.0f);
                             V3 li, wi, lp, lperr, ln;
                             float lpdf;
-                            if (light_sample_any<SPH>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln)) {
+                            bool sampled;
+                            if constexpr (ENV) sampled = light_sample_kind<SPH, true>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
+                            else sampled = light_sample_any<SPH>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
+                            if (sampled) {
                                 if (lpdf > 0.0f && !is_black(li)) {
                                     V3 f = eval_f(s.wo, wi) * abs_dot(wi, s.sh_n);
                                     float spdf = eval_pdf(s.wo, wi);
@@ -2979,6 +3098,24 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 if (!is_black(f) && spdf2 > 0.0f) {
                                     // light.pdf_li -> Shape::pdf_from (shape.rs:40-54): one test against the light's own triangle
                                     V3 po = offset_ray_origin(s.p, s.p_error, s.n, wi2);
+                                    bool env_done = false;
+                                    if constexpr (ENV) {
+                                        if (lt.mesh_flags & PT_LIGHT_INFINITE) {      // pdf_li of the map; B counts when the probe escapes (k_nee_resolve_env)
+                                            env_done = true;
+                                            const PtEnvLight& e = scene_envs(sc)[__float_as_uint(lt.p0[0])];
+                                            const float lp2 = env_pdf_li(e, wi2);
+                                            if (lp2 != 0.0f) {
+                                                const float weight = power_heuristic(spdf2, lp2);
+                                                const V3 le = env_le(sc, e, wi2);
+                                                B = f * le * 1.0f * (weight / spdf2);
+                                                s_stage[2][threadIdx.x] = make_float4(po.x, po.y, po.z, PT_INF);
+                                                s_stage[3][threadIdx.x] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                                                wr |= 8u; PT_COMMIT_NOW(2);
+                                                nee |= PT_NEE_PROBE;
+                                            }
+                                        }
+                                    }
+                                    if (!env_done) {
                                     Surf ls;
                                     float lt_t;
                                     bool lhit;
@@ -3005,6 +3142,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                             wr |= 8u; PT_COMMIT_NOW(2);
                                             nee |= PT_NEE_PROBE;
                                         }
+                                    }
                                     }
                                 }
                             }
@@ -3257,6 +3395,15 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_s
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_all_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
+// Scenes with an infinite light (LightSource "infinite"): one kernel over the unsorted shade queue, misses included -- a path whose ray left the
+// scene is shaded here before its slot is recycled (its Le at bounce 0 / after a specular bounce).  The lobe-list form with spheres and per-hit
+// textures covers every material; _inst adds the instance-space reconstruction (scenes with ObjectInstance).
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_env(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, false, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_env_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, true, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
 
 // ============================================================ film
 PT_DEV V3 validate_radiance(V3 l) {    // sampler.rs:151-176
@@ -3404,7 +3551,7 @@ PT_DEV void light_grid_voxel(const PtLightGrid& g, uint32_t v, V3* vmin, V3* vma
 constexpr int kGridBatch = 64;            // (voxel, light) pairs a workgroup takes at a time
 // vox_list: the voxels whose tables rows 0 .. n_vox-1 of `data` receive (the lazily filled grid: the voxels a bounce has touched for the first time);
 // nullptr: row k is voxel k (the dense grid, filled at upload).
-template <bool SPH>
+template <bool SPH, bool ENV = false>
 PT_DEV void light_grid_sums(const PtScene& sc, float* data, uint32_t n_vox, const uint32_t* vox_list) {
     __shared__ float s_term[kGridBatch][129];
     __shared__ float s_box[kGridBatch][6];
@@ -3433,7 +3580,10 @@ PT_DEV void light_grid_sums(const PtScene& sc, float* data, uint32_t n_vox, cons
             V3 li, wi, lp, le, ln;
             float pdf, term = 0.0f;
             // the reference point is a bare Interaction: zero normal and error (spatial.rs:152-159)
-            if (light_sample_any<SPH>(sc, sc.lights[j], po, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), u, &li, &wi, &pdf, &lp, &le, &ln))
+            bool sampled;
+            if constexpr (ENV) sampled = light_sample_kind<SPH, true>(sc, sc.lights[j], po, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), u, &li, &wi, &pdf, &lp, &le, &ln);
+            else sampled = light_sample_any<SPH>(sc, sc.lights[j], po, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), u, &li, &wi, &pdf, &lp, &le, &ln);
+            if (sampled)
                 if (pdf > 0.0f) term = lum_y(li) / pdf;
             s_term[b][i] = term;
         }
@@ -3469,6 +3619,7 @@ PT_DEV void light_grid_cdf(const PtScene& sc, float* data, uint32_t n_vox) {
 }
 extern "C" __global__ __launch_bounds__(128) void k_light_grid(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<false>(sc, data, n_vox, vox_list); }
 extern "C" __global__ __launch_bounds__(128) void k_light_grid_sph(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true>(sc, data, n_vox, vox_list); }
+extern "C" __global__ __launch_bounds__(128) void k_light_grid_env(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true, true>(sc, data, n_vox, vox_list); }
 // ---- the lazily filled grid (PtLightGrid::row_of; SpatialLightDistribution::lookup, spatial.rs:199-260, fills a voxel on its first touch).
 // Before a bounce is shaded, k_grid_mark rebuilds every hit of the bounce's queue exactly as the shading kernels will (same interaction point,
 // same voxel arithmetic) and lists the voxels nobody has asked for yet; the host gives them rows, k_light_grid fills those, k_grid_assign
@@ -3557,6 +3708,30 @@ PT_DEV GBsdf canonical_bsdf(const PtScene& sc, uint32_t material) {
     gb.n_lobes = sc.materials[material].n_lobes;
     return gb;
 }
+// Light hooks (pt_light_sample_li / pt_light_pdf_li / pt_light_le): mode 0 sample_li (a: ref points, b: u; o3a: Li, o3b: wi, o1: pdf),
+// 1 pdf_li of an infinite light (a: wi; o1), 2 its le (a: d; o3a)
+extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_hooks(PtScene sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b,
+                                                                    float* o3a, float* o3b, float* o1) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PtLight& lt = sc.lights[light];
+    const V3 va = mk3(a[3 * i], a[3 * i + 1], a[3 * i + 2]);
+    if (mode == 0) {
+        V3 li = mk3(0.0f, 0.0f, 0.0f), wi = li, lp, lperr, ln;
+        float pdf = 0.0f;
+        if (!light_sample_kind<true, true>(sc, lt, va, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), mk2(b[2 * i], b[2 * i + 1]), &li, &wi, &pdf, &lp, &lperr, &ln)) {
+            li = mk3(0.0f, 0.0f, 0.0f); wi = li; pdf = 0.0f;
+        }
+        o3a[3 * i] = li.x; o3a[3 * i + 1] = li.y; o3a[3 * i + 2] = li.z;
+        o3b[3 * i] = wi.x; o3b[3 * i + 1] = wi.y; o3b[3 * i + 2] = wi.z;
+        o1[i] = pdf;
+        return;
+    }
+    const PtEnvLight& e = scene_envs(sc)[__float_as_uint(lt.p0[0])];
+    if (mode == 1) { o1[i] = env_pdf_li(e, va); return; }
+    const V3 le = env_le(sc, e, va);
+    o3a[3 * i] = le.x; o3a[3 * i + 1] = le.y; o3a[3 * i + 2] = le.z;
+}
 extern "C" __global__ void k_bsdf_eval(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         GBsdf gb = canonical_bsdf(sc, material);
@@ -3639,7 +3814,8 @@ PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t ins
 PT_DEV float4* rec_frame(const PtRec& R, uint32_t depth, uint32_t k, uint32_t p) { return R.frames + ((size_t)depth * PT_REC_FRAME_F4 + k) * R.n_paths + p; }
 // estimate_direct (sample_lights.rs:178-328) for light `light_num`: the two MIS terms and their rays go to entry e, the rays' results
 // are combined by k_rec_next.  Returns the PT_NEE_* flags of the entry.
-template <bool FULL>
+// ENV: the scene has an infinite light (k_rec_enter_env): its map is sampled, B counts when the probe escapes (k_rec_next_env)
+template <bool FULL, bool ENV = false>
 PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const RecNode& nd, uint32_t light_num, V2 u_light, V2 u_scat, uint32_t e, float divisor = 1.0f) {
     const Surf& s = nd.s;
     const PtLight& lt = sc.lights[light_num];
@@ -3648,7 +3824,10 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
     V3 A = mk3(0.0f, 0.0f, 0.0f), B = A;
     V3 li, wi, lp, lperr, ln;
     float lpdf;
-    if (light_sample_any<FULL>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln)) {
+    bool sampled;
+    if constexpr (ENV) sampled = light_sample_kind<FULL, true>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
+    else sampled = light_sample_any<FULL>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
+    if (sampled) {
         if (lpdf > 0.0f && !is_black(li)) {
             V3 f = gbsdf_f(nd.gb, s.wo, wi, kNoSpec) * abs_dot(wi, s.sh_n);
             float spdf = gbsdf_pdf(nd.gb, s.wo, wi, kNoSpec);
@@ -3673,7 +3852,23 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
             V3 po = offset_ray_origin(s.p, s.p_error, s.n, wi2);
             Surf ls;
             float lt_t;
-            if (make_surf_any<FULL>(sc, po, wi2, lt.tri_rec, ls, &lt_t)) {          // light.pdf_li -> Shape::pdf_from (shape.rs:40-54)
+            bool env_done = false;
+            if constexpr (ENV) {
+                if (lt.mesh_flags & PT_LIGHT_INFINITE) {            // InfiniteAreaLight::pdf_li; B from le(wi) before the probe is traced
+                    env_done = true;
+                    const PtEnvLight& en = scene_envs(sc)[__float_as_uint(lt.p0[0])];
+                    const float lp2 = env_pdf_li(en, wi2);
+                    if (lp2 != 0.0f) {
+                        const float weight = power_heuristic(spdf2, lp2);
+                        const V3 le = env_le(sc, en, wi2);
+                        B = f * le * 1.0f * (weight / spdf2);
+                        R.pr_o[e] = make_float4(po.x, po.y, po.z, PT_INF);
+                        R.pr_d[e] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                        nee |= PT_NEE_PROBE;
+                    }
+                }
+            }
+            if (!env_done && make_surf_any<FULL>(sc, po, wi2, lt.tri_rec, ls, &lt_t)) {          // light.pdf_li -> Shape::pdf_from (shape.rs:40-54)
                 float lp2 = distance_squared(s.p, ls.p) / (abs_dot(ls.n, -wi2) * lt.area);
                 if (isinf(lp2)) lp2 = 0.0f;
                 if (lp2 != 0.0f) {
@@ -3721,7 +3916,7 @@ PT_DEV RayDiffs rec_load_diff(const PtRec& R, uint32_t p) {
     d.rx_d = f4_3(R.diff[2 * (size_t)R.n_paths + p]); d.ry_d = f4_3(R.diff[3 * (size_t)R.n_paths + p]);
     return d;
 }
-template <bool FULL>
+template <bool FULL, bool ENV = false>
 PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtQueues& Qn, const PtRec& R, PtCounters* cnt) {
     const uint32_t n = Q.counts[PT_Q_CUR];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3776,7 +3971,10 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                     V3 A = mk3(0.0f, 0.0f, 0.0f);
                     V3 li, wi, lp, lperr, ln;
                     float lpdf;
-                    if (light_sample_any<FULL>(sc, lt, nd.s.p, nd.s.p_error, nd.s.n, u, &li, &wi, &lpdf, &lp, &lperr, &ln) && !(lpdf <= 0.0f || is_black(li))) {
+                    bool sampled;
+                    if constexpr (ENV) sampled = light_sample_kind<FULL, true>(sc, lt, nd.s.p, nd.s.p_error, nd.s.n, u, &li, &wi, &lpdf, &lp, &lperr, &ln);
+                    else sampled = light_sample_any<FULL>(sc, lt, nd.s.p, nd.s.p_error, nd.s.n, u, &li, &wi, &lpdf, &lp, &lperr, &ln);
+                    if (sampled && !(lpdf <= 0.0f || is_black(li))) {
                         V3 f = gbsdf_f(nd.gb, nd.s.wo, wi, PT_BSDF_ALL);
                         if (!is_black(f)) {
                             V3 origin = offset_ray_origin(nd.s.p, nd.s.p_error, nd.s.n, lp - nd.s.p);
@@ -3808,13 +4006,13 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                                 for (uint32_t k = 0; k < n; k++) {
                                     const uint64_t idx = n == 1u ? sm.index : sampler_index(sc, sample_num * n + k, sm.px, sm.py);
                                     const V2 u = mk2(sample_dimension(sc, idx, 5u, sm.px, sm.py), sample_dimension(sc, idx, 6u, sm.px, sm.py));
-                                    rec_estimate_direct<FULL>(sc, R, nd, j, u, u, e0 + off + k, (float)n);
+                                    rec_estimate_direct<FULL, ENV>(sc, R, nd, j, u, u, e0 + off + k, (float)n);
                                 }
                             } else {
                                 arr = R.n_arrays;
                                 const V2 u_light = sm.get_2d(sc);
                                 const V2 u_scat = sm.get_2d(sc);
-                                rec_estimate_direct<FULL>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f);
+                                rec_estimate_direct<FULL, ENV>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f);
                                 for (uint32_t k = 1; k < n; k++) R.flags[e0 + off + k] = 0u;
                             }
                             off += n;
@@ -3827,7 +4025,7 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                         const float light_pdf = 1.0f / (float)sc.n_lights;
                         const V2 u_light = sm.get_2d(sc);
                         const V2 u_scat = sm.get_2d(sc);
-                        rec_estimate_direct<FULL>(sc, R, nd, light_num, u_light, u_scat, e0);
+                        rec_estimate_direct<FULL, ENV>(sc, R, nd, light_num, u_light, u_scat, e0);
                         float4 a = R.A[e0];
                         a.w = light_pdf;
                         R.A[e0] = a;
@@ -3844,6 +4042,12 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
             *rec_frame(R, depth, 4, p) = make_float4(rdf.rx_d.x, rdf.rx_d.y, rdf.rx_d.z, 0.0f);
             *rec_frame(R, depth, 5, p) = make_float4(rdf.ry_d.x, rdf.ry_d.y, rdf.ry_d.z, 0.0f);
             *rec_frame(R, depth, 6, p) = make_float4(l.x, l.y, l.z, 0.0f);
+        }
+        if constexpr (ENV) {           // what the node returns when it ends here: the lights' le(ray) for a ray that left the scene
+            if (outcome == PT_REC_OUT_RETURN0) {          // (directlighting.rs:112-122, whitted.rs:86-96); k_rec_next_env reads it from the free frame slot
+                const V3 le = nd.found ? mk3(0.0f, 0.0f, 0.0f) : (rec < 0 ? env_le_all(sc, rd) : mk3(0.0f, 0.0f, 0.0f));
+                *rec_frame(R, depth, 6, p) = make_float4(le.x, le.y, le.z, 0.0f);
+            }
         }
         P.state[p] = (dim & 0xffffu) | (depth << 16) | ((flags | (outcome << 2)) << 24);
         if (outcome == PT_REC_OUT_FRAME) {
@@ -3893,6 +4097,10 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_r
 }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_plain(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
     rec_enter_body<false>(sc, P, Q, Qn, R, cnt);
+}
+// scenes with an infinite light
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_env(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+    rec_enter_body<true, true>(sc, P, Q, Qn, R, cnt);
 }
 // specular_reflect / specular_transmit at the frame `depth` (sampler.rs:37-143): true = a child ray was set up (cur ray, differentials, pending f / scale)
 template <bool FULL>
@@ -3964,7 +4172,7 @@ PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R
     *pend_scale = wi_ns / pdf;
     return true;
 }
-template <bool FULL>
+template <bool FULL, bool ENV = false>
 PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtRec& R) {
     const uint32_t n = Q.counts[PT_Q_CUR];
     const uint32_t lane = threadIdx.x & 63;
@@ -4010,6 +4218,7 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
                 sm.py = (int32_t)(pk >> 16) + sc.film.sample_bounds[1];
                 V3 v = mk3(0.0f, 0.0f, 0.0f);       // the value a finished node hands to its parent
                 bool returning = outcome == PT_REC_OUT_RETURN0;
+                if constexpr (ENV) { if (returning) v = f4_3(*rec_frame(R, depth, 6, p)); }     // k_rec_enter_env left the escaped ray's le there
                 int32_t d = returning ? (int32_t)depth - 1 : (int32_t)depth;
                 uint32_t phase = 0;                  // of the frame d when not returning: 0 = sample reflect next, 1 = sample transmit next
                 V3 l = mk3(0.0f, 0.0f, 0.0f);
@@ -4042,7 +4251,12 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
                                 if ((fl & PT_NEE_SHADOW) && R.occ[e] == 0) est = est + f4_3(R.A[e]);
                                 if (fl & PT_NEE_PROBE) {
                                     const int32_t best = R.prec[e];
-                                    if (best >= 0 && (uint32_t)best == sc.lights[fl >> 8].tri_rec) est = est + f4_3(R.B[e]);
+                                    if constexpr (ENV) {
+                                        const PtLight& lt = sc.lights[fl >> 8];
+                                        if ((lt.mesh_flags & PT_LIGHT_INFINITE) ? best < 0 : (best >= 0 && (uint32_t)best == lt.tri_rec)) est = est + f4_3(R.B[e]);
+                                    } else {
+                                        if (best >= 0 && (uint32_t)best == sc.lights[fl >> 8].tri_rec) est = est + f4_3(R.B[e]);
+                                    }
                                 }
                                 ld = ld + est;
                             }
@@ -4113,6 +4327,7 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
 }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true>(sc, P, Q, R); }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_plain(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<false>(sc, P, Q, R); }
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_env(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true>(sc, P, Q, R); }
 hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtRec& R, uint32_t n) {
     hipLaunchKernelGGL(k_rec_init, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, R, n);
     return hipGetLastError();
@@ -4120,12 +4335,14 @@ hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPat
 hipError_t ptk_rec_enter(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtQueues& Qn, const PtRec& R, PtCounters* cnt,
                          uint32_t lights_per_node) {
     (void)lights_per_node;
-    if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_enter, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
+    if (sc.n_envs) hipLaunchKernelGGL(k_rec_enter_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
+    else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_enter, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     else hipLaunchKernelGGL(k_rec_enter_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     return hipGetLastError();
 }
 hipError_t ptk_rec_next(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtRec& R) {
-    if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_next, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
+    if (sc.n_envs) hipLaunchKernelGGL(k_rec_next_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
+    else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_next, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     else hipLaunchKernelGGL(k_rec_next_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     return hipGetLastError();
 }
@@ -4160,7 +4377,27 @@ hipError_t ptk_trace(hipStream_t st, int grid, int grid_dist, const PtScene& sc,
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_nee_resolve(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q) {
-    hipLaunchKernelGGL(k_nee_resolve, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
+    if (sc.n_envs) hipLaunchKernelGGL(k_nee_resolve_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
+    else hipLaunchKernelGGL(k_nee_resolve, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
+    return PT_LAUNCH_CHECK();
+}
+// Scenes with an infinite light: an area light's index moves up by the infinite lights put before it in the light list; the hit records
+// (light1, tri_info.light) were numbered without them
+extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_renumber(PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || (lights[i].mesh_flags & PT_LIGHT_INFINITE)) return;
+    const uint32_t r = lights[i].tri_rec;
+    tris[r].light1 = i + 1u;
+    if (tinfo) tinfo[r].light = (int32_t)i;
+}
+hipError_t ptk_light_renumber(hipStream_t st, PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_light_renumber, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, tris, tinfo, lights, n);
+    return PT_LAUNCH_CHECK();
+}
+hipError_t ptk_light_hooks(hipStream_t st, const PtScene& sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b, float* o3a, float* o3b,
+                           float* o1) {
+    hipLaunchKernelGGL(k_light_hooks, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, light, mode, n, a, b, o3a, o3b, o1);
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_trace_batch(hipStream_t st, int grid, const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out,
@@ -4306,6 +4543,13 @@ hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode) {
 }
 int ptk_nee_split_default() { return PT_NEE_SPLIT_DEFAULT; }
 hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nsplit, int local_sort) {
+    if (sc.n_envs) {
+        // an infinite light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort, the split next-event kernels
+        // (PBRTGPU_NEE_SPLIT), the local sort (PBRTGPU_SHADE_LOCAL), the textured split (PBRTGPU_TEX_SPLIT) and PBRTGPU_SHADE_UNSORTED are routed around
+        if (sc.n_instances) hipLaunchKernelGGL(k_shade_env_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        else hipLaunchKernelGGL(k_shade_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        return PT_LAUNCH_CHECK();
+    }
     if (sc.general_materials && local_sort && !sc.n_instances && sc.textured && !sc.n_spheres && P.tex_res) {
         // ... with textured materials: the texture half over the same list (it passes over the untextured entries), then the lobe-list kernel that
         // takes a textured hit's parameters from what the texture half left
@@ -4403,7 +4647,8 @@ hipError_t ptk_light_grid(hipStream_t st, const PtScene& sc, float* data, uint32
     if (jobs == 0) return hipSuccess;
     const uint64_t batches = (jobs + 63) / 64;          // kGridBatch pairs each
     const uint32_t grid = (uint32_t)(batches < 2048u ? batches : 2048u);
-    if (sc.n_spheres) hipLaunchKernelGGL(k_light_grid_sph, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
+    if (sc.n_envs) hipLaunchKernelGGL(k_light_grid_env, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
+    else if (sc.n_spheres) hipLaunchKernelGGL(k_light_grid_sph, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
     else hipLaunchKernelGGL(k_light_grid, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
     hipLaunchKernelGGL(k_light_grid_cdf, dim3((n_vox + 63) / 64), dim3(64), 0, st, sc, data, n_vox);
     return PT_LAUNCH_CHECK();

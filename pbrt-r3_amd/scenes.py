@@ -233,6 +233,7 @@ class SceneBuilder:
         self.spheres = []
         self.textures = []
         self.images = []            # (pt_image, texel buffer)
+        self.infinite_lights = []   # capi.pt_infinite_light, in directive order
         self.instances = []
         self.objects = {}           # name -> object index
         self.cur_object = 0         # 0 = world, k = inside ObjectBegin of object k - 1
@@ -534,6 +535,30 @@ class SceneBuilder:
         self.area_lights.append(al)
         self.cur_area_light = len(self.area_lights) - 1
 
+    def light_infinite(self, L=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), image=None, light_to_world=None, world_to_light=None, nsamples=1):
+        """LightSource "infinite" (lights/infinite.rs:273-293) read at this point of the scene: its place in the light list is the number of
+        lights created so far.  image: the map as read (H, W, 3), power of two, row 0 = t 0 (no y flip); negative values are clamped to 0 and
+        the map is multiplied by L * scale (make_mipmap, :44-67).  None: the 1 x 1 map of L * scale.  Returns the light's index."""
+        ls = np.array([f32(l) * f32(s) for l, s in zip(L, scale)], np.float32)
+        base = ls.reshape(1, 1, 3) if image is None else (np.maximum(np.asarray(image, np.float32), f32(0.0)) * ls).astype(np.float32)
+        il = capi.pt_infinite_light()
+        m = np.eye(4) if light_to_world is None else np.asarray(light_to_world, np.float64).reshape(4, 4)
+        minv = np.linalg.inv(m) if world_to_light is None else np.asarray(world_to_light, np.float64).reshape(4, 4)
+        il.light_to_world[:] = [float(v) for v in m.astype(np.float32).reshape(-1)]
+        il.world_to_light[:] = [float(v) for v in minv.astype(np.float32).reshape(-1)]
+        il.image = self.image_pyramid(base)
+        il.n_samples = int(nsamples)
+        n = 0
+        for tm in self.tri_mesh:
+            for mid in np.asarray(tm).reshape(-1):
+                mm = self.meshes[int(mid)]
+                n += 1 if (mm.area_light >= 0 and mm.object == 0) else 0
+        n += sum(1 for sp in self.spheres if sp.area_light >= 0 and sp.object == 0)
+        n += len(self.infinite_lights)
+        il.light_index = n
+        self.infinite_lights.append(il)
+        return n
+
     def no_area_light(self):
         self.cur_area_light = -1
 
@@ -697,6 +722,7 @@ class SceneBuilder:
             sph = (capi.pt_sphere * len(self.spheres))(*self.spheres)
             sd.buffers["spheres"] = sph
             d.n_spheres, d.spheres = len(self.spheres), sph
+        sd.infinite_lights = list(self.infinite_lights)
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
         d.camera_to_world[:] = [float(v) for v in self.camera_to_world]
         d.fov = self.fov
@@ -767,8 +793,10 @@ def cornell_box(res=512, spp=64, max_depth=5, light_strategy="spatial", sampler=
     return b.build()
 
 
-def rt1m(n_triangles=1000000, res=1024, spp=256, max_depth=8, s=0.005, seed_sequence=1, sampler="sobol", materials="matte", light="quad", instances=0):
-    """BASELINE config 2 ("RT1M"): 12-triangle enclosure + light, the rest random matte triangles.
+def rt1m(n_triangles=1000000, res=1024, spp=256, max_depth=8, s=0.005, seed_sequence=1, sampler="sobol", materials="matte", light="quad", instances=0,
+         finish=None):
+    """BASELINE config 2 ("RT1M"): 12-triangle enclosure + light, the rest random matte triangles.  finish(builder), if given, runs
+    just before the scene is built.
 
     Filler triangle k draws, in order, cx cy cz then v0x..v2z as lerp(uniform_float(), lo, hi)
     from PCG32 RNG::new_sequence(1) (src/core/rng.rs:21-33, :59-66)."""
@@ -850,6 +878,8 @@ def rt1m(n_triangles=1000000, res=1024, spp=256, max_depth=8, s=0.005, seed_sequ
         b.shape_sphere(radius=0.1, object_to_world=t[0], world_to_object=t[1])
     else:
         _quad(b, (0.25, 0.999, -0.25), (0.25, 0.999, 0.25), (-0.25, 0.999, 0.25), (-0.25, 0.999, -0.25))  # faces -y
+    if finish is not None:          # callers add to the scene last (tools/env_light_bench.py: an environment)
+        finish(b)
     return b.build()
 
 
