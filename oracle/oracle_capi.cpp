@@ -32,15 +32,50 @@ extern "C" {
 
 const char* orc_header(void) { return "oracle: CPU restatement of pbrt-r3 (test infrastructure, not the product)"; }
 
-int orc_scene_create(const pt_scene_desc* d, const char* data_dir, orc_scene** out) {
+// n infinite lights (pt_scene_set_infinite_lights' layout) with the scene; orc_scene_create is the call with none
+int orc_scene_create_env(const pt_scene_desc* d, const char* data_dir, uint32_t n, const pt_infinite_light* lights, orc_scene** out) {
     orc_scene* s = new orc_scene;
-    if (!s->sc.build(*d, data_dir, &s->err)) {
+    if (!s->sc.build(*d, data_dir, &s->err, n, lights)) {
         std::fprintf(stderr, "orc_scene_create: %s\n", s->err.c_str());
         delete s;
         return 1;
     }
     s->ld.init(&s->sc);
     *out = s;
+    return 0;
+}
+int orc_scene_create(const pt_scene_desc* d, const char* data_dir, orc_scene** out) { return orc_scene_create_env(d, data_dir, 0, nullptr, out); }
+
+// The light hooks, argument for argument pt_light_sample_li / pt_light_pdf_li / pt_light_le.  sample_li: any light of the list, reference
+// points without error or normal; li, wi, pdf zero where it returns None.  pdf_li and le: infinite lights only (return 1 otherwise).
+int orc_light_sample_li(const orc_scene* s, uint32_t light, uint32_t n, const float* ref_p, const float* u, float* li_out, float* wi_out, float* pdf_out) {
+    if (light >= s->sc.lights.size()) return 1;
+    const AreaLight& l = s->sc.lights[light];
+    for (uint32_t i = 0; i < n; i++) {
+        RGB li; V3 wi(0.0f, 0.0f, 0.0f), lp, lperr, ln; Float pdf = 0.0f;
+        if (!light_sample_li(s->sc, l, V3(ref_p[3 * i], ref_p[3 * i + 1], ref_p[3 * i + 2]), V3(0.0f, 0.0f, 0.0f), V3(0.0f, 0.0f, 0.0f),
+                             V2(u[2 * i], u[2 * i + 1]), &li, &wi, &pdf, &lp, &lperr, &ln)) {
+            li = RGB(); wi = V3(0.0f, 0.0f, 0.0f); pdf = 0.0f;
+        }
+        li_out[3 * i] = li.c[0]; li_out[3 * i + 1] = li.c[1]; li_out[3 * i + 2] = li.c[2];
+        wi_out[3 * i] = wi.x; wi_out[3 * i + 1] = wi.y; wi_out[3 * i + 2] = wi.z;
+        pdf_out[i] = pdf;
+    }
+    return 0;
+}
+int orc_light_pdf_li(const orc_scene* s, uint32_t light, uint32_t n, const float* wi, float* pdf_out) {
+    if (light >= s->sc.lights.size() || s->sc.lights[light].env < 0) return 1;
+    const EnvLight& e = s->sc.envs[s->sc.lights[light].env];
+    for (uint32_t i = 0; i < n; i++) pdf_out[i] = e.pdf_li(V3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]));
+    return 0;
+}
+int orc_light_le(const orc_scene* s, uint32_t light, uint32_t n, const float* d, float* rgb_out) {
+    if (light >= s->sc.lights.size() || s->sc.lights[light].env < 0) return 1;
+    const EnvLight& e = s->sc.envs[s->sc.lights[light].env];
+    for (uint32_t i = 0; i < n; i++) {
+        RGB c = e.le(V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
+        rgb_out[3 * i] = c.c[0]; rgb_out[3 * i + 1] = c.c[1]; rgb_out[3 * i + 2] = c.c[2];
+    }
     return 0;
 }
 void orc_scene_destroy(orc_scene* s) { delete s; }

@@ -4,7 +4,7 @@
 //   follows src/cameras/perspective.rs, src/core/camera/projective.rs,
 //           src/core/interaction/{surface_interaction,interaction}.rs,
 //           src/materials/{matte,plastic,mirror,glass,metal,uber,substrate}.rs, src/core/reflection/bsdf.rs,
-//           src/lights/diffuse.rs, src/core/light/visibility_tester.rs,
+//           src/lights/{diffuse,infinite}.rs, src/core/sampling/distribution.rs, src/core/light/visibility_tester.rs,
 //           src/core/lightdistrib/{spatial,power,uniform,create_light_sample_distribution}.rs,
 //           src/core/integrator/{sample_lights,sampler}.rs, src/integrators/path.rs,
 //           src/core/film/{film,film_tile}.rs
@@ -118,6 +118,106 @@ struct AreaLight {          // lights/diffuse.rs:5-11
     bool two_sided;
     Float area;
     uint32_t n_samples = 1;     // "nsamples" (diffuse.rs:177-189): Light::get_sample_count
+    int32_t env = -1;           // >= 0: this entry of the light list is the InfiniteAreaLight Scene::envs[env], the fields above unused
+};
+
+// Distribution2D (core/sampling/distribution.rs:109-145)
+struct Distribution2D {
+    std::vector<Distribution1D> conditional_v;
+    Distribution1D marginal;
+    void init(const std::vector<Float>& data, size_t nu, size_t nv) {
+        conditional_v.clear();
+        std::vector<Float> marginal_func;
+        for (size_t v = 0; v < nv; v++) {
+            conditional_v.emplace_back(std::vector<Float>(data.begin() + v * nu, data.begin() + (v + 1) * nu));
+            marginal_func.push_back(conditional_v.back().func_int);
+        }
+        marginal = Distribution1D(marginal_func);
+    }
+    V2 sample_continuous(V2 u, Float* pdf) const {            // :133-137
+        Float pdf0, pdf1;
+        size_t v;
+        Float d1 = marginal.sample_continuous(u.y, &pdf1, &v);
+        Float d0 = conditional_v[v].sample_continuous(u.x, &pdf0, nullptr);
+        *pdf = pdf0 * pdf1;
+        return V2(d0, d1);
+    }
+    static size_t cell(Float x, size_t n) {                    // `(x * count as Float) as usize` saturates (NaN -> 0), then the clamp
+        Float f = x * (Float)n;
+        size_t i = !(f > 0.0f) ? 0 : (f >= 18446744073709551616.0f ? SIZE_MAX : (size_t)f);
+        return i > n - 1 ? n - 1 : i;
+    }
+    Float pdf(V2 p) const {                                    // :138-144
+        size_t iu = cell(p.x, conditional_v[0].func.size()), iv = cell(p.y, marginal.func.size());
+        return conditional_v[iv].func[iu] / marginal.func_int;
+    }
+};
+
+// spherical_theta / spherical_phi (core/geometry/misc.rs:96-104): libm acosf / atan2f
+inline Float spherical_theta(V3 v) { return std::acos(clampf(v.z, -1.0f, 1.0f)); }
+inline Float spherical_phi(V3 v) { Float p = std::atan2(v.y, v.x); return p < 0.0f ? p + 2.0f * kPi : p; }
+
+// InfiniteAreaLight (lights/infinite.rs).  The map is the pyramid of pt_scene_desc.images[image] (make_mipmap, :44-67: the front end
+// clamps and scales the texels), wrapped s repeat, t clamp (create_spectrum_mipmap, core/texture/mipmap.rs:1013-1025).
+struct EnvLight {
+    Mat4 light_to_world, world_to_light;
+    MipImage lmap;
+    Distribution2D distribution;
+    Float radius = kInfinity;       // get_bound() before preprocess (:36-43)
+    uint32_t n_samples = 1;
+    // make_distribution (:69-91): a (2w) x (2h) table of lookup(st, 0.5 / min(2w, 2h)).y() * sin(pi v'); maps that are not 2:1 land on a
+    // level above 0 of the pyramid
+    void make_distribution() {
+        size_t width = (size_t)lmap.w[0] * 2, height = (size_t)lmap.h[0] * 2;
+        std::vector<Float> img(width * height, 0.0f);
+        Float fwidth = 0.5f / (Float)std::min(width, height);
+        for (size_t v = 0; v < height; v++) {
+            Float vp = ((Float)v + 0.5f) / (Float)height;
+            Float sin_theta = std::sin(kPi * vp);
+            for (size_t u = 0; u < width; u++) {
+                Float up = ((Float)u + 0.5f) / (Float)width;
+                Float y = lmap.lookup(V2(up, vp), fwidth).y();
+                y = fmax_(y, 0.0f);                                  // quirk Q27
+                img[v * width + u] = y * sin_theta;
+            }
+        }
+        distribution.init(img, width, height);
+    }
+    // preprocess (:95-99): Bounds3::bounding_sphere of the world bound (bounds3.rs:173-177), quirk Q28
+    void preprocess(const Bounds3& wb) { radius = length(wb.max - wb.min) * 0.5f; }
+    // power (:101-109)
+    RGB power() const { return lmap.lookup(V2(0.5f, 0.5f), 0.5f) * (kPi * radius * radius); }
+    // le (:111-122): the only one of the three that normalises the direction
+    RGB le(V3 d) const {
+        V3 w = normalize(world_to_light.transform_vector(d));
+        return lmap.lookup(V2(spherical_phi(w) * kInv2Pi, spherical_theta(w) * kInvPi), 0.0f);
+    }
+    // sample_li (:124-159): false where it returns None; pdf 0 at the poles (quirk Q29).  The visibility target p + wi * 2r is an interaction
+    // without error or normal.
+    bool sample_li(V3 ref_p, V2 u, RGB* li, V3* wi, Float* pdf, V3* lp, V3* lperr, V3* ln) const {
+        Float map_pdf;
+        V2 uv = distribution.sample_continuous(u, &map_pdf);
+        if (map_pdf <= 0.0f) return false;
+        Float theta = uv.y * kPi, phi = uv.x * 2.0f * kPi;
+        Float cos_theta = std::cos(theta), sin_theta = std::sin(theta);
+        sin_theta = clampf(sin_theta, 0.0f, 1.0f);
+        Float cos_phi = std::cos(phi), sin_phi = std::sin(phi);
+        *wi = light_to_world.transform_vector(V3(sin_theta * cos_phi, sin_theta * sin_phi, cos_theta));
+        *pdf = sin_theta == 0.0f ? 0.0f : map_pdf / (2.0f * kPi * kPi * sin_theta);
+        *lp = ref_p + *wi * (2.0f * radius);
+        *lperr = V3(0.0f, 0.0f, 0.0f);
+        *ln = V3(0.0f, 0.0f, 0.0f);
+        *li = lmap.lookup(uv, 0.0f);
+        return true;
+    }
+    // pdf_li (:161-180)
+    Float pdf_li(V3 w) const {
+        V3 wi = world_to_light.transform_vector(w);
+        Float theta = spherical_theta(wi), phi = spherical_phi(wi);
+        Float sin_theta = clampf(std::sin(theta), 0.0f, 1.0f);
+        if (sin_theta == 0.0f) return 0.0f;
+        return distribution.pdf(V2(phi * kInv2Pi, theta * kInvPi)) / (2.0f * kPi * kPi * sin_theta);
+    }
 };
 
 struct Scene {
@@ -134,6 +234,7 @@ struct Scene {
         return (ref & PRIM_SPHERE) ? sphere_material[ref & ~PRIM_SPHERE] : mesh_material[geom.tri_mesh[ref]];
     }
     std::vector<AreaLight> lights;
+    std::vector<EnvLight> envs;         // the infinite lights in light-list order (Scene::infinite_lights, scene.rs:24-25)
     Bounds3 world_bound;
 
     // camera
@@ -162,7 +263,14 @@ struct Scene {
     }
     Float rr_threshold = 1.0f;
 
-    bool build(const pt_scene_desc& d, const std::string& data_dir, std::string* err);
+    bool build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env = 0, const pt_infinite_light* env = nullptr);
+    // what every infinite light returns for a ray that leaves the scene, summed in list order (path.rs:86-98, directlighting.rs:117-129,
+    // whitted.rs:96-105; an area light's le is zero)
+    RGB env_le_all(V3 d) const {
+        RGB r;
+        for (const EnvLight& e : envs) r += e.le(d);
+        return r;
+    }
 };
 
 // DiffuseAreaLight::l (diffuse.rs:155-163)
@@ -171,6 +279,7 @@ inline RGB light_L(const AreaLight& l, V3 n, V3 w) { return (l.two_sided || dot(
 // DiffuseAreaLight::sample_li (diffuse.rs:70-87).  Outputs wi, pdf, the sampled
 // point (p, p_error, n) for the visibility tester.
 inline bool light_sample_li(const Scene& sc, const AreaLight& l, V3 ref_p, V3 ref_p_error, V3 ref_n, V2 u, RGB* li, V3* wi, Float* pdf, V3* lp, V3* lperr, V3* ln) {
+    if (l.env >= 0) return sc.envs[l.env].sample_li(ref_p, u, li, wi, pdf, lp, lperr, ln);
     if (l.shape & PRIM_SPHERE) {
         if (!sc.geom.spheres[l.shape & ~PRIM_SPHERE].sample_from(ref_p, ref_p_error, ref_n, u, lp, ln, lperr, pdf)) return false;
     } else {
@@ -201,6 +310,7 @@ struct LightDistribution {
         } else if (strategy == PT_LIGHTS_POWER) {   // power.rs:9-17, diffuse.rs:65-68
             std::vector<Float> pw;
             for (const AreaLight& l : s->lights) {
+                if (l.env >= 0) { pw.push_back(s->envs[l.env].power().y()); continue; }
                 Float n = l.two_sided ? 2.0f : 1.0f;
                 RGB p = l.lemit * (n * l.area * kPi);
                 pw.push_back(p.y());
@@ -566,7 +676,8 @@ inline RGB estimate_direct(const Scene& sc, const SurfHit& it, const BSDF& bsdf,
             Float weight = 1.0f;
             bool skip = false;
             if (!sampled_specular) {
-                Float lpdf = (light.shape & PRIM_SPHERE) ? sc.geom.spheres[light.shape & ~PRIM_SPHERE].pdf_from(it.p, it.p_error, it.n, wi)
+                Float lpdf = light.env >= 0 ? sc.envs[light.env].pdf_li(wi)
+                           : (light.shape & PRIM_SPHERE) ? sc.geom.spheres[light.shape & ~PRIM_SPHERE].pdf_from(it.p, it.p_error, it.n, wi)
                                                          : TriRef(&sc.geom, light.shape).pdf_from(it.p, it.p_error, it.n, wi);   // pdf_li, diffuse.rs:89-94
                 if (lpdf == 0.0f) skip = true;     // `return ld`
                 else weight = power_heuristic(1, scattering_pdf, 1, lpdf);
@@ -581,7 +692,9 @@ inline RGB estimate_direct(const Scene& sc, const SurfHit& it, const BSDF& bsdf,
                 RGB li;
                 if (found) {
                     if (sc.prim_light[lh.prim] == (int32_t)light_num) li = surf_le(sc, lh, -wi);
-                }   // else light.le(ray): zero for area lights (light.rs:33-35)
+                } else if (light.env >= 0) {
+                    li = sc.envs[light.env].le(wi);        // light.le(ray): zero for area lights (light.rs:33-35)
+                }
                 if (!li.is_black()) ld += f * li * (weight / scattering_pdf);
             }
         }
@@ -617,6 +730,7 @@ inline RGB path_li(const Scene& sc, LightDistribution& ldist, Ray ray, SobolSamp
         rc.nodes += st.nodes; rc.tris += st.tris;
         if (bounces == 0 || specular_bounce) {
             if (found) l += beta * surf_le(sc, isect, -ray.d);
+            else for (const EnvLight& e : sc.envs) l += beta * e.le(ray.d);
         }
         if (!found || bounces >= sc.max_depth) break;
         BSDF bsdf;
@@ -696,7 +810,7 @@ inline RGB rec_li(const Scene& sc, Ray ray, RayDiff rd, SobolSampler& sampler, R
     QBVH::Stats st;
     bool found = sc.bvh.intersect(ray, &isect, &st);
     rc.nodes += st.nodes; rc.tris += st.tris;
-    if (!found) return RGB();                       // sum of light.le(ray): zero for area lights (light.rs:33-35)
+    if (!found) return sc.env_le_all(ray.d);        // sum of light.le(ray): zero for area lights (light.rs:33-35)
     const V3 n_before = isect.sh_n;                 // whitted.rs:52: the shading normal before compute_scattering_functions (bump mapping)
     const V3 wo = isect.wo;
     const TexHit th = compute_differentials(isect, rd);      // what compute_scattering_functions leaves in isect.dpdx / dudx .. (surface_interaction.rs:284-295)
@@ -1010,7 +1124,7 @@ inline void render(const Scene& sc, LightDistribution& ldist, const pt_tile* til
 }
 
 // ---- scene assembly from the flattened description
-inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, std::string* err) {
+inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env, const pt_infinite_light* env) {
     if (!sobol.load(data_dir + "/sobol_tables.bin")) { *err = "cannot load sobol_tables.bin from " + data_dir; return false; }
     geom.P.resize(d.n_vertices);
     for (uint32_t i = 0; i < d.n_vertices; i++) geom.P[i] = V3(d.P[3 * i], d.P[3 * i + 1], d.P[3 * i + 2]);
@@ -1118,6 +1232,45 @@ inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, st
         return false;
     }
     world_bound = bvh.bounds;
+    // LightSource "infinite": the directive appends the light to the list when it is read, area lights are appended as their shapes are
+    // created (scene_context.rs:1178-1188, :1300-1316), so light_index is the light's place in the merged list; an index past the area
+    // lights appends it.  Every light is preprocessed with the scene's world bound (scene.rs:21-37).
+    if (n_env) {
+        std::vector<uint32_t> order(n_env);
+        for (uint32_t k = 0; k < n_env; k++) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return env[a].light_index < env[b].light_index; });
+        for (uint32_t k : order) {
+            const pt_infinite_light& il = env[k];
+            if (il.image < 0 || (uint32_t)il.image >= d.n_images || d.images[il.image].channels != 3) { if (err) *err = "infinite light image index out of range"; return false; }
+            EnvLight e;
+            std::memcpy(e.light_to_world.m, il.light_to_world, 64);
+            std::memcpy(e.world_to_light.m, il.world_to_light, 64);
+            e.lmap.init(d.images[il.image]);
+            e.lmap.swrap = PT_WRAP_REPEAT;
+            e.lmap.twrap = PT_WRAP_CLAMP;
+            e.n_samples = (uint32_t)std::min(4096, std::max(1, il.n_samples));
+            e.make_distribution();
+            e.preprocess(world_bound);
+            envs.push_back(std::move(e));
+        }
+        std::vector<AreaLight> area;
+        area.swap(lights);
+        std::vector<int32_t> area_to_list(area.size());
+        size_t ai = 0, ei = 0;
+        while (ai < area.size() || ei < order.size()) {
+            if (ei < order.size() && (ai == area.size() || env[order[ei]].light_index <= lights.size())) {
+                AreaLight l = AreaLight();
+                l.shape = 0; l.two_sided = false; l.area = 0.0f;
+                l.n_samples = envs[ei].n_samples;
+                l.env = (int32_t)ei++;
+                lights.push_back(l);
+            } else {
+                area_to_list[ai] = (int32_t)lights.size();
+                lights.push_back(area[ai++]);
+            }
+        }
+        for (int32_t& pl : prim_light) if (pl >= 0) pl = area_to_list[pl];
+    }
     // film (film.rs:62-100, :166-179)
     xres = d.xres; yres = d.yres;
     crop[0] = std::max(0, (int32_t)std::floor((Float)xres * d.crop_window[0]));

@@ -2909,9 +2909,11 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             }
             if constexpr (ENV && PART != 1) {         // a ray that left the scene: every infinite light's Le (path.rs:86-98)
                 if (rec < 0 && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
-                    const V3 add = beta * env_le_all(sc, rd);
                     float4 L = P.L[p];
-                    L.x += add.x; L.y += add.y; L.z += add.z;
+                    for (uint32_t k = 0; k < sc.n_envs; k++) {      // `l += beta * light.le(ray)` light by light, not beta times their sum
+                        const V3 add = beta * env_le(sc, scene_envs(sc)[k], rd);
+                        L.x += add.x; L.y += add.y; L.z += add.z;
+                    }
                     P.L[p] = L;
                 }
             }

@@ -25,11 +25,14 @@ def uv_sphere(center, radius, nt=8, nphi=12):
     return np.array(P, np.float32), np.array(N, np.float32), np.array(UV, np.float32), idx
 
 
-def room(b, size=2.0, light_L=(10, 9, 8), two_sided_light=False):
+def room(b, size=2.0, light_L=(10, 9, 8), two_sided_light=False, open_top=False):
+    """Floor, ceiling, back and side walls, open towards the camera; open_top leaves the ceiling out (an environment then lights the room
+    from above too)."""
     s = size
     b.material_matte((0.7, 0.7, 0.7))
     scenes._quad(b, (s, -s, -s), (-s, -s, -s), (-s, -s, s), (s, -s, s))
-    scenes._quad(b, (s, s, -s), (s, s, s), (-s, s, s), (-s, s, -s))
+    if not open_top:
+        scenes._quad(b, (s, s, -s), (s, s, s), (-s, s, s), (-s, s, -s))
     scenes._quad(b, (s, -s, s), (-s, -s, s), (-s, s, s), (s, s, s))
     b.material_matte((0.2, 0.6, 0.3))
     scenes._quad(b, (-s, -s, s), (-s, -s, -s), (-s, s, -s), (-s, s, s))
@@ -648,3 +651,128 @@ def scene_instance_swarm(split="sah", maxnodeprims=4, n_inst=36, res=48, spp=8, 
             q = rng.uniform(-1.0, 1.0, 3).astype(np.float32)
             b.shape_trianglemesh([tuple(q), tuple(q + np.float32([0.3, 0.0, 0.05])), tuple(q + np.float32([0.0, 0.3, 0.1]))], [0, 1, 2])
     return b.build()
+
+
+# ---- LightSource "infinite" scenes (lights/infinite.rs) for the device-against-oracle parity tests and the env golden fixture
+ENV_MAPS = ("constant", "image", "wide", "tall", "row", "column", "holes")
+
+
+def env_map_image(kind, seed=5):
+    """The environment maps of the parity matrix: None (constant), 2:1, 8:1 (make_distribution's lookup lands on level 1), 1:4, 1 x N,
+    N x 1, and a 2:1 map with all-black rows and columns (zero-probability cells of the Distribution2D, pdf_li 0 there)."""
+    if kind == "constant":
+        return None
+    if kind == "holes":
+        img = 0.2 + test_image(32, 16, 3, seed=seed)
+        img[:, 4:9] = 0.0
+        img[6:9] = 0.0
+        img[0] = 0.0
+        return img
+    w, h = {"image": (32, 16), "wide": (64, 8), "tall": (8, 32), "row": (16, 1), "column": (1, 16)}[kind]
+    return 0.2 + test_image(w, h, 3, seed=seed)
+
+
+def env_transform(kind):
+    """light_to_world of the map: identity, rotated, mirrored (swaps handedness), non-uniformly scaled (sample_li and pdf_li do not
+    normalise their directions, le does)."""
+    T = scenes
+    rot = T.transform_mul(T.transform_rotate_x(-70.0), T.transform_mul(T.transform_rotate_x(20.0), T.transform_scale(1.0, 1.0, 1.0)))
+    if kind == "identity":
+        return None
+    if kind == "rotated":
+        return rot
+    if kind == "mirrored":
+        return T.transform_mul(T.transform_scale(-1.0, 1.0, 1.0), rot)
+    return T.transform_mul(T.transform_scale(2.0, 0.5, 1.25), rot)
+
+
+def scene_env(integrator="path", strategy="spatial", materials=("matte",), env_map="image", transform="identity", order="after", n_env=1,
+              sampler="sobol", nsamples=1, far=False, area_light=True, res=24, spp=8, depth=4, L=(1.0, 0.9, 0.8)):
+    """A floor with objects of the given materials under an environment.  order: the environment read "before" or "after" the area lights;
+    n_env = 2 adds a second (constant) environment at the other end of the list.  far: an instance and a sphere far from the origin set the
+    world bound (the radius r of the shadow target p + wi * 2r).  integrator "directlighting" takes strategy "all" / "one"."""
+    T = scenes
+    b = scenes.SceneBuilder()
+    b.look_at((0.0, -4.0, 1.6), (0.0, 0.0, 0.4), (0.0, 0.0, 1.0))
+    b.camera_perspective(fov=62.0)
+    b.film(xresolution=res, yresolution=res)
+    b.pixel_filter_box()
+    b.sampler_sobol(spp) if sampler == "sobol" else b.sampler_halton(spp)
+    if integrator == "path":
+        b.integrator_path(maxdepth=depth, lightsamplestrategy=strategy)
+    elif integrator == "directlighting":
+        b.integrator_directlighting(maxdepth=depth, strategy=strategy)
+    else:
+        b.integrator_whitted(maxdepth=depth)
+    img = env_map_image(env_map)
+    l2w = env_transform(transform)
+
+    def env(second=False):
+        if second:
+            b.light_infinite(L=(0.3, 0.35, 0.5), nsamples=2)
+        else:
+            b.light_infinite(L=L, image=img, light_to_world=None if l2w is None else l2w[0].reshape(4, 4),
+                             world_to_light=None if l2w is None else l2w[1].reshape(4, 4), nsamples=nsamples)
+    if order == "before":
+        env()
+        if n_env == 2:
+            env(second=True)
+    if area_light:
+        b.area_light_source_diffuse(L=(4.0, 3.5, 3.0), nsamples=2)
+        b.shape_trianglemesh([(-0.4, -0.3, 2.2), (0.4, -0.3, 2.2), (0.4, 0.5, 2.2), (-0.4, 0.5, 2.2)], [0, 2, 1, 0, 3, 2])
+        b.no_area_light()
+    if order == "after" and n_env == 2:
+        env(second=True)
+    b.material_matte((0.6, 0.55, 0.5))
+    b.shape_trianglemesh([(-3, -3, 0), (3, -3, 0), (3, 3, 0), (-3, 3, 0)], [0, 1, 2, 0, 2, 3])
+    xs = np.linspace(-1.3, 1.3, max(1, len(materials))) if len(materials) > 1 else [0.0]
+    for k, (m, x) in enumerate(zip(materials, xs)):
+        x = float(x)
+        if m == "matte":
+            b.material_matte((0.7, 0.4, 0.3))
+        elif m == "plastic":
+            b.material_plastic(Kd=(0.3, 0.4, 0.5), Ks=(0.4, 0.4, 0.4), roughness=0.15)
+        elif m == "mirror":
+            b.material_mirror(Kr=(0.9, 0.9, 0.85))
+        elif m == "glass":
+            b.material_glass(Kr=(1.0, 1.0, 1.0), Kt=(1.0, 1.0, 1.0), eta=1.5)
+        elif m == "metal":
+            b.material_metal(eta=(0.2, 0.92, 1.1), k=(3.9, 2.45, 2.14), roughness=0.05)
+        elif m == "textured":
+            b.material_matte(Kd=b.texture_checkerboard(tex1=(0.8, 0.2, 0.2), tex2=(0.2, 0.8, 0.2), uscale=4, vscale=4))
+        if m in ("glass", "sphere"):
+            if m == "sphere":
+                b.material_matte((0.7, 0.7, 0.7))
+            t = T.transform_translate(x, 0.0, 0.45)
+            b.shape_sphere(radius=0.42, object_to_world=t[0], world_to_object=t[1])
+        elif m == "instanced":
+            b.object_begin("env_q%d" % k)
+            b.material_plastic(Kd=(0.5, 0.7, 0.3), Ks=(0.2, 0.2, 0.2), roughness=0.3)
+            b.shape_trianglemesh([(-0.25, 0, 0), (0.25, 0, 0), (0.25, 0, 0.5), (-0.25, 0, 0.5)], [0, 1, 2, 0, 2, 3])
+            b.object_end()
+            for j in range(3):
+                b.object_instance("env_q%d" % k, T.transform_mul(T.transform_translate(x + 0.3 * (j - 1), 0.25 * j, 0.05),
+                                                                  T.transform_rotate_x(15.0 * j)))
+        else:           # a quad tilted towards the camera: mirror and metal show the sky and the floor in it
+            b.shape_trianglemesh([(x - 0.4, 0.2, 0.0), (x + 0.4, 0.2, 0.0), (x + 0.4, 0.6, 0.9), (x - 0.4, 0.6, 0.9)], [0, 1, 2, 0, 2, 3])
+    if far:
+        b.object_begin("env_far")
+        b.material_matte((0.5, 0.5, 0.5))
+        b.shape_trianglemesh([(0, 0, 0), (1, 0, 0), (0, 1, 0)], [0, 1, 2])
+        b.object_end()
+        b.object_instance("env_far", T.transform_translate(60.0, 90.0, 25.0))
+        t = T.transform_translate(-40.0, 120.0, -8.0)
+        b.material_matte((0.4, 0.4, 0.6))
+        b.shape_sphere(radius=2.0, object_to_world=t[0], world_to_object=t[1])
+    if order == "after":
+        env()
+    elif order == "middle" and n_env == 1:
+        env()
+    return b.build()
+
+
+def scene_env_golden():
+    """The environment-lit fixture (tools/make_golden.py): an image-mapped sky under a rotation, a mirror and a glass sphere next to a
+    plastic quad, directlighting "all" with samples 3, Halton."""
+    return scene_env("directlighting", "all", ("mirror", "glass", "plastic"), env_map="image", transform="rotated", order="before",
+                     sampler="halton", nsamples=3, res=32, spp=4, depth=4)

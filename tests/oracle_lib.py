@@ -29,6 +29,10 @@ class Oracle:
         self.lib = lib
         vp, u32 = C.c_void_p, C.c_uint32
         lib.orc_scene_create.argtypes = [C.POINTER(capi.pt_scene_desc), C.c_char_p, C.POINTER(vp)]
+        lib.orc_scene_create_env.argtypes = [C.POINTER(capi.pt_scene_desc), C.c_char_p, u32, C.POINTER(capi.pt_infinite_light), C.POINTER(vp)]
+        lib.orc_light_sample_li.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+        lib.orc_light_pdf_li.argtypes = [vp, u32, u32, vp, vp]
+        lib.orc_light_le.argtypes = [vp, u32, u32, vp, vp]
         lib.orc_scene_destroy.argtypes = [vp]
         lib.orc_scene_destroy.restype = None
         lib.orc_scene_info.argtypes = [vp, C.POINTER(capi.pt_scene_info)]
@@ -104,7 +108,9 @@ class OracleScene:
     def __init__(self, orc, sd):
         self.orc, self.lib, self.sd = orc, orc.lib, sd
         self.h = C.c_void_p()
-        rc = self.lib.orc_scene_create(C.byref(sd.desc), DATA_DIR.encode(), C.byref(self.h))
+        inf = list(getattr(sd, "infinite_lights", None) or [])        # LightSource "infinite": rendered by the oracle too, never dropped
+        arr = (capi.pt_infinite_light * max(1, len(inf)))(*inf)
+        rc = self.lib.orc_scene_create_env(C.byref(sd.desc), DATA_DIR.encode(), len(inf), arr, C.byref(self.h))
         assert rc == 0, "orc_scene_create failed"
         self.info = capi.pt_scene_info()
         self.lib.orc_scene_info(self.h, C.byref(self.info))
@@ -201,6 +207,30 @@ class OracleScene:
         f = np.empty((n, 3), np.float32); wi = np.empty((n, 3), np.float32); pdf = np.empty(n, np.float32); t = np.empty(n, np.uint32)
         self.lib.orc_bsdf_sample(self.h, C.c_uint32(material), C.c_uint32(n), _p(wo), _p(u), C.c_uint32(flags), _p(f), _p(wi), _p(pdf), _p(t))
         return f, wi, pdf, t
+
+    def light_sample_li(self, light, ref_p, u):
+        """Light::sample_li of light `light` (index into the light list): (Li, wi, pdf), pdf 0 where it returns None; as Context.light_sample_li."""
+        ref_p = np.ascontiguousarray(ref_p, np.float32).reshape(-1, 3); u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = len(u)
+        if len(ref_p) == 1 and n > 1:
+            ref_p = np.ascontiguousarray(np.repeat(ref_p, n, axis=0))
+        li = np.empty((n, 3), np.float32); wi = np.empty((n, 3), np.float32); pdf = np.empty(n, np.float32)
+        assert self.lib.orc_light_sample_li(self.h, light, n, _p(ref_p), _p(u), _p(li), _p(wi), _p(pdf)) == 0, "not a light"
+        return li, wi, pdf
+
+    def light_pdf_li(self, light, wi):
+        """InfiniteAreaLight::pdf_li for world directions wi."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        pdf = np.empty(len(wi), np.float32)
+        assert self.lib.orc_light_pdf_li(self.h, light, len(wi), _p(wi), _p(pdf)) == 0, "not an infinite light"
+        return pdf
+
+    def light_le(self, light, d):
+        """InfiniteAreaLight::le for world ray directions d: RGB."""
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        out = np.empty((len(d), 3), np.float32)
+        assert self.lib.orc_light_le(self.h, light, len(d), _p(d), _p(out)) == 0, "not an infinite light"
+        return out
 
     def light_distribution(self, p):
         n = self.info.n_lights

@@ -12,14 +12,21 @@ def _digest(sd):
              np.ctypeslib.as_array(d.indices, shape=(3 * d.n_triangles,)).tobytes() if d.n_triangles else b"",
              bytes([d.integrator & 255, d.sampler & 255, d.split_method & 255, d.max_node_prims & 255]),
              np.int64([d.n_spheres, d.n_instances, d.n_materials, d.n_textures, d.spp, d.max_depth]).tobytes()]
+    for il in getattr(sd, "infinite_lights", []):
+        h, w = d.images[il.image].height, d.images[il.image].width
+        parts += [bytes(il), np.ctypeslib.as_array(d.images[il.image].texels, shape=(3 * w * h,)).tobytes()]
     return b"".join(parts)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 5, 7, 970])
-def test_random_scene_is_deterministic_and_renders(oracle, seed):
-    a, exact_a = fz.random_scene(seed)
-    b, exact_b = fz.random_scene(seed)
+def test_random_scene_is_deterministic_and_renders(oracle, seed, env=False):
+    a, exact_a = fz.random_scene(seed, env)
+    b, exact_b = fz.random_scene(seed, env)
     assert exact_a == exact_b and _digest(a) == _digest(b)
+    if env:         # the environment adds its lights and leaves every other draw alone
+        plain, _ = fz.random_scene(seed)
+        assert len(a.infinite_lights) in (1, 2) and a.desc.n_images >= plain.desc.n_images
+        assert a.desc.integrator == plain.desc.integrator and a.desc.spp == plain.desc.spp and a.desc.n_spheres == plain.desc.n_spheres
     osc = oracle.scene(a)
     oracle.reference_panics()
     try:
@@ -28,6 +35,12 @@ def test_random_scene_is_deterministic_and_renders(oracle, seed):
         assert (oracle.reference_panics() & 1) == (1 if seed == 970 else 0)        # seed 970: the scene that found quirk Q24
     finally:
         osc.close()
+
+
+@pytest.mark.parametrize("seed", [0, 3, 11, 970])
+def test_random_env_scene_is_deterministic_and_renders(oracle, seed):
+    """The same seeds with one or two infinite lights drawn in (test_gpu_fuzz.random_scene(seed, env=True)), rendered by the oracle."""
+    test_random_scene_is_deterministic_and_renders(oracle, seed, env=True)
 
 
 def test_instanced_bench_scene_is_the_plain_one_copied(oracle):

@@ -163,7 +163,27 @@ def _shape(b, rng, where):
         b.reverse_orientation = False
 
 
-def random_scene(seed):
+def _env_lights(b, erng):
+    """LightSource "infinite": a constant or image map of random power-of-two size, a random rotation (sometimes mirrored or non-uniformly
+    scaled), "scale", and "samples" 1-4."""
+    img = None
+    if erng.random() < 0.6:
+        img = 0.1 + fs.test_image(int(2 ** erng.integers(0, 7)), int(2 ** erng.integers(0, 6)), 3, seed=int(erng.integers(0, 99)))
+    m = T.transform_mul(T.transform_rotate_x(float(erng.uniform(-180, 180))), T.transform_rotate_x(0.0))
+    if erng.random() < 0.3:
+        s = erng.uniform(0.5, 2.0, 3)
+        if erng.random() < 0.5:
+            s[int(erng.integers(0, 3))] *= -1.0
+        m = T.transform_mul(m, T.transform_scale(float(s[0]), float(s[1]), float(s[2])))
+    b.light_infinite(L=_rgb(erng, 0.1, 1.5), scale=tuple([float(erng.uniform(0.5, 2.0))] * 3), image=img, light_to_world=m[0].reshape(4, 4),
+                     world_to_light=m[1].reshape(4, 4), nsamples=int(erng.integers(1, 5)))
+
+
+def random_scene(seed, env=False):
+    """env: the same scene (every draw of the main generator unchanged) plus one or two infinite lights, drawn from a generator of their own,
+    before or after the area lights, and sometimes a room without its ceiling."""
+    erng = np.random.default_rng((seed, 0xE)) if env else None
+    env_where = [int(erng.integers(0, 2)) for _ in range(1 if erng.random() < 0.7 else 2)] if env else []    # 0: before the lights, 1: after
     rng = np.random.default_rng(1000 + seed)
     b = scenes.SceneBuilder()
     eye = (float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)), -6.5 + float(rng.uniform(-0.5, 0.5)))
@@ -212,7 +232,9 @@ def random_scene(seed):
             _shape(b, rng, (0.0, 0.0, 0.0))
         b.object_end()
         names.append(name)
-    fs.room(b, light_L=_rgb(rng, 3.0, 12.0), two_sided_light=bool(rng.random() < 0.3))
+    for _ in range(env_where.count(0)):
+        _env_lights(b, erng)
+    fs.room(b, light_L=_rgb(rng, 3.0, 12.0), two_sided_light=bool(rng.random() < 0.3), open_top=bool(env and erng.random() < 0.5))
     for _ in range(int(rng.integers(1, 6))):
         _material(b, rng, ao)
         _shape(b, rng, tuple(float(x) for x in rng.uniform(-1.4, 1.4, 3)))
@@ -235,6 +257,8 @@ def random_scene(seed):
             m = _xform(rng, c)
             b.shape_sphere(radius=float(rng.uniform(0.1, 0.3)), object_to_world=m[0], world_to_object=m[1])
         b.no_area_light()
+    for _ in range(env_where.count(1)):
+        _env_lights(b, erng)
     return b.build(), exact_film
 
 
@@ -271,8 +295,19 @@ def test_random_scene_pairwise_node_fetch(fuzz_ctx_far, oracle, seed):
 
 
 @pytest.mark.parametrize("seed", _seeds())
-def test_random_scene(fuzz_ctx, oracle, seed):
-    sd, exact_film = random_scene(seed)
+def test_random_env_scene(fuzz_ctx, oracle, seed):
+    """The same scenes lit by one or two environments as well (LightSource "infinite", oracle restatement in orc_render.hpp)."""
+    test_random_scene(fuzz_ctx, oracle, seed, env=True)
+
+
+@pytest.mark.parametrize("seed", _seeds()[:int(os.environ.get("FUZZ_FAR_N", "16"))])
+def test_random_env_scene_pairwise_node_fetch(fuzz_ctx_far, oracle, seed):
+    test_random_scene(fuzz_ctx_far, oracle, seed, env=True)
+
+
+@pytest.mark.parametrize("seed", _seeds())
+def test_random_scene(fuzz_ctx, oracle, seed, env=False):
+    sd, exact_film = random_scene(seed, env)
     fuzz_ctx.set_bvh_build(DEVICE if seed % 3 == 0 else (HOST if seed % 3 == 1 else AUTO))
     osc = oracle.scene(sd)
     oracle.reference_panics()          # cleared

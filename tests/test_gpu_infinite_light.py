@@ -1,6 +1,8 @@
 """LightSource "infinite" on the GPU path: the light hooks against numpy restatements of infinite.rs / distribution.rs, escaped camera rays,
 the enclosing-sphere equivalence, an image-mapped environment against a quadrature, a black environment, the routing switches and the CLI.
-The oracle cannot render infinite lights: truth comes from closed forms and from the equivalent area-light scene."""
+Truth comes from closed forms and from the equivalent area-light scene, and the environment scenes are held to the oracle's restatement
+(orc_render.hpp EnvLight) bit for bit as well; test_gpu_infinite_light_parity.py does that over a matrix of scenes, and
+test_infinite_light_oracle.py checks the restatement itself on the CPU."""
 import os
 import subprocess
 import sys
@@ -192,6 +194,10 @@ def test_escaped_camera_rays_see_le():
         le = ctx.light_le(0, d)
         got = rad.reshape(-1, 3)
         assert np.array_equal(got[miss], le[miss])
+        # and the whole tile is the oracle's, bit for bit
+        import oracle_lib
+        r = oracle_lib.load().scene(sd).radiance_samples(tuple(sb_))
+        assert np.array_equal(rad.view(np.uint32), r.view(np.uint32))
     finally:
         ctx.close()
 
@@ -255,7 +261,8 @@ def equivalence_scene(env, family, strategy, L=(1.2, 1.0, 0.8), extra_light=Fals
     ("matte", None, True, "whitted", True), ("textured", None, False, "whitted", False),
 ])
 def test_enclosing_sphere_equivalence(family, strategy, extra, integrator, env_first):
-    a, _ = render_samples(equivalence_scene(True, family, strategy, extra_light=extra, integrator=integrator, env_first=env_first))
+    sd_a = equivalence_scene(True, family, strategy, extra_light=extra, integrator=integrator, env_first=env_first)
+    a, info_a = render_samples(sd_a)
     sd_b = equivalence_scene(False, family, strategy, extra_light=extra, integrator=integrator)
     b, info_b = render_samples(sd_b)
     b_full = b
@@ -286,6 +293,10 @@ def test_enclosing_sphere_equivalence(family, strategy, extra, integrator, env_f
     r = osc.radiance_samples(tuple(info_b.sample_bounds))
     err = np.sqrt(((b_full.astype(np.float64) - r) ** 2).sum() / (r.astype(np.float64) ** 2).sum())
     assert err < 1e-4, err
+    # and so is the environment version, bit for bit
+    a_full = render_samples(sd_a)[0]
+    ra = oracle_lib.load().scene(sd_a).radiance_samples(tuple(info_a.sample_bounds))
+    assert np.array_equal(a_full.view(np.uint32), ra.view(np.uint32))
 
 
 def test_emitters_after_the_directive_keep_their_own_radiance():

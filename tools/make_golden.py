@@ -9,6 +9,7 @@ against accidental change and give the GPU tests a committed target:
   tests/golden/materials_sobol_40x40_8spp_samples.npy per-sample radiance of a 12x12 tile: metal / uber / substrate
   tests/golden/{directlighting_all_ns3,whitted_depth4,ao_16cos_cornell}_*.npz   the other integrators: film, per-sample radiance of the
                                                       middle tile, ray counters (tests/feature_scenes.py::GOLDEN_INTEGRATORS)
+  tests/golden/env_directlighting_halton_32x32_4spp.npz   the same for an environment-lit scene (feature_scenes.scene_env_golden)
 """
 import importlib, os, sys
 import numpy as np
@@ -54,4 +55,11 @@ for name, make in fs.GOLDEN_INTEGRATORS.items():
     np.savez_compressed(os.path.join(G, name + ".npz"), xyzw=xyzw_i, radiance=rad_i,
                         counters=np.array([cnt_i[k] for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices")], np.int64))
     sci.close()
+# an environment-lit scene (LightSource "infinite": image-mapped sky, mirror, glass, directlighting "all" with samples 3, Halton)
+sde = fs.scene_env_golden()
+sce = orc.scene(sde)
+xyzw_e, cnt_e, _ = sce.render(threads=1)
+np.savez_compressed(os.path.join(G, "env_directlighting_halton_32x32_4spp.npz"), xyzw=xyzw_e, radiance=sce.radiance_samples(fs.golden_tile(sce.info)),
+                    counters=np.array([cnt_e[k] for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices")], np.int64))
+sce.close()
 print("golden written:", os.listdir(G))
