@@ -184,6 +184,25 @@ typedef struct {
     uint32_t reserved;
 } pt_infinite_light;
 
+/* AlphaMaskShape (src/shapes/alphamask.rs) around every triangle of a mesh: "alpha" / "shadowalpha" of a trianglemesh or plymesh
+ * (shapes/triangle.rs:654-694).  A candidate hit is rejected when the mask evaluated at its intersection-time interaction is <= 0;
+ * the rejected hit does not shorten the ray.  Closest-hit rays test "alpha", shadow (any-hit) rays "alpha" and then "shadowalpha".
+ * Constants: <= 0 cuts the mesh out of those rays, > 0 does nothing.  The triangles stay in the accelerator (world bound) and an
+ * emitter keeps its light (area, sampling and pdf ignore the mask).  Passed with pt_scene_set_alpha_masks, not in pt_scene_desc. */
+#define PT_ALPHA_NONE     0
+#define PT_ALPHA_CONSTANT 1
+#define PT_ALPHA_TEXTURE  2
+typedef struct {
+    uint32_t mesh;              /* index into pt_scene_desc.meshes */
+    int32_t alpha_kind;         /* PT_ALPHA_*: "alpha" */
+    float alpha_value;          /* PT_ALPHA_CONSTANT: the value */
+    int32_t alpha_texture;      /* PT_ALPHA_TEXTURE: index into pt_scene_desc.textures (a float texture) */
+    int32_t shadow_kind;        /* the same for "shadowalpha" */
+    float shadow_value;
+    int32_t shadow_texture;
+    uint32_t reserved[5];
+} pt_alpha_mask;
+
 /* TriangleMesh flags (src/shapes/triangle.rs:10-22). */
 #define PT_MESH_TWO_SIDED            1u  /* "twosided" shape param, default true (triangle.rs:707) */
 #define PT_MESH_REVERSE_ORIENTATION  2u
@@ -376,6 +395,10 @@ pt_status pt_set_data_dir(pt_context* ctx, const char* dir);
  * scene with infinite lights is preceded by this call.  A scene with one runs the *_env kernels of the path, directlighting and whitted
  * integrators (escaped rays add Le, next-event estimation samples the map). */
 pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_infinite_light* lights);
+/* The alpha masks of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the infinite lights.  At most one record
+ * per mesh.  A bad mesh or texture index, or a texture that is not a float texture, fails the upload with PT_ERR_INVALID_ARGUMENT.  A
+ * scene with a mask traces every ray with k_trace_alpha (k_trace_batch_alpha for the trace hooks). */
+pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_mask* masks);
 pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* desc);
 pt_status pt_scene_info_get(const pt_context* ctx, pt_scene_info* out);
 

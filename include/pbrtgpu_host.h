@@ -57,6 +57,8 @@ pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** o
 const pt_scene_desc* pth_scene_get_desc(const pth_scene* s);
 /* The scene's LightSource "infinite" lights (for pt_scene_set_infinite_lights); *n receives their count.  Valid until pth_scene_free. */
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n);
+/* The scene's alpha-masked meshes (for pt_scene_set_alpha_masks); *n receives their count.  Valid until pth_scene_free. */
+const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
 /* Film "filename" parameter (default "pbrt.exr"). */
 const char* pth_scene_output_filename(const pth_scene* s);
 /* Command-line overrides of the reference CLI (src/bin/pbrt.rs:234-244). */

@@ -71,6 +71,14 @@ class pt_infinite_light(C.Structure):
                 ("light_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PT_ALPHA_NONE, PT_ALPHA_CONSTANT, PT_ALPHA_TEXTURE = range(3)
+
+
+class pt_alpha_mask(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("alpha_kind", C.c_int32), ("alpha_value", C.c_float), ("alpha_texture", C.c_int32),
+                ("shadow_kind", C.c_int32), ("shadow_value", C.c_float), ("shadow_texture", C.c_int32), ("reserved", C.c_uint32 * 5)]
+
+
 class pt_mesh(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("material", C.c_int32), ("area_light", C.c_int32), ("object", C.c_uint32)]
 
@@ -154,7 +162,7 @@ SYMBOLS = [
     "pt_film_device_xyzw", "pt_film_commit_xyzw", "pt_film_allreduce", "pt_film_add_xyzw", "pt_film_resolve_rgb", "pt_trace_closest", "pt_trace_any", "pt_trace_wavefront",
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
-    "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le",
+    "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le", "pt_scene_set_alpha_masks",
 ]
 
 _lib = None
@@ -219,7 +227,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights"]
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks"]
 
 
 class ParsedScene:
@@ -256,6 +264,11 @@ class ParsedScene:
         n_inf = C.c_uint32()
         arr = L.pth_scene_get_infinite_lights(self.h, C.byref(n_inf))
         self.infinite_lights = [arr[i] for i in range(n_inf.value)]       # LightSource "infinite" (copies)
+        L.pth_scene_get_alpha_masks.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.pth_scene_get_alpha_masks.restype = C.POINTER(pt_alpha_mask)
+        n_am = C.c_uint32()
+        am = L.pth_scene_get_alpha_masks(self.h, C.byref(n_am))
+        self.alpha_masks = [pt_alpha_mask.from_buffer_copy(am[i]) for i in range(n_am.value)]      # "alpha" / "shadowalpha" of the meshes (copies)
 
     @property
     def output_filename(self):
@@ -335,6 +348,9 @@ class Context:
         inf = list(getattr(scene, "infinite_lights", None) or [])
         arr = (pt_infinite_light * max(1, len(inf)))(*inf)
         self._check(self.lib.pt_scene_set_infinite_lights(self.h, C.c_uint32(len(inf)), arr if inf else None))
+        am = list(getattr(scene, "alpha_masks", None) or [])
+        am_arr = (pt_alpha_mask * max(1, len(am)))(*am)
+        self._check(self.lib.pt_scene_set_alpha_masks(self.h, C.c_uint32(len(am)), am_arr if am else None))
         self._check(self.lib.pt_scene_upload(self.h, C.byref(scene.desc)))
         info = pt_scene_info()
         self._check(self.lib.pt_scene_info_get(self.h, C.byref(info)))

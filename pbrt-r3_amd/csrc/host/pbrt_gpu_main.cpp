@@ -71,7 +71,7 @@ struct Rendezvous {
     }
 };
 
-static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
+static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const pt_alpha_mask* am, uint32_t n_am, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
                             double* secs_out, std::vector<RankReport>* reports, std::vector<float>* xyzw_out) {
     const int n_gpus = (int)devs.size();
     bool shared_device = false;
@@ -105,6 +105,7 @@ static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* i
     bool ok = each([&](int r) {
         if (!check(r, pt_context_create(devs[(size_t)r], &ctxs[(size_t)r]), "no usable HIP device")) return;
         if (!check(r, pt_scene_set_infinite_lights(ctxs[(size_t)r], n_inf, inf), "infinite lights")) return;
+        if (!check(r, pt_scene_set_alpha_masks(ctxs[(size_t)r], n_am, am), "alpha masks")) return;
         check(r, pt_scene_upload(ctxs[(size_t)r], dsc), "scene upload");
     });
     double secs = 0;
@@ -215,6 +216,8 @@ int main(int argc, char** argv) {
     if (!quiet && pth_scene_warnings(scene)[0]) std::fprintf(stderr, "%s", pth_scene_warnings(scene));
     uint32_t n_inf_lights = 0;
     const pt_infinite_light* inf_lights = pth_scene_get_infinite_lights(scene, &n_inf_lights);
+    uint32_t n_alpha_masks = 0;
+    const pt_alpha_mask* alpha_masks = pth_scene_get_alpha_masks(scene, &n_alpha_masks);
     if (outfile.empty()) {
         outfile = pth_scene_output_filename(scene);
         size_t dot = outfile.find_last_of('.');
@@ -231,7 +234,7 @@ int main(int argc, char** argv) {
         double secs = 0;
         std::vector<RankReport> reports;
         std::vector<float> xyzw;
-        if (render_multi_gpu(pth_scene_get_desc(scene), inf_lights, n_inf_lights, devices, rgb, &info, &c, &secs, &reports, xyzw_file.empty() ? nullptr : &xyzw) != 0) { pth_scene_free(scene); return 1; }
+        if (render_multi_gpu(pth_scene_get_desc(scene), inf_lights, n_inf_lights, alpha_masks, n_alpha_masks, devices, rgb, &info, &c, &secs, &reports, xyzw_file.empty() ? nullptr : &xyzw) != 0) { pth_scene_free(scene); return 1; }
         if (!xyzw_file.empty() && !write_floats(xyzw_file, xyzw)) return 1;
         int w = info.cropped_bounds[2] - info.cropped_bounds[0], h = info.cropped_bounds[3] - info.cropped_bounds[1];
         const pt_scene_desc* dsc = pth_scene_get_desc(scene);
@@ -254,6 +257,7 @@ int main(int argc, char** argv) {
     if (st != PT_OK) { std::fprintf(stderr, "pbrt_gpu: no usable HIP device %d (there is no CPU fallback)\n", device); return 1; }
     auto fail = [&](const char* what) { std::fprintf(stderr, "pbrt_gpu: %s: %s\n", what, pt_last_error(ctx)); pt_context_destroy(ctx); pth_scene_free(scene); return 1; };
     if (pt_scene_set_infinite_lights(ctx, n_inf_lights, inf_lights) != PT_OK) return fail("infinite lights");
+    if (pt_scene_set_alpha_masks(ctx, n_alpha_masks, alpha_masks) != PT_OK) return fail("alpha masks");
     if (pt_scene_upload(ctx, pth_scene_get_desc(scene)) != PT_OK) return fail("scene upload");
     pt_scene_info info;
     pt_scene_info_get(ctx, &info);

@@ -139,6 +139,7 @@ public:
     std::map<std::string, uint32_t> node_float_textures, node_spectrum_textures;   // name -> index into textures
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
+    std::vector<pt_alpha_mask> alpha_masks;                             // "alpha" / "shadowalpha" of trianglemesh / plymesh shapes, one per mesh
     uint32_t n_world_lights = 0;                                        // lights appended to the scene's list so far (area lights per primitive)
     bool any_n = false, any_s = false, any_uv = false;
     pt_scene_desc desc;
@@ -681,8 +682,7 @@ public:
         if (name != "trianglemesh" && name != "plymesh" && name != "sphere") { fail("Shape \"" + name + "\": only trianglemesh, plymesh and sphere are on the accelerated path"); return; }
         const TransformSet& ts = transforms.back();
         if (std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) != 0) { fail("animated transforms are outside the accelerated path"); return; }
-        if (p.has("alpha") || p.has("shadowalpha")) { fail("alpha-masked shapes are outside the accelerated path"); return; }
-        if (name == "sphere") {                                     // create_sphere_shape (shapes/sphere.rs:401-420)
+        if (name == "sphere") {                                     // create_sphere_shape (shapes/sphere.rs:401-420); "alpha" / "shadowalpha" are not read there
             const Xf& o2w = ts.t[0];
             if (o2w.m.a[12] != 0.0f || o2w.m.a[13] != 0.0f || o2w.m.a[14] != 0.0f || o2w.m.a[15] != 1.0f) { fail("sphere under a projective transform is outside the accelerated path"); return; }
             pt_sphere sp;
@@ -745,6 +745,23 @@ public:
         emit_mesh(p, idx, *ps, nn, sv, uv);
     }
 
+    // get_alpha_texture / get_shadow_alpha_texture (triangle.rs:654-694), shape parameters only: "texture <n>" first -- a name that is no
+    // float texture gives no mask, even beside a "float <n>" --, else "float <n>".  A named texture that folded to a constant is a
+    // ConstantTexture there: the same value at every hit, so a constant mask here.
+    void alpha_param(const ParamSet& p, const char* n, int32_t* kind, float* value, int32_t* tex) {
+        *kind = PT_ALPHA_NONE; *value = 0.0f; *tex = -1;
+        auto t = p.textures.find(n);
+        if (t != p.textures.end()) {
+            if (t->second.empty()) return;
+            auto nd = node_float_textures.find(t->second[0]);
+            if (nd != node_float_textures.end()) { *kind = PT_ALPHA_TEXTURE; *tex = (int32_t)nd->second; return; }
+            auto c = float_textures.find(t->second[0]);
+            if (c != float_textures.end()) { *kind = PT_ALPHA_CONSTANT; *value = c->second; }
+            return;
+        }
+        auto f = p.floats.find(n);
+        if (f != p.floats.end() && !f->second.empty()) { *kind = PT_ALPHA_CONSTANT; *value = f->second[0]; }
+    }
     // create_triangle_mesh (triangle.rs:696-731) on object-space arrays: pre-transform, flags, material / light, degenerate filter
     void emit_mesh(const ParamSet& p, const std::vector<uint32_t>& idx, const std::vector<float>& obj_p, const std::vector<float>* nn,
                    const std::vector<float>* sv, const std::vector<float>& uv) {
@@ -790,6 +807,14 @@ public:
         }
         if (mesh.area_light >= 0) n_world_lights += (uint32_t)kept;
         meshes.push_back(mesh);
+        {   // AlphaMaskShape around every triangle of the mesh (triangle.rs:852-863, plymesh.rs:365-376)
+            pt_alpha_mask am;
+            std::memset(&am, 0, sizeof(am));
+            am.mesh = mesh_id;
+            alpha_param(p, "alpha", &am.alpha_kind, &am.alpha_value, &am.alpha_texture);
+            alpha_param(p, "shadowalpha", &am.shadow_kind, &am.shadow_value, &am.shadow_texture);
+            if (am.alpha_kind != PT_ALPHA_NONE || am.shadow_kind != PT_ALPHA_NONE) alpha_masks.push_back(am);
+        }
         size_t old_nv = P.size() / 3;
         P.insert(P.end(), wp.begin(), wp.end());
         auto grow = [&](std::vector<float>& dst, const std::vector<float>& src, int width, bool& any) {
@@ -1017,6 +1042,10 @@ const pt_scene_desc* pth_scene_get_desc(const pth_scene* s) { return s ? &s->ctx
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.infinite_lights.size() : 0u;
     return (s && !s->ctx.infinite_lights.empty()) ? s->ctx.infinite_lights.data() : nullptr;
+}
+const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n) {
+    if (n) *n = s ? (uint32_t)s->ctx.alpha_masks.size() : 0u;
+    return (s && !s->ctx.alpha_masks.empty()) ? s->ctx.alpha_masks.data() : nullptr;
 }
 const char* pth_scene_output_filename(const pth_scene* s) { return s ? s->ctx.out_filename.c_str() : ""; }
 void pth_scene_set_pixelsamples(pth_scene* s, int spp) { if (s && spp > 0) s->ctx.desc.spp = spp; }

@@ -66,6 +66,8 @@ struct pt_context {
     PtScene sc;
     pt_scene_info info;
     std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
+    std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
+    bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
     std::vector<uint32_t> sobol_m32;
@@ -537,6 +539,12 @@ pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_inf
     return PT_OK;
 }
 
+pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_mask* masks) {
+    if (!ctx || (n && !masks)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->alpha_masks.assign(masks, masks + n);
+    return PT_OK;
+}
+
 static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d);
 // The infinite lights set with pt_scene_set_infinite_lights belong to this upload alone: a later upload of another scene does not inherit
 // them (their image indices point into this descriptor's images[]).
@@ -544,6 +552,7 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (!ctx || !d) return PT_ERR_INVALID_ARGUMENT;
     const pt_status st = scene_upload(ctx, d);
     ctx->inf_lights.clear();
+    ctx->alpha_masks.clear();
     return st;
 }
 
@@ -639,6 +648,46 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: its image is not a power-of-two pyramid of 1 or 3 channels (at most 16384 wide)");
         if (il.n_samples < 0 || il.n_samples > 4096) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: n_samples outside [0, 4096]");
     }
+    // alpha masks: one record per mesh, float textures only (a texture whose channels are equal wherever it is evaluated)
+    std::vector<uint8_t> mesh_alpha(d->n_meshes, 0);    // 1: the mesh's triangles carry PT_TRI_ALPHA
+    {
+        std::vector<int8_t> is_float(d->n_textures, 0);
+        auto eq3 = [](const float* v) { return v[0] == v[1] && v[1] == v[2]; };
+        for (uint32_t i = 0; i < d->n_textures; i++) {
+            const pt_texture& t = d->textures[i];
+            auto slot = [&](int k) { return t.tex[k] >= 0 ? is_float[t.tex[k]] != 0 : eq3(t.value[k]); };
+            bool f = false;
+            switch (t.type) {
+                case PT_TEX_CONSTANT: f = eq3(t.value[0]); break;
+                case PT_TEX_SCALE: case PT_TEX_CHECKERBOARD_2D: case PT_TEX_CHECKERBOARD_3D: case PT_TEX_DOTS: f = slot(0) && slot(1); break;
+                case PT_TEX_MIX: f = slot(0) && slot(1); break;       // (the amount is read as channel 0 either way)
+                case PT_TEX_BILERP: f = eq3(t.value[0]) && eq3(t.value[1]) && eq3(t.value[2]) && eq3(t.value[3]); break;
+                case PT_TEX_FBM: case PT_TEX_WRINKLED: case PT_TEX_WINDY: f = true; break;
+                case PT_TEX_IMAGEMAP: f = d->images[t.image].channels == 1; break;
+                default: f = false; break;           // uv, marble: three different channels
+            }
+            is_float[i] = f ? 1 : 0;
+        }
+        for (const pt_alpha_mask& am : ctx->alpha_masks) {
+            if (am.mesh >= d->n_meshes) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "alpha mask: mesh index out of range");
+            if (mesh_alpha[am.mesh]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "alpha mask: two records for one mesh");
+            const int32_t kinds[2] = {am.alpha_kind, am.shadow_kind}, texs[2] = {am.alpha_texture, am.shadow_texture};
+            for (int k = 0; k < 2; k++) {
+                if (kinds[k] < PT_ALPHA_NONE || kinds[k] > PT_ALPHA_TEXTURE) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "alpha mask: unknown kind");
+                if (kinds[k] == PT_ALPHA_TEXTURE) {
+                    if (texs[k] < 0 || (uint32_t)texs[k] >= d->n_textures || !d->textures) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "alpha mask: texture index out of range");
+                    if (!is_float[texs[k]]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "alpha mask: not a float texture");
+                }
+            }
+            // AlphaMaskShape::new (alphamask.rs:27-53): a constant > 0 does nothing
+            const bool live = am.alpha_kind == PT_ALPHA_TEXTURE || am.shadow_kind == PT_ALPHA_TEXTURE || (am.alpha_kind == PT_ALPHA_CONSTANT && am.alpha_value <= 0.0f) ||
+                              (am.shadow_kind == PT_ALPHA_CONSTANT && am.shadow_value <= 0.0f);
+            mesh_alpha[am.mesh] = live ? 1 : 2;
+        }
+        for (uint8_t& m : mesh_alpha) if (m == 2) m = 0;
+    }
+    bool any_alpha = false;
+    for (uint8_t m : mesh_alpha) any_alpha |= m != 0;
     // integrator-specific refusals come after the index range checks above (they dereference materials[])
     if (d->integrator == PT_INTEGRATOR_PATH && d->sampler == PT_SAMPLER_HALTON && d->max_depth > 124)
         return ctx->fail(PT_ERR_UNSUPPORTED, "path with the Halton sampler and maxdepth above 124: a path that long asks for more than the sampler's 1000 "
@@ -705,6 +754,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
                 if (((mf & PT_MESH_HAS_N) && d->N) || ((mf & PT_MESH_HAS_S) && d->S) || ((mf & PT_MESH_HAS_UV) && d->UV)) f |= PT_TRI_HAS_ATTR;
                 const int32_t mat = d->meshes[i].material;
                 if (mat >= 0 && d->materials[mat].type != PT_MATERIAL_NONE) f |= (uint32_t)(mat + 1) << PT_TRI_MATERIAL_SHIFT;
+                if (mesh_alpha[i]) f |= PT_TRI_ALPHA;
                 m_triflags[i] = f;
                 if (!d->N) mf &= ~PT_MESH_HAS_N;
                 if (!d->S) mf &= ~PT_MESH_HAS_S;
@@ -842,6 +892,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         if (((mf & PT_MESH_HAS_N) && d->N) || ((mf & PT_MESH_HAS_S) && d->S) || ((mf & PT_MESH_HAS_UV) && d->UV)) f |= PT_TRI_HAS_ATTR;
         int32_t mat = d->meshes[d->tri_mesh[t]].material;
         if (mat >= 0 && d->materials[mat].type != PT_MATERIAL_NONE) f |= (uint32_t)(mat + 1) << PT_TRI_MATERIAL_SHIFT;
+        if (mesh_alpha[d->tri_mesh[t]]) f |= PT_TRI_ALPHA;
         tri_flags[t] = f;
     }
     });
@@ -1160,6 +1211,27 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         else mats[i].sort_bin = general ? PT_SORT_GENERAL0 + std::min(n_general_bins++, PT_SORT_TEX0 - PT_SORT_GENERAL0 - 1u)
                                         : std::min(n_matte_bins++, PT_SORT_GENERAL0 - 1u);
     }
+    // alpha masks: the mask textures' programs and the per-mesh table behind them, located by word 0 (PT_ALPHA_CUT, pt_device.h)
+    if (any_alpha) {
+        std::vector<uint32_t> words(2 * (size_t)d->n_meshes, 0u);
+        for (const pt_alpha_mask& am : ctx->alpha_masks) {
+            const int32_t kinds[2] = {am.alpha_kind, am.shadow_kind}, texs[2] = {am.alpha_texture, am.shadow_texture};
+            const float vals[2] = {am.alpha_value, am.shadow_value};
+            for (int k = 0; k < 2; k++) {
+                uint32_t w = 0;
+                if (kinds[k] == PT_ALPHA_CONSTANT && vals[k] <= 0.0f) w = PT_ALPHA_CUT;
+                else if (kinds[k] == PT_ALPHA_TEXTURE) {
+                    w = add_program((uint32_t)texs[k]);
+                    if (!w) return ctx->fail(PT_ERR_UNSUPPORTED, "an alpha mask's texture graph needs more than 12 nodes");
+                }
+                words[2 * (size_t)am.mesh + k] = w;
+            }
+        }
+        tex_prog[0] = (uint32_t)tex_prog.size();
+        tex_prog.insert(tex_prog.end(), words.begin(), words.end());
+    }
+    bool any_alpha_tex = false;
+    for (const pt_alpha_mask& am : ctx->alpha_masks) any_alpha_tex |= mesh_alpha[am.mesh] && (am.alpha_kind == PT_ALPHA_TEXTURE || am.shadow_kind == PT_ALPHA_TEXTURE);
 
     PtScene& sc = ctx->sc;
     std::memset(&sc, 0, sizeof(sc));
@@ -1249,7 +1321,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (d->n_spheres) { if ((st = upload(ctx, ctx->d_spheres, sph.data(), sph.size())) != PT_OK) return st; } else ctx->d_spheres.release();
     if (d->n_instances) { if ((st = upload(ctx, ctx->d_instances, dinst.data(), dinst.size())) != PT_OK) return st; } else ctx->d_instances.release();
     std::vector<PtImage> dimages(d->n_images);
-    const bool images_on_device = (any_textured || !ctx->inf_lights.empty()) && d->n_images;
+    const bool images_on_device = (any_textured || !ctx->inf_lights.empty() || any_alpha_tex) && d->n_images;
     if (images_on_device) {           // all pyramids in one buffer
         size_t total = 0;
         for (uint32_t i = 0; i < d->n_images; i++) {
@@ -1283,11 +1355,11 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         for (uint32_t i = 0; i < d->n_images; i++) dimages[i].texels = ctx->d_image_texels.as<float>() + base[i];
         if ((st = upload(ctx, ctx->d_images, dimages.data(), dimages.size())) != PT_OK) return st;
     } else { ctx->d_image_texels.release(); ctx->d_images.release(); }
-    if (any_textured) {
-        if ((st = upload(ctx, ctx->d_textures, d->textures, d->n_textures)) != PT_OK) return st;
+    if (any_textured || any_alpha) {
+        if (d->n_textures) { if ((st = upload(ctx, ctx->d_textures, d->textures, d->n_textures)) != PT_OK) return st; } else ctx->d_textures.release();
         if ((st = upload(ctx, ctx->d_tex_prog, tex_prog.data(), tex_prog.size())) != PT_OK) return st;
-        if ((st = upload(ctx, ctx->d_mat_params, mparams.data(), mparams.size())) != PT_OK) return st;
-    } else { ctx->d_textures.release(); ctx->d_tex_prog.release(); ctx->d_mat_params.release(); }
+    } else { ctx->d_textures.release(); ctx->d_tex_prog.release(); }
+    if (any_textured) { if ((st = upload(ctx, ctx->d_mat_params, mparams.data(), mparams.size())) != PT_OK) return st; } else ctx->d_mat_params.release();
     if (d->N) { if ((st = upload(ctx, ctx->d_N, d->N, 3 * (size_t)d->n_vertices)) != PT_OK) return st; } else ctx->d_N.release();
     if (d->S) { if ((st = upload(ctx, ctx->d_S, d->S, 3 * (size_t)d->n_vertices)) != PT_OK) return st; } else ctx->d_S.release();
     if (d->UV) { if ((st = upload(ctx, ctx->d_UV, d->UV, 2 * (size_t)d->n_vertices)) != PT_OK) return st; } else ctx->d_UV.release();
@@ -1306,8 +1378,9 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     sc.lights = ctx->d_lights.as<PtLight>();
     sc.n_lights = (uint32_t)lights.size();
     sc.textured = any_textured ? 1u : 0u;
-    sc.textures = any_textured ? ctx->d_textures.as<pt_texture>() : nullptr;
-    sc.tex_prog = any_textured ? ctx->d_tex_prog.as<uint32_t>() : nullptr;
+    sc.textures = (any_textured || any_alpha) && d->n_textures ? ctx->d_textures.as<pt_texture>() : nullptr;
+    sc.tex_prog = (any_textured || any_alpha) ? ctx->d_tex_prog.as<uint32_t>() : nullptr;
+    ctx->scene_alpha = any_alpha;
     sc.images = images_on_device ? ctx->d_images.as<PtImage>() : nullptr;
     sc.mat_params = any_textured ? ctx->d_mat_params.as<PtMatParams>() : nullptr;
     sc.spheres = d->n_spheres ? ctx->d_spheres.as<PtSphere>() : nullptr;
@@ -1820,7 +1893,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 PT_HIP(hipMemsetAsync(ctx->d_ticket.p, 0, 16, ctx->stream));
                 PT_HIP(ptk_ao_tag(ctx->stream, ctx->grid_wide, ctx->paths, n_pix, n_paths, s0));
                 PT_HIP(hipEventRecord(a, ctx->stream));
-                PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err));
+                PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                 ctx->trace_launches++;
                 PT_HIP(ptk_ao_rays(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_o, ao_d, ao_w, ao_count, cnt));
                 {   // the occlusion rays as shadow work items of the wavefront traversal kernel itself (any hit -> occlusion flag);
@@ -1830,7 +1903,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     PtQueues AQ = Q;
                     AQ.shadow = ao_ids;
                     PT_HIP(ptk_ao_queue(ctx->stream, AQ, ao_count, (uint32_t)sc.ao_samples));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, AP, AQ, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err));
+                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, AP, AQ, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     ctx->trace_launches++;
                 }
                 PT_HIP(hipEventRecord(b, ctx->stream));
@@ -1882,7 +1955,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     if (ev_i < 3000) { spans.push_back({ev_i, 0}); ev_i += 3; }
                     Qn.cur = Q.cur;
                     PT_HIP(hipEventRecord(a, ctx->stream));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err));
+                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     PT_HIP(ptk_prep(ctx->stream, Qn, 0));
                     PT_HIP(ptk_rec_enter(ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, Qn, R, cnt, rec_epp));
                     PtQueues Qt = Qn;
@@ -1900,7 +1973,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                             Qt.shadow = sorted;
                         }
                     }
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, NP, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err));
+                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, NP, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     ctx->trace_launches += 2;
                     PT_HIP(hipEventRecord(b, ctx->stream));
                     PT_HIP(ptk_rec_next(ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, R));
@@ -1924,8 +1997,9 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 // traced twice, by each kernel, on the same lists; results are identical (the second launch rewrites them), the counters are put back.
                 const char* far_min_env = std::getenv("PBRTGPU_TRACE_FAR_MIN_BYTES");          // (tests: the trial on small scenes)
                 const size_t far_min_bytes = far_min_env ? (size_t)std::strtoull(far_min_env, nullptr, 10) : ((size_t)256 << 20);
-                const bool far_able = ptk_trace_has_far(sc) && ctx->n_nodes_up * sizeof(PtNode) + ctx->n_tris_up * sizeof(PtTri) > far_min_bytes;
-                if (ctx->trace_far >= 0 || !far_able) ctx->trace_far_choice = (ctx->trace_far > 0 && ptk_trace_has_far(sc)) ? 1 : 0;
+                // (a scene with alpha masks runs k_trace_alpha for every ray: no far trial, PBRTGPU_TRACE_FAR ignored)
+                const bool far_able = !ctx->scene_alpha && ptk_trace_has_far(sc) && ctx->n_nodes_up * sizeof(PtNode) + ctx->n_tris_up * sizeof(PtTri) > far_min_bytes;
+                if (ctx->trace_far >= 0 || !far_able) ctx->trace_far_choice = (ctx->trace_far > 0 && ptk_trace_has_far(sc) && !ctx->scene_alpha) ? 1 : 0;
                 int bounce_i = 0;
                 PtQueues Q_last_trace = Q;
                 auto trace = [&]() -> hipError_t {
@@ -1936,7 +2010,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     cont_sorted = nullptr;
                     Q_last_trace = Qt;
                     return ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err,
-                                     ctx->trace_far_choice > 0 ? 1 : 0);
+                                     ctx->trace_far_choice > 0 ? 1 : 0, ctx->scene_alpha ? 1 : 0);
                 };
                 auto far_trial = [&](hipEvent_t near_a, hipEvent_t near_b) -> pt_status {      // right after bounce 1's launch by k_trace (timed by near_a .. near_b)
                     hipEvent_t fa = get_event(ctx, ev_i), fb = get_event(ctx, ev_i + 1);
@@ -1946,7 +2020,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     PT_HIP(hipMemcpyAsync(ctx->d_cnt_save.p, cnt, sizeof(PtCounters), hipMemcpyDeviceToDevice, ctx->stream));
                     PT_HIP(hipMemsetAsync(Q.counts + PT_Q_SEG_TICKET0, 0, 8u * 32u * 4u, ctx->stream));          // the launch's work tickets
                     PT_HIP(hipEventRecord(fa, ctx->stream));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q_last_trace, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 1));
+                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q_last_trace, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 1, 0));
                     PT_HIP(hipEventRecord(fb, ctx->stream));
                     PT_HIP(hipMemcpyAsync(cnt, ctx->d_cnt_save.p, sizeof(PtCounters), hipMemcpyDeviceToDevice, ctx->stream));
                     PT_HIP(hipStreamSynchronize(ctx->stream));
@@ -2255,7 +2329,7 @@ static pt_status trace_batch(pt_context* ctx, uint32_t n, const float* o, const 
     PT_HIP(hipEventRecord(a, ctx->stream));
     PT_HIP(ptk_trace_batch(ctx->stream, ctx->grid_trace, ctx->sc, n, d_o.as<float>(), d_d.as<float>(), d_t.as<float>(), any_hit ? nullptr : d_out.as<pt_hit>(),
                            any_hit ? d_out.as<uint8_t>() : nullptr, any_hit, ctx->d_ticket.as<uint32_t>(), ctx->d_counters.as<PtCounters>(),
-                           ctx->d_spill.as<uint32_t>(), ctx->spill_depth, ctx->d_err.as<uint32_t>()));
+                           ctx->d_spill.as<uint32_t>(), ctx->spill_depth, ctx->d_err.as<uint32_t>(), ctx->scene_alpha ? 1 : 0));
     PT_HIP(hipEventRecord(b, ctx->stream));
     PT_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0;
@@ -2319,7 +2393,7 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
     hipEvent_t a = get_event(ctx, 0), b = get_event(ctx, 1);
     PT_HIP(hipEventRecord(a, ctx->stream));
     PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, ctx->sc, P, Q, ctx->d_counters.as<PtCounters>(), ctx->d_spill.as<uint32_t>(), ctx->spill_depth,
-                     ctx->d_err.as<uint32_t>()));
+                     ctx->d_err.as<uint32_t>(), 0, ctx->scene_alpha ? 1 : 0));
     PT_HIP(hipEventRecord(b, ctx->stream));
     PT_HIP(ptk_wavefront_results(ctx->stream, ctx->grid_wide, ctx->sc, P, n, d_kind.as<uint8_t>(), d_out.as<pt_hit>(), d_occ.as<uint8_t>()));
     PT_HIP(hipMemsetAsync(Q.counts, 0, PT_COUNTS_WORDS * 4, ctx->stream));

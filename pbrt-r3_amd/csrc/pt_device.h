@@ -75,7 +75,11 @@ struct PtNode {
 #define PT_TRI_HAS_ATTR 8u       // mesh carries N / S / UV: shading must also read PtTriInfo
 #define PT_TRI_SPHERE 16u        // the record stands for a sphere: p0[0] holds its index into PtScene::spheres (as bits)
 #define PT_TRI_INSTANCE 32u      // the record stands for an object instance: p0[0] holds its index into PtScene::instances (as bits)
+#define PT_TRI_ALPHA 64u         // the mesh has an alpha mask (pt_alpha_mask): the alpha traversal kernels evaluate it at each candidate hit
 #define PT_TRI_MATERIAL_SHIFT 16 // bits 16..31: material index + 1 (0 = no material)
+// Alpha masks on the device: in a scene with one, word 0 of PtScene::tex_prog (never a program: offset 0 means "constant") is the offset of
+// a per-mesh table of two words, "alpha" then "shadowalpha": 0 no mask, PT_ALPHA_CUT a constant <= 0, else the offset of the texture's program.
+#define PT_ALPHA_CUT 0xffffffffu
 struct PtTri {
     float p0[3];
     uint32_t prim;               // caller's triangle index

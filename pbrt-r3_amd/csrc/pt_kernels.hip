@@ -637,12 +637,45 @@ PT_DEV bool sphere_rec_test(const PtScene& sc, const TriVerts& tv, const LaneRay
     *t = sh.t;
     return true;
 }
-template <bool SPH>
-PT_DEV bool prim_test(const PtScene& sc, const TriVerts& tv, const LaneRay& r, bool any_hit, TriHit& h) {
+// AlphaMaskShape::intersect / intersect_p (alphamask.rs:73-113) at a candidate that passed the triangle test (record `rec`, barycentrics b):
+// the masks see the interaction Triangle::intersect builds (triangle.rs:349-449) -- p and uv from the barycentrics, no ray differentials,
+// so an image map reads level 0 bilinearly (mipmap.rs:620-629) -- in the space the ray is in: an instance's object space
+// (transformed_primitive.rs:26-45).  Closest-hit rays test "alpha", shadow rays "alpha" then "shadowalpha"; a value <= 0 rejects the hit.
+// Out of line, with the texture interpreter (tex_eval) out of line behind it: the traversal loop keeps its registers.
+__device__ __noinline__ bool alpha_pass(const PtScene& sc, uint32_t rec, V3 p0, V3 p1, V3 p2, uint32_t flags, float b0, float b1, float b2, bool any_hit) {
+    const PtTriInfo ti = sc.tri_info[rec];
+    const uint32_t* w = sc.tex_prog + sc.tex_prog[0] + 2u * ti.mesh;      // the mesh's two words (pt_device.h, PT_ALPHA_CUT)
+    const uint32_t wa = w[0], ws = any_hit ? w[1] : 0u;
+    if (wa == PT_ALPHA_CUT || ws == PT_ALPHA_CUT) return false;            // a constant <= 0: no texture work
+    if (!(wa | ws)) return true;
+    V2 uv0 = mk2(0.0f, 0.0f), uv1 = mk2(1.0f, 0.0f), uv2 = mk2(1.0f, 1.0f);
+    if ((flags & PT_TRI_HAS_ATTR) && (ti.mesh_flags & PT_MESH_HAS_UV) && sc.UV) {
+        uv0 = mk2(sc.UV[2 * ti.v[0]], sc.UV[2 * ti.v[0] + 1]);
+        uv1 = mk2(sc.UV[2 * ti.v[1]], sc.UV[2 * ti.v[1] + 1]);
+        uv2 = mk2(sc.UV[2 * ti.v[2]], sc.UV[2 * ti.v[2] + 1]);
+    }
+    TexHit th;
+    th.p = b0 * p0 + b1 * p1 + b2 * p2;
+    th.uv = mk2(b0 * uv0.x + b1 * uv1.x + b2 * uv2.x, b0 * uv0.y + b1 * uv1.y + b2 * uv2.y);
+    RayDiffs none;
+    none.rx_o = none.ry_o = none.rx_d = none.ry_d = mk3(0.0f, 0.0f, 0.0f);
+    compute_differentials(th, th.p, mk3(0.0f, 0.0f, 1.0f), mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 0.0f), false, none);
+    if (wa && tex_eval(sc.textures, sc.tex_prog + wa, th, sc.images).x <= 0.0f) return false;
+    if (ws && tex_eval(sc.textures, sc.tex_prog + ws, th, sc.images).x <= 0.0f) return false;
+    return true;
+}
+// ALPHA (the alpha traversal kernels): a triangle of a masked mesh is a hit only if its masks let it through; a rejected candidate leaves
+// t_max as it was (alphamask.rs:80-83).  `rec` is the record's index (read by the mask only).
+template <bool SPH, bool ALPHA = false>
+PT_DEV bool prim_test(const PtScene& sc, const TriVerts& tv, const LaneRay& r, bool any_hit, TriHit& h, uint32_t rec = 0) {
     if constexpr (SPH) {
         if (tv.flags & PT_TRI_SPHERE) return sphere_rec_test(sc, tv, r, any_hit, &h.t);
     }
-    return tri_test(r.rp, tv.p0, tv.p1, tv.p2, tv.flags, r.ray_tmax, h);
+    bool ok = tri_test(r.rp, tv.p0, tv.p1, tv.p2, tv.flags, r.ray_tmax, h);
+    if constexpr (ALPHA) {
+        if (ok && (tv.flags & PT_TRI_ALPHA)) ok = alpha_pass(sc, rec, tv.p0, tv.p1, tv.p2, tv.flags, h.b0, h.b1, h.b2, any_hit);
+    }
+    return ok;
 }
 // Transform::transform_ray with the instance's inverse (transformed_primitive.rs:27-29, transform.rs:184-203, :245-282)
 PT_DEV void instance_ray(const PtInstance& in, V3 ro, V3 rd, V3* o_out, V3* d_out) {
@@ -659,13 +692,13 @@ PT_DEV void instance_ray(const PtInstance& in, V3 ro, V3 rd, V3* o_out, V3* d_ou
     }
     *o_out = o; *d_out = d;
 }
-template <bool SPH, bool INST>
+template <bool SPH, bool INST, bool ALPHA = false>
 PT_DEV void ray_step_tri(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c, uint32_t base = 0);
 PT_DEV void ray_step_node(const PtScene& sc, LaneRay& r, TravCtx& c);
 // TransformedPrimitive::intersect / intersect_p (transformed_primitive.rs:26-48): the ray goes to instance space, the object's
 // accelerator is walked to the end on the stack above the caller's entries (the other lanes of the wave wait: instances are a
 // breadth feature, not the hot path), t carries over because the direction is not renormalised.
-template <bool SPH>
+template <bool SPH, bool ALPHA = false>
 __device__ __noinline__ bool instance_rec_test(const PtScene& sc, uint32_t inst, const LaneRay& r, bool any_hit, TravCtx& c, float* t_out, int32_t* rec_out) {
     const PtInstance& in = sc.instances[inst];
     V3 o, d;
@@ -683,11 +716,11 @@ __device__ __noinline__ bool instance_rec_test(const PtScene& sc, uint32_t inst,
     if (in.direct) {                     // a single primitive, wrapped without an accelerator: no root box, not a counted leaf test
         TriVerts tv = load_tri(sc.tris, in.root_ref);
         TriHit h;
-        if (prim_test<SPH>(sc, tv, ri, any_hit, h)) { ri.best = (int32_t)in.root_ref; ri.ray_tmax = h.t; }
+        if (prim_test<SPH, ALPHA>(sc, tv, ri, any_hit, h, in.root_ref)) { ri.best = (int32_t)in.root_ref; ri.ray_tmax = h.t; }
     } else if (box_root_test(in.root_lo, in.root_hi, o, ri.idir, ri.sbits, ri.ray_tmax, ri.tmin, ri.tmax)) {
         ri.top = in.root_ref; ri.sp = base + 1;
         while (ri.sp > base) {
-            if (ri.top & PT_LEAF_BIT) ray_step_tri<SPH, false>(sc, ri, any_hit, c, base);
+            if (ri.top & PT_LEAF_BIT) ray_step_tri<SPH, false, ALPHA>(sc, ri, any_hit, c, base);
             else ray_step_node(sc, ri, c);
         }
     }
@@ -695,7 +728,7 @@ __device__ __noinline__ bool instance_rec_test(const PtScene& sc, uint32_t inst,
     *t_out = ri.ray_tmax; *rec_out = ri.best;
     return true;
 }
-template <bool SPH, bool INST>
+template <bool SPH, bool INST, bool ALPHA>
 PT_DEV void ray_step_tri(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c, uint32_t base) {
     uint32_t rec = stk_pop(c, r.top, r.sp) & PT_LEAF_FIRST_MASK;
     bool leaf_hit = false;
@@ -704,14 +737,14 @@ PT_DEV void ray_step_tri(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c
             TriVerts t0 = load_tri(sc.tris, rec), t1 = load_tri(sc.tris, rec + 1);   // array is padded by one record
             TriHit h;
             c.n_tris++;
-            if (prim_test<SPH>(sc, t0, r, any_hit, h)) {
+            if (prim_test<SPH, ALPHA>(sc, t0, r, any_hit, h, rec)) {
                 r.best = (int32_t)rec; leaf_hit = true;
                 if (any_hit) { r.sp = base; r.top = PT_EMPTY_REF; return; }
                 r.ray_tmax = h.t;                           // GeometricPrimitive::intersect: r.t_max = t_hit
             }
             if (t0.flags & PT_TRI_LAST) break;
             c.n_tris++;
-            if (prim_test<SPH>(sc, t1, r, any_hit, h)) {
+            if (prim_test<SPH, ALPHA>(sc, t1, r, any_hit, h, rec + 1)) {
                 r.best = (int32_t)(rec + 1); leaf_hit = true;
                 if (any_hit) { r.sp = base; r.top = PT_EMPTY_REF; return; }
                 r.ray_tmax = h.t;
@@ -731,8 +764,8 @@ PT_DEV void ray_step_tri(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c
         uint32_t hit_inst = 0;
         if (INST && (t0.flags & PT_TRI_INSTANCE)) {
             hit_inst = __float_as_uint(t0.p0.x) + 1u;
-            hit = instance_rec_test<SPH>(sc, hit_inst - 1u, r, any_hit, c, &h.t, &hit_rec);
-        } else hit = prim_test<SPH>(sc, t0, r, any_hit, h);
+            hit = instance_rec_test<SPH, ALPHA>(sc, hit_inst - 1u, r, any_hit, c, &h.t, &hit_rec);
+        } else hit = prim_test<SPH, ALPHA>(sc, t0, r, any_hit, h, rec);
         if (hit) {
             r.best = hit_rec; leaf_hit = true;
             if (INST) r.best_inst = hit_inst;
@@ -744,9 +777,9 @@ PT_DEV void ray_step_tri(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c
     }
     if (leaf_hit) r.tmax = r.ray_tmax;                  // intersect_simd: tmax shrinks after the whole leaf
 }
-template <bool SPH, bool INST>
+template <bool SPH, bool INST, bool ALPHA = false>
 PT_DEV void ray_step(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c) {
-    if (ray_wants_tri(r)) ray_step_tri<SPH, INST>(sc, r, any_hit, c);
+    if (ray_wants_tri(r)) ray_step_tri<SPH, INST, ALPHA>(sc, r, any_hit, c);
     else ray_step_node(sc, r, c);
 }
 
@@ -770,7 +803,7 @@ PT_DEV void ray_set_direction_state(LaneRay& r, V3 o, V3 d) {        // what ray
     if (!(fabsf(r.idir.x) < PT_INF) || !(fabsf(r.idir.y) < PT_INF) || !(fabsf(r.idir.z) < PT_INF)) r.sbits |= 8u;
     ray_precompute(r.rp, o, d);
 }
-template <bool SPH>
+template <bool SPH, bool ALPHA = false>
 PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c) {
     uint32_t rec = stk_pop(c, r.top, r.sp) & PT_LEAF_FIRST_MASK;
     bool leaf_hit = false;
@@ -795,7 +828,7 @@ PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, Trav
             ri.ray_tmax = r.ray_tmax;
             if (in.direct) {                         // a single primitive, wrapped without an accelerator: no root box, not a counted leaf test
                 TriVerts tv = load_tri(sc.tris, in.root_ref);
-                hit = prim_test<SPH>(sc, tv, ri, any_hit, h);
+                hit = prim_test<SPH, ALPHA>(sc, tv, ri, any_hit, h, in.root_ref);
                 hit_rec = (int32_t)in.root_ref; hit_inst = inst + 1u;
             } else if (box_root_test(in.root_lo, in.root_hi, o, ri.idir, ri.sbits, ri.ray_tmax, ri.tmin, ri.tmax)) {
                 if (leaf_hit) r.tmax = r.ray_tmax;
@@ -808,7 +841,7 @@ PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, Trav
                 stk_push(c, r.top, r.sp, in.root_ref);
                 return;
             }
-        } else hit = prim_test<SPH>(sc, t0, r, any_hit, h);
+        } else hit = prim_test<SPH, ALPHA>(sc, t0, r, any_hit, h, rec);
         if (hit) {
             r.best = hit_rec; leaf_hit = true;
             r.best_inst = hit_inst;
@@ -1189,21 +1222,21 @@ PT_DEV void node_step_coop(const PtScene& sc, LaneRay& r, TravCtx& c, bool w_nod
 #endif
 
 // intersect_simd (qbvh_x86.rs:230-287): closest hit.  Returns record index or -1.
-template <bool SPH, bool INST>
+template <bool SPH, bool INST, bool ALPHA = false>
 PT_DEV int32_t trace_closest(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c, float* t_out, uint32_t* inst_out) {
     LaneRay r;
     ray_begin(sc, r, o, d, t_max);
-    while (!ray_done(r)) ray_step<SPH, INST>(sc, r, false, c);
+    while (!ray_done(r)) ray_step<SPH, INST, ALPHA>(sc, r, false, c);
     *t_out = r.ray_tmax;
     *inst_out = r.best_inst;
     return r.best;
 }
 // intersect_simd_p (qbvh_x86.rs:289-343): any hit
-template <bool SPH, bool INST>
+template <bool SPH, bool INST, bool ALPHA = false>
 PT_DEV bool trace_any(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c) {
     LaneRay r;
     ray_begin(sc, r, o, d, t_max);
-    while (!ray_done(r)) ray_step<SPH, INST>(sc, r, true, c);
+    while (!ray_done(r)) ray_step<SPH, INST, ALPHA>(sc, r, true, c);
     return r.best >= 0;
 }
 
@@ -1292,7 +1325,7 @@ PT_DEV uint32_t wave_ticket(uint32_t* ticket) {
 #endif
 // DIST: every leaf holds at most 8 triangles and its reference carries the count, so a leaf phase can pool the
 // triangles of all parked lanes and hand one (ray, triangle) test to each lane of the wave.
-template <bool DIST, bool SPH, bool INST = false, int TOUCH = 0>
+template <bool DIST, bool SPH, bool INST = false, int TOUCH = 0, bool ALPHA = false>
 PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     // LDS per block.  Pooled-leaf kernels: 16 stack slots x 1 KB + 8 KB node staging per wave + node-index exchange = 49 KB, three
     // blocks per CU (RT1M: 99.98 % of node visits find the stack at 13 entries or fewer; deeper lanes spill to HBM); a leaf round's
@@ -1423,7 +1456,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
 #endif
         // ---- retire finished rays: stores only
         if (kind != 0 && ray_done(r)) {
-            if (kind == 1) { P.hit_t[p] = r.ray_tmax; P.hit_rec[p] = r.best; if (INST) P.hit_inst[p] = r.best_inst; }
+            if (kind == 1) { P.hit_t[p] = r.ray_tmax; P.hit_rec[p] = r.best; if (INST && (!ALPHA || sc.n_instances)) P.hit_inst[p] = r.best_inst; }
             else if (kind == 2) P.occluded[p] = r.best >= 0 ? 1 : 0;
             else P.probe_rec[p] = r.best;
             kind = 0;
@@ -1736,7 +1769,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         ray_set_direction_state(r, f4_3(ro), mk3(rd.x, rd.y, rd.z));
                         r.tmin = w_tmin; r.tmax = hit_inside ? r.ray_tmax : w_tmax;
                         r.cur_inst = 0;
-                    } else ray_step_tri_enter<SPH>(sc, r, kind == 2, c);
+                    } else ray_step_tri_enter<SPH, ALPHA>(sc, r, kind == 2, c);
                 }
             } else {
                 if (w_tri) ray_step_tri<SPH, INST>(sc, r, kind == 2, c);
@@ -1782,6 +1815,12 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_tr
                                                                        uint32_t spill_depth, uint32_t* err) {
     trace_body<false, true, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
+// scenes with alpha masks, whatever else they hold (spheres, instances): k_trace_inst's per-lane traversal with the mask test at every
+// candidate hit of a masked mesh (prim_test<.., true>).  Every ray kind of every integrator runs here for such a scene.
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_alpha(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+                                                                        uint32_t spill_depth, uint32_t* err) {
+    trace_body<false, true, true, 0, true>(sc, P, Q, cnt, spill, spill_depth, err);
+}
 // scenes with spheres: a leaf record may stand for a sphere
 extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_sph_dist(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                            uint32_t spill_depth, uint32_t* err) {
@@ -1793,7 +1832,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, 2) k_trace_sph(PtScene sc
 }
 
 // ============================================================ hooks: plain ray batches
-template <bool SPH, bool INST = false>
+template <bool SPH, bool INST = false, bool ALPHA = false>
 PT_DEV void trace_batch_body(const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out, uint8_t* occ_out, int any_hit,
                              uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     __shared__ uint32_t s_stack[PT_LDS_STACK * PT_BLOCK];
@@ -1813,12 +1852,12 @@ PT_DEV void trace_batch_body(const PtScene& sc, uint32_t n, const float* o, cons
         V3 ro = ld3(o + 3 * (size_t)i), rd = ld3(d + 3 * (size_t)i);
         if (any_hit) {
             shadow++;
-            occ_out[i] = trace_any<SPH, INST>(sc, ro, rd, tmax[i], c) ? 1 : 0;
+            occ_out[i] = trace_any<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c) ? 1 : 0;
         } else {
             regular++;
             float t;
             uint32_t inst = 0;
-            int32_t rec = trace_closest<SPH, INST>(sc, ro, rd, tmax[i], c, &t, &inst);
+            int32_t rec = trace_closest<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c, &t, &inst);
             pt_hit h;
             h.t = 0.0f; h.prim = -1; h.b0 = 0.0f; h.b1 = 0.0f;
             if (rec >= 0 && INST && inst) {          // the hit is reported as the instance's own world primitive
@@ -1854,6 +1893,11 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_inst(PtScen
                                                                          pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
                                                                          uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
+                                                                          pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
+                                                                          uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
+    trace_batch_body<true, true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
 }
 
 // ============================================================ hook: caller rays through the wavefront's own traversal kernel
@@ -4367,7 +4411,11 @@ int ptk_shade_prof_read(unsigned long long* out16) {       // 1 when the library
 }
 bool ptk_trace_has_far(const PtScene& sc) { return sc.dist_leaves && !sc.n_instances && !sc.n_spheres; }
 hipError_t ptk_trace(hipStream_t st, int grid, int grid_dist, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, uint32_t* spill,
-                     uint32_t spill_depth, uint32_t* err, int far) {
+                     uint32_t spill_depth, uint32_t* err, int far, int alpha) {
+    if (alpha) {            // a scene with alpha masks: the one kernel that tests them, for every kind of ray (PBRTGPU_TRACE_FAR does not apply)
+        hipLaunchKernelGGL(k_trace_alpha, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
+        return PT_LAUNCH_CHECK();
+    }
     static const bool force_sph = std::getenv("PBRTGPU_FORCE_SPH_TRACE") != nullptr;      // diagnosis: what the sphere-capable kernel costs a scene without spheres
     if (sc.dist_leaves && !sc.n_instances) grid = grid_dist;      // the pooled-leaf kernels fit three blocks per CU, the others four
     if (sc.n_instances) hipLaunchKernelGGL(k_trace_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
@@ -4403,8 +4451,9 @@ hipError_t ptk_light_hooks(hipStream_t st, const PtScene& sc, uint32_t light, ui
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_trace_batch(hipStream_t st, int grid, const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out,
-                           uint8_t* occ, int any_hit, uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
-    if (sc.n_instances) hipLaunchKernelGGL(k_trace_batch_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
+                           uint8_t* occ, int any_hit, uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err, int alpha) {
+    if (alpha) hipLaunchKernelGGL(k_trace_batch_alpha, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
+    else if (sc.n_instances) hipLaunchKernelGGL(k_trace_batch_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
     else if (sc.n_spheres) hipLaunchKernelGGL(k_trace_batch_sph, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
     else hipLaunchKernelGGL(k_trace_batch, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
     return PT_LAUNCH_CHECK();

@@ -213,6 +213,7 @@ class SceneDesc:
     def __init__(self):
         self.desc = capi.pt_scene_desc()
         self.buffers = {}
+        self.alpha_masks = []       # capi.pt_alpha_mask, one per masked mesh (uploaded beside the descriptor, like infinite_lights)
 
     def _set(self, name, arr, ctype):
         self.buffers[name] = arr
@@ -234,6 +235,7 @@ class SceneBuilder:
         self.textures = []
         self.images = []            # (pt_image, texel buffer)
         self.infinite_lights = []   # capi.pt_infinite_light, in directive order
+        self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
         self.instances = []
         self.objects = {}           # name -> object index
         self.cur_object = 0         # 0 = world, k = inside ObjectBegin of object k - 1
@@ -563,7 +565,9 @@ class SceneBuilder:
         self.cur_area_light = -1
 
     # ---- shapes
-    def shape_trianglemesh(self, P, indices, N=None, S=None, uv=None, twosided=True, object_to_world=None):
+    def shape_trianglemesh(self, P, indices, N=None, S=None, uv=None, twosided=True, object_to_world=None, alpha=None, shadowalpha=None):
+        """alpha / shadowalpha: "float alpha" (a number) or "texture alpha" (a float Tex) -- an AlphaMaskShape around every triangle
+        (shapes/alphamask.rs); None = not given."""
         P = np.asarray(P, np.float32).reshape(-1, 3)
         idx = np.asarray(indices, np.int64).reshape(-1, 3)
         nv = len(P)
@@ -586,9 +590,17 @@ class SceneBuilder:
                         UV[v] = tri_uv[j]
         else:
             UV = None
-        return self._append_mesh(P, idx, N, S, UV, twosided, swaps)
+        return self._append_mesh(P, idx, N, S, UV, twosided, swaps, alpha, shadowalpha)
 
-    def _append_mesh(self, P, idx, N, S, UV, twosided, swaps):
+    @staticmethod
+    def _alpha_param(v):
+        if v is None:
+            return capi.PT_ALPHA_NONE, 0.0, -1
+        if isinstance(v, Tex):
+            return capi.PT_ALPHA_TEXTURE, 0.0, v.index
+        return capi.PT_ALPHA_CONSTANT, float(v), -1
+
+    def _append_mesh(self, P, idx, N, S, UV, twosided, swaps, alpha=None, shadowalpha=None):
         nv = len(P)
         keep = _tri_areas(P, idx) > f32(1e-16)      # triangle.rs:726
         idx = idx[keep]
@@ -615,11 +627,18 @@ class SceneBuilder:
         self.idx.append((idx + self.n_vertices).astype(np.uint32))
         self.tri_mesh.append(np.full(len(idx), mid, np.uint32))
         self.n_vertices += nv
+        if alpha is not None or shadowalpha is not None:
+            am = capi.pt_alpha_mask()
+            am.mesh = mid
+            am.alpha_kind, am.alpha_value, am.alpha_texture = self._alpha_param(alpha)
+            am.shadow_kind, am.shadow_value, am.shadow_texture = self._alpha_param(shadowalpha)
+            self.alpha_masks.append(am)
         return mid
 
-    def shape_sphere(self, radius=1.0, zmin=None, zmax=None, phimax=360.0, object_to_world=None, world_to_object=None):
+    def shape_sphere(self, radius=1.0, zmin=None, zmax=None, phimax=360.0, object_to_world=None, world_to_object=None, alpha=None, shadowalpha=None):
         """Shape "sphere" (shapes/sphere.rs:401-420) under the given CTM (m and m_inv, row-major; identity by
-        default).  A translate/scale/rotate product and its inverse are built by `transform_*` below."""
+        default).  A translate/scale/rotate product and its inverse are built by `transform_*` below.  alpha / shadowalpha are
+        accepted and ignored: create_sphere_shape never reads them."""
         sp = capi.pt_sphere()
         m = np.eye(4, dtype=np.float32).reshape(-1) if object_to_world is None else np.asarray(object_to_world, np.float32).reshape(-1)
         if world_to_object is None:
@@ -667,14 +686,14 @@ class SceneBuilder:
         self.n_extra += 1
         self.instances.append(it)
 
-    def shape_trianglemesh_fast(self, P, indices, twosided=True):
+    def shape_trianglemesh_fast(self, P, indices, twosided=True, alpha=None, shadowalpha=None):
         """Bulk path for meshes whose triangles do not share vertices (indices == arange):
         identical result to shape_trianglemesh (uv fill = (0,0),(1,0),(1,1) per triangle)."""
         P = np.asarray(P, np.float32).reshape(-1, 3)
         idx = np.asarray(indices, np.int64).reshape(-1, 3)
         assert np.array_equal(idx.reshape(-1), np.arange(len(P)))
         UV = np.tile(np.array([[0, 0], [1, 0], [1, 1]], np.float32), (len(idx), 1))
-        return self._append_mesh(P, idx, None, None, UV, twosided, False)
+        return self._append_mesh(P, idx, None, None, UV, twosided, False, alpha, shadowalpha)
 
     # ---- finish
     def build(self):
@@ -723,6 +742,7 @@ class SceneBuilder:
             sd.buffers["spheres"] = sph
             d.n_spheres, d.spheres = len(self.spheres), sph
         sd.infinite_lights = list(self.infinite_lights)
+        sd.alpha_masks = list(self.alpha_masks)
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
         d.camera_to_world[:] = [float(v) for v in self.camera_to_world]
         d.fov = self.fov
