@@ -9,7 +9,8 @@
  *                                           src/core/api/scene_context/scene_context.rs:817-1396
  * for the subset of the format the accelerated path renders:
  *   shapes      "trianglemesh", "plymesh" (ASCII / binary / gzip PLY), "sphere" (full or clipped by zmin / zmax /
- *               phimax, under any affine CTM; as a scene object or as an area light)
+ *               phimax, under any affine CTM; as a scene object or as an area light); "loopsubdiv", "nurbs" and
+ *               "heightfield", tessellated on the host into triangle meshes as the reference does
  *   materials   matte, plastic, mirror, glass, metal, uber, substrate with constant parameters; named
  *               materials; colours as rgb, .spd "spectrum" files or "blackbody" (metal defaults to the
  *               measured copper spectrum); Texture "constant" / "scale" / "mix" (folded when constant), "checkerboard"
@@ -75,6 +76,35 @@ pt_status pth_parse_to_log(const char* text, const char* work_dir, char* out, si
  * (src/core/spectrum/blackbody.rs:3-22; zero for t <= 0).  Exported so that the reference's own known-answer test
  * (tests/spectrum.rs:10-40) runs against this restatement. */
 void pth_blackbody(const double* lambda_nm, int n, double t_kelvin, double* out);
+
+/* ---- tessellated shapes: "loopsubdiv" (shapes/loopsubdiv.rs), "nurbs" (shapes/nurbs.rs), "heightfield" (shapes/heightfield.rs).
+ * Each returns the object-space arrays the reference hands to create_triangle_mesh (triangle.rs:696-731), in its vertex and face
+ * order; the front end runs the same code for the Shape directives.  On failure the status is PT_ERR_INVALID_ARGUMENT, err receives
+ * a message that names the shape and *out is zeroed.  Free a result with pth_tess_mesh_free. */
+typedef struct {
+    uint32_t n_vertices, n_triangles;
+    float* P;                   /* 3 * n_vertices */
+    float* N;                   /* 3 * n_vertices, or NULL (heightfield) */
+    float* uv;                  /* 2 * n_vertices, or NULL (loopsubdiv) */
+    uint32_t* indices;          /* 3 * n_triangles */
+} pth_tess_mesh;
+/* indices / P: NULL = the parameter is missing; n_p counts floats.  levels: "levels", else "nlevels", else 3 (the caller's choice). */
+pt_status pth_tessellate_loopsubdiv(const int32_t* indices, size_t n_indices, const float* P, size_t n_p, int32_t levels,
+                                    pth_tess_mesh* out, char* err, size_t err_cap);
+typedef struct {
+    int32_t nu, nv, uorder, vorder;     /* -1 = missing */
+    const float* uknots; size_t n_uknots;
+    const float* vknots; size_t n_vknots;
+    const float* P; size_t n_p;         /* floats: 3 per control point, or 4 (x, y, z, w) when homogeneous ("Pw"); NULL = missing */
+    int32_t homogeneous;
+    int32_t range_given;                /* bit 0: u0, bit 1: u1, bit 2: v0, bit 3: v1 given (else the knot range) */
+    float u0, u1, v0, v1;
+    int32_t diceu, dicev;               /* the reference's defaults are 30; values below 2 count as 2 */
+} pth_nurbs_params;
+pt_status pth_tessellate_nurbs(const pth_nurbs_params* params, pth_tess_mesh* out, char* err, size_t err_cap);
+/* Pz: NULL = missing. */
+pt_status pth_tessellate_heightfield(int32_t nu, int32_t nv, const float* Pz, size_t n_pz, pth_tess_mesh* out, char* err, size_t err_cap);
+void pth_tess_mesh_free(pth_tess_mesh* m);
 
 /* Linear-RGB float image as PFM (the smallest float format the reference can also write,
  * src/core/imageio/write_image.rs:59-76). */

@@ -227,7 +227,8 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks"]
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks",
+                "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
 class ParsedScene:
@@ -299,6 +300,98 @@ def parse_to_log(text, lib=None):
     if st != 0:
         raise PtError(st, out.value.decode())
     return out.value.decode().splitlines()
+
+
+class pth_tess_mesh(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("P", C.POINTER(C.c_float)), ("N", C.POINTER(C.c_float)),
+                ("uv", C.POINTER(C.c_float)), ("indices", C.POINTER(C.c_uint32))]
+
+
+class pth_nurbs_params(C.Structure):
+    _fields_ = [("nu", C.c_int32), ("nv", C.c_int32), ("uorder", C.c_int32), ("vorder", C.c_int32),
+                ("uknots", C.POINTER(C.c_float)), ("n_uknots", C.c_size_t), ("vknots", C.POINTER(C.c_float)), ("n_vknots", C.c_size_t),
+                ("P", C.POINTER(C.c_float)), ("n_p", C.c_size_t), ("homogeneous", C.c_int32), ("range_given", C.c_int32),
+                ("u0", C.c_float), ("u1", C.c_float), ("v0", C.c_float), ("v1", C.c_float), ("diceu", C.c_int32), ("dicev", C.c_int32)]
+
+
+def _f32_array(a):
+    """(contiguous float32 copy, ctypes pointer to it) -- or (None, None) for a missing parameter."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _tess_result(lib, st, m, err):
+    """Copy a pth_tess_mesh into numpy arrays (P, N, uv, indices; N / uv None when absent) and free it."""
+    if st != 0:
+        raise PtError(st, err.value.decode())
+    try:
+        nv, nt = m.n_vertices, m.n_triangles
+        P = np.ctypeslib.as_array(m.P, (nv, 3)).copy() if nv else np.zeros((0, 3), np.float32)
+        N = np.ctypeslib.as_array(m.N, (nv, 3)).copy() if m.N else None
+        uv = np.ctypeslib.as_array(m.uv, (nv, 2)).copy() if m.uv else None
+        idx = np.ctypeslib.as_array(m.indices, (nt, 3)).copy() if nt else np.zeros((0, 3), np.uint32)
+    finally:
+        lib.pth_tess_mesh_free(C.byref(m))
+    return {"P": P, "N": N, "uv": uv, "indices": idx}
+
+
+def _tess_lib(lib):
+    lib = lib or load_library()
+    lib.pth_tessellate_loopsubdiv.argtypes = [C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.c_int32,
+                                              C.POINTER(pth_tess_mesh), C.c_char_p, C.c_size_t]
+    lib.pth_tessellate_nurbs.argtypes = [C.POINTER(pth_nurbs_params), C.POINTER(pth_tess_mesh), C.c_char_p, C.c_size_t]
+    lib.pth_tessellate_heightfield.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_size_t, C.POINTER(pth_tess_mesh),
+                                               C.c_char_p, C.c_size_t]
+    lib.pth_tess_mesh_free.argtypes = [C.POINTER(pth_tess_mesh)]
+    lib.pth_tess_mesh_free.restype = None
+    return lib
+
+
+def tessellate_loopsubdiv(indices, P, levels=3, lib=None):
+    """Shape "loopsubdiv" (shapes/loopsubdiv.rs) in object space: {"P", "N", "uv": None, "indices"}.  indices / P = None: the
+    parameter is missing (the reference's errors).  Raises PtError on what the reference rejects or cannot handle."""
+    lib = _tess_lib(lib)
+    vi = None if indices is None else np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1).astype(np.int32))
+    pa, pp = _f32_array(P)
+    m, err = pth_tess_mesh(), C.create_string_buffer(1024)
+    st = lib.pth_tessellate_loopsubdiv(vi.ctypes.data_as(C.POINTER(C.c_int32)) if vi is not None else None, 0 if vi is None else len(vi),
+                                       pp, 0 if pa is None else len(pa), int(levels), C.byref(m), err, 1024)
+    return _tess_result(lib, st, m, err)
+
+
+def tessellate_nurbs(nu, nv, uorder, vorder, uknots, vknots, P=None, Pw=None, u0=None, u1=None, v0=None, v1=None, diceu=30, dicev=30, lib=None):
+    """Shape "nurbs" (shapes/nurbs.rs) in object space: {"P", "N", "uv", "indices"}.  P: 3 floats per control point; Pw: 4
+    (homogeneous), used when P is absent; u0 ... v1 = None: the knot range.  -1 / None for nu ... vknots = missing."""
+    lib = _tess_lib(lib)
+    prm = pth_nurbs_params()
+    prm.nu, prm.nv, prm.uorder, prm.vorder = int(nu), int(nv), int(uorder), int(vorder)
+    uk, prm.uknots = _f32_array(uknots)
+    vk, prm.vknots = _f32_array(vknots)
+    prm.n_uknots, prm.n_vknots = 0 if uk is None else len(uk), 0 if vk is None else len(vk)
+    cp, prm.homogeneous = (P, 0) if P is not None and len(np.asarray(P).reshape(-1)) else (Pw, 1 if Pw is not None else 0)
+    cpa, prm.P = _f32_array(cp)
+    prm.n_p = 0 if cpa is None else len(cpa)
+    given = 0
+    for bit, (name, val) in enumerate((("u0", u0), ("u1", u1), ("v0", v0), ("v1", v1))):
+        if val is not None:
+            given |= 1 << bit
+            setattr(prm, name, float(val))
+    prm.range_given = given
+    prm.diceu, prm.dicev = int(diceu), int(dicev)
+    m, err = pth_tess_mesh(), C.create_string_buffer(1024)
+    st = lib.pth_tessellate_nurbs(C.byref(prm), C.byref(m), err, 1024)
+    return _tess_result(lib, st, m, err)
+
+
+def tessellate_heightfield(nu, nv, Pz, lib=None):
+    """Shape "heightfield" (shapes/heightfield.rs) in object space: {"P", "N": None, "uv", "indices"}.  Pz = None: missing."""
+    lib = _tess_lib(lib)
+    za, zp = _f32_array(Pz)
+    m, err = pth_tess_mesh(), C.create_string_buffer(1024)
+    st = lib.pth_tessellate_heightfield(int(nu), int(nv), zp, 0 if za is None else len(za), C.byref(m), err, 1024)
+    return _tess_result(lib, st, m, err)
 
 
 def bvh_leaf_order(scene, lib=None):

@@ -141,7 +141,7 @@ struct Parser {
             else if (type == "bool") { std::vector<bool> bv; for (auto& s : strs) bv.push_back(s == "true"); ps.bools[name] = bv; }
             else if (type == "string") ps.strings[name] = strs;
             else if (type == "texture") ps.textures[name] = strs;
-            else if (type == "point" || type == "point3" || type == "point2") ps.points[name] = nums;
+            else if (type == "point" || type == "point3" || type == "point2" || type == "point4") ps.points[name] = nums;
             else if (type == "vector" || type == "vector3" || type == "vector2") ps.vectors[name] = nums;
             else if (type == "normal" || type == "normal3") ps.normals[name] = nums;
             else if (type == "rgb" || type == "color") ps.rgbs[name] = nums;

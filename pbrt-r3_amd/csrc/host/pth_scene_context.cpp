@@ -3,7 +3,7 @@
 // reference's SceneContext does between the parser callbacks and Integrator::render:
 //   transform / attribute stacks, named coordinate systems   scene_context.rs:821-943, :1037-1082
 //   options (Film, Camera, Sampler, ...) + WorldEnd factories  scene_context.rs:953-1016, :606-729
-//   pbrt_shape for "trianglemesh"                              scene_context.rs:1201-1318,
+//   pbrt_shape for "trianglemesh" (and the tessellated shapes) scene_context.rs:1201-1318,
 //                                                             shapes/triangle.rs:696-868
 //   material lookup with per-shape overrides                   scene_context.rs:224-296, materials/matte.rs:56-61
 //   diffuse area lights                                        lights/diffuse.rs:165-194
@@ -25,6 +25,7 @@
 #include "pth_ply.h"
 #include "pth_texture_image.h"
 #include "pth_spectrum.h"
+#include "pth_tessellate.h"
 
 namespace pth {
 
@@ -679,7 +680,10 @@ public:
 
     void pbrt_shape(const std::string& name, const ParamSet& p) override {
         if (!error.empty()) return;
-        if (name != "trianglemesh" && name != "plymesh" && name != "sphere") { fail("Shape \"" + name + "\": only trianglemesh, plymesh and sphere are on the accelerated path"); return; }
+        if (name != "trianglemesh" && name != "plymesh" && name != "sphere" && name != "loopsubdiv" && name != "nurbs" && name != "heightfield") {
+            fail("Shape \"" + name + "\": only trianglemesh, plymesh, sphere, loopsubdiv, nurbs and heightfield are on the accelerated path");
+            return;
+        }
         const TransformSet& ts = transforms.back();
         if (std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) != 0) { fail("animated transforms are outside the accelerated path"); return; }
         if (name == "sphere") {                                     // create_sphere_shape (shapes/sphere.rs:401-420); "alpha" / "shadowalpha" are not read there
@@ -706,6 +710,7 @@ public:
             spheres.push_back(sp);
             return;
         }
+        if (name == "loopsubdiv" || name == "nurbs" || name == "heightfield") { tessellated_shape(name, p); return; }
         if (name == "plymesh") {                                    // shapes/plymesh.rs:251-380
             std::string file = p.find_one_string("filename", "");
             if (!file.empty() && file[0] != '/' && !p.base_dir.empty()) file = p.base_dir + "/" + file;
@@ -745,6 +750,45 @@ public:
         emit_mesh(p, idx, *ps, nn, sv, uv);
     }
 
+    // create_loop_subdiv / create_nurbs / create_heightfield (host/pth_tessellate.cpp), then create_triangle_mesh.  loopsubdiv passes its
+    // own parameters on ("twosided" read there, default true); nurbs and heightfield pass an empty ParamSet, so they are always
+    // two-sided.  None of them reads "alpha" / "shadowalpha", and none gets the uv fill of create_triangle_mesh_shape.
+    void tessellated_shape(const std::string& name, const ParamSet& p) {
+        TessMesh m;
+        std::string terr;
+        bool ok;
+        if (name == "loopsubdiv") {
+            const int levels = p.find_one_int("levels", p.find_one_int("nlevels", 3));
+            ok = tessellate_loopsubdiv(p.get_ints("indices"), any_points(p, "P"), levels, &m, &terr);
+        } else if (name == "nurbs") {
+            NurbsInput in;
+            in.nu = p.find_one_int("nu", -1); in.nv = p.find_one_int("nv", -1);
+            in.uorder = p.find_one_int("uorder", -1); in.vorder = p.find_one_int("vorder", -1);
+            if (const std::vector<float>* k = p.get_floats("uknots")) in.uknots = *k;
+            if (const std::vector<float>* k = p.get_floats("vknots")) in.vknots = *k;
+            const std::vector<float>* cp = any_points(p, "P");              // get_points("P"), else get_points("Pw"); empty = missing
+            if (cp && !cp->empty()) { in.P = *cp; in.have_p = true; }
+            else if ((cp = any_points(p, "Pw")) && !cp->empty()) { in.P = *cp; in.have_p = true; in.homogeneous = true; }
+            auto range = [&](const char* k, bool* have, float* v) { const std::vector<float>* f = p.get_floats(k); if (f && f->size() == 1) { *have = true; *v = (*f)[0]; } };
+            range("u0", &in.have_u0, &in.u0); range("u1", &in.have_u1, &in.u1);
+            range("v0", &in.have_v0, &in.v0); range("v1", &in.have_v1, &in.v1);
+            in.diceu = p.find_one_int("diceu", 30); in.dicev = p.find_one_int("dicev", 30);
+            ok = tessellate_nurbs(in, &m, &terr);
+        } else {
+            ok = tessellate_heightfield(p.find_one_int("nu", -1), p.find_one_int("nv", -1), p.get_floats("Pz"), &m, &terr);
+        }
+        if (!ok) { fail("Shape \"" + name + "\": " + terr); return; }
+        if (m.indices.empty()) { warn("Shape \"" + name + "\": no triangles"); return; }
+        emit_mesh(p, m.indices, m.P, m.N.empty() ? nullptr : &m.N, nullptr, m.UV, name == "loopsubdiv" ? p.find_one_bool("twosided", true) : true, false);
+    }
+    // the reference's ParamSet keeps point*, vector* and normal values in one table (param_set.rs:188-191)
+    static const std::vector<float>* any_points(const ParamSet& p, const char* n) {
+        const std::vector<float>* v = p.get_points(n);
+        if (!v) v = p.get_vectors(n);
+        if (!v) v = p.get_normals(n);
+        return v;
+    }
+
     // get_alpha_texture / get_shadow_alpha_texture (triangle.rs:654-694), shape parameters only: "texture <n>" first -- a name that is no
     // float texture gives no mask, even beside a "float <n>" --, else "float <n>".  A named texture that folded to a constant is a
     // ConstantTexture there: the same value at every hit, so a constant mask here.
@@ -763,8 +807,13 @@ public:
         if (f != p.floats.end() && !f->second.empty()) { *kind = PT_ALPHA_CONSTANT; *value = f->second[0]; }
     }
     // create_triangle_mesh (triangle.rs:696-731) on object-space arrays: pre-transform, flags, material / light, degenerate filter
+    // (two_sided: create_triangle_mesh's "twosided"; alpha: whether the caller wraps the triangles in AlphaMaskShape)
     void emit_mesh(const ParamSet& p, const std::vector<uint32_t>& idx, const std::vector<float>& obj_p, const std::vector<float>* nn,
                    const std::vector<float>* sv, const std::vector<float>& uv) {
+        emit_mesh(p, idx, obj_p, nn, sv, uv, p.find_one_bool("twosided", true), true);
+    }
+    void emit_mesh(const ParamSet& p, const std::vector<uint32_t>& idx, const std::vector<float>& obj_p, const std::vector<float>* nn,
+                   const std::vector<float>* sv, const std::vector<float>& uv, bool two_sided, bool alpha) {
         const TransformSet& ts = transforms.back();
         const std::vector<float>* ps = &obj_p;
         size_t nv = obj_p.size() / 3;
@@ -781,7 +830,7 @@ public:
 
         pt_mesh mesh;
         mesh.flags = 0;
-        if (p.find_one_bool("twosided", true)) mesh.flags |= PT_MESH_TWO_SIDED;
+        if (two_sided) mesh.flags |= PT_MESH_TWO_SIDED;
         if (gstates.back().reverse_orientation) mesh.flags |= PT_MESH_REVERSE_ORIENTATION;
         if (swaps_handedness(o2w.m)) mesh.flags |= PT_MESH_SWAPS_HANDEDNESS;
         if (nn) mesh.flags |= PT_MESH_HAS_N;
@@ -807,7 +856,7 @@ public:
         }
         if (mesh.area_light >= 0) n_world_lights += (uint32_t)kept;
         meshes.push_back(mesh);
-        {   // AlphaMaskShape around every triangle of the mesh (triangle.rs:852-863, plymesh.rs:365-376)
+        if (alpha) {   // AlphaMaskShape around every triangle of the mesh (triangle.rs:852-863, plymesh.rs:365-376)
             pt_alpha_mask am;
             std::memset(&am, 0, sizeof(am));
             am.mesh = mesh_id;

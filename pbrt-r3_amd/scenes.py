@@ -136,6 +136,13 @@ def _transform_points(m, P):
     return out
 
 
+def _transform_normals(minv, N):
+    """Transform::transform_normal: the transpose of the stored inverse, f32, left to right."""
+    m = np.asarray(minv, np.float32)
+    x, y, z = N[:, 0], N[:, 1], N[:, 2]
+    return np.stack([(m[0] * x + m[4] * y) + m[8] * z, (m[1] * x + m[5] * y) + m[9] * z, (m[2] * x + m[6] * y) + m[10] * z], 1).astype(np.float32)
+
+
 def transform_translate(x, y, z):
     """Transform::translate (transform.rs:33-37): (m, m_inv) row-major."""
     m, mi = np.eye(4, dtype=np.float32), np.eye(4, dtype=np.float32)
@@ -685,6 +692,38 @@ class SceneBuilder:
         it.order = self.n_extra
         self.n_extra += 1
         self.instances.append(it)
+
+    # ---- tessellated shapes: the front end's tessellators (capi.tessellate_*), then create_triangle_mesh (triangle.rs:696-731).  No uv
+    # fill and no alpha masks (create_triangle_mesh reads neither); nurbs and heightfield are always two-sided (they pass it an empty
+    # ParamSet).  object_to_world / world_to_object: the CTM and its stored inverse (row-major; transform_* above), which carries N.
+    def _append_tessellated(self, t, twosided, object_to_world, world_to_object):
+        P, N, idx = t["P"], t["N"], t["indices"].astype(np.int64)
+        swaps = False
+        if object_to_world is not None:
+            m = np.asarray(object_to_world, np.float32).reshape(-1)
+            P = _transform_points(m, P)
+            swaps = _swaps_handedness(m)
+            if N is not None:
+                if world_to_object is None:
+                    raise ValueError("a transformed shape with normals needs world_to_object")
+                N = _transform_normals(np.asarray(world_to_object, np.float32).reshape(-1), N)
+        return self._append_mesh(P, idx, N, None, t["uv"], twosided, swaps)
+
+    def shape_loopsubdiv(self, P, indices, levels=3, twosided=True, object_to_world=None, world_to_object=None):
+        """Shape "loopsubdiv" (shapes/loopsubdiv.rs): "levels" (the front end falls back to "nlevels", then 3); limit normals, no uv."""
+        t = capi.tessellate_loopsubdiv(indices, P, levels)
+        return self._append_tessellated(t, twosided, object_to_world, world_to_object)
+
+    def shape_nurbs(self, nu, nv, uorder, vorder, uknots, vknots, P=None, Pw=None, u0=None, u1=None, v0=None, v1=None, diceu=30, dicev=30,
+                    object_to_world=None, world_to_object=None):
+        """Shape "nurbs" (shapes/nurbs.rs): a diceu x dicev grid with N = normalize(dpdu x dpdv) (NaN where that vanishes) and uv = (u, v)."""
+        t = capi.tessellate_nurbs(nu, nv, uorder, vorder, uknots, vknots, P=P, Pw=Pw, u0=u0, u1=u1, v0=v0, v1=v1, diceu=diceu, dicev=dicev)
+        return self._append_tessellated(t, True, object_to_world, world_to_object)
+
+    def shape_heightfield(self, nu, nv, Pz, object_to_world=None, world_to_object=None):
+        """Shape "heightfield" (shapes/heightfield.rs): the unit square at heights Pz, uv = (x, y)."""
+        t = capi.tessellate_heightfield(nu, nv, Pz)
+        return self._append_tessellated(t, True, object_to_world, world_to_object)
 
     def shape_trianglemesh_fast(self, P, indices, twosided=True, alpha=None, shadowalpha=None):
         """Bulk path for meshes whose triangles do not share vertices (indices == arange):
