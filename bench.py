@@ -25,6 +25,11 @@ roofline         = the traversal kernel (k_trace).  Primary bound: the request r
 cpu_baseline     = the CPU oracle (C++ restatement of the reference; the Rust binary cannot
                    be built in this image) rendering a bounded sample of the same workload on
                    the host cores of rank 0.
+
+A plain run does only what the headline needs: scene, one upload, the warm-up and timed steps, --dump-outputs, the
+line (`roofline` and `per_rank` come from the timed steps' own counters).  --full adds what takes time of its own:
+the re-upload of the scene (`bvh_build_ms`, `upload_ms`), `cpu_baseline` and the oracle's `parity` on the benchmarked
+frame, the `spp1024` frame, and at N > 1 the check of the reduced film; without it those fields are null.
 """
 import argparse
 import importlib
@@ -101,9 +106,11 @@ def main():
     ap.add_argument("--integrator", default="path", choices=["path", "ao", "directlighting", "whitted"],
                     help="path = the headline; ao = Integrator \"ao\" with 64 occlusion rays per camera sample; directlighting / whitted = the recursive integrators (secondary numbers)")
     ap.add_argument("--instances", type=int, default=0, help="secondary number: the filler triangles as ONE object instanced this many times (k_trace_inst, k_shade_general_inst*)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-spp1024", action="store_true", help="skip the secondary 1024-spp frame (N=1 only)")
-    ap.add_argument("--cpu-tiles", type=int, default=0, help="tiles in the CPU sample (0 = auto, about 15 s)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the scene's re-upload, the CPU baseline and the oracle's parity, the 1024-spp "
+                    "frame (N=1), the reduced-film check (N>1).  Off: those fields of the line are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle's parity")
+    ap.add_argument("--no-spp1024", action="store_true", help="with --full: skip the secondary 1024-spp frame (N=1 only)")
+    ap.add_argument("--cpu-tiles", type=int, default=0, help="with --full: tiles in the CPU sample (0 = auto, about 15 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the film of the last timed step (film_xyzw, film_rgb: what Context.film_xyzw() / film_rgb() "
                          "return; at N > 1 the reduced film) as DIR/<name>.npy in float32; over %d MB in all, a fixed, seeded sample of pixels and their "
@@ -177,10 +184,12 @@ def main():
     ctx = pkg.Context(local_rank)
     info = ctx.upload(sd)
     first_build_ms, first_upload_ms = info.bvh_build_ms, info.upload_ms
-    info = ctx.upload(sd)            # the same scene again: the context's staging buffers exist now (what a rebuild of a changed scene costs)
-    rebuild_ms, reupload_ms = info.bvh_build_ms, info.upload_ms
-    info = ctx.upload(sd)            # ... twice, the faster one reported (host threads: the first rebuild still grows a few buffers)
-    rebuild_ms, reupload_ms = min(rebuild_ms, info.bvh_build_ms), min(reupload_ms, info.upload_ms)
+    rebuild_ms, reupload_ms = None, None
+    if args.full:
+        info = ctx.upload(sd)            # the same scene again: the context's staging buffers exist now (what a rebuild of a changed scene costs)
+        rebuild_ms, reupload_ms = info.bvh_build_ms, info.upload_ms
+        info = ctx.upload(sd)            # ... twice, the faster one reported (host threads: the first rebuild still grows a few buffers)
+        rebuild_ms, reupload_ms = min(rebuild_ms, info.bvh_build_ms), min(reupload_ms, info.upload_ms)
     tiles = pkg.scenes.all_tiles(info)
     my_tiles = tiles[rank::world]
 
@@ -275,7 +284,7 @@ def main():
         log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, dump_outputs(ctx, args.dump_outputs)))
 
     film_check = None
-    if use_dist and world > 1 and os.environ.get("BENCH_CHECK_FILM") != "0":      # a scaling line vouches for its own film (every rank holds the sum)
+    if args.full and use_dist and world > 1 and os.environ.get("BENCH_CHECK_FILM") != "0":      # a full scaling line vouches for its own film (every rank holds the sum)
         film_check = check_reduced_film()
         flag = torch.tensor([1.0 if film_check["ok"] else 0.0], dtype=torch.float64, device="cpu" if rehearse else "cuda")
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
@@ -406,7 +415,7 @@ def main():
             log("parity: rel-L2 %.3e over %d pixels" % (out_["rel_l2"], out_["n_pixels"]))
             return out_
 
-        if not args.no_cpu_baseline and world > 1:
+        if args.full and not args.no_cpu_baseline and world > 1:
             # N > 1: no CPU timing leg (the other ranks would wait for it), but the line still vouches for its film -- the oracle renders four
             # of RANK 0's tiles and four of the LAST rank's, and the reduced film must match on both
             import oracle_lib
@@ -417,7 +426,7 @@ def main():
             parity = film_parity(osc, oxyzw, sample, "oracle (CPU restatement) on 4 tiles of rank 0 and 4 of rank %d against the REDUCED film, interior pixels, all %d spp (%.1f s)"
                                  % (world - 1, info.spp, secs))
             osc.close()
-        if not args.no_cpu_baseline and world == 1:      # the CPU timing leg runs at N=1 only (rank 0 would keep the other ranks waiting)
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU timing leg runs at N=1 only (rank 0 would keep the other ranks waiting)
             import oracle_lib
             osc = oracle_lib.load().scene(sd)
             cores = min(effective_cores(), 16)      # a 1-GPU box grants 16 host CPUs; BENCH_CPU_THREADS overrides the probe
@@ -466,7 +475,7 @@ def main():
             if native is not None:
                 tsc.close()
             osc.close()
-        if world == 1 and not args.no_spp1024 and args.spp != 1024:
+        if args.full and world == 1 and not args.no_spp1024 and args.spp != 1024:
             # north_star's target sentence quotes 1024 spp for the same scene (BASELINE config 2 says 256; Mrays/s is spp-independent,
             # wall-clock scales): one extra frame at 1024 spp, wall-clock reported beside the headline
             sd4 = pkg.scenes.rt1m(args.triangles, res=args.res, spp=1024, max_depth=args.max_depth, s=args.tri_size, materials=args.materials, sampler=args.sampler, light=args.light, instances=args.instances)
@@ -494,7 +503,8 @@ def main():
                                       " + a sphere area light" if args.light == "sphere" else "", "" if args.tri_size == 0.005 else " of half-extent %g" % args.tri_size, args.res, args.res, "Sobol" if args.sampler == "sobol" else "Halton", info.spp, args.max_depth),
                        "partition": "16x16 film tiles round-robin over %d rank(s), RCCL all-reduce of the XYZW film" % world,
                        "rays_per_step": int(rays / max(1, args.steps)), "camera_samples_per_step": int(tot[8] / max(1, args.steps)),
-                       "bvh_build_ms": round(rebuild_ms, 1), "upload_ms": round(reupload_ms, 1),
+                       "bvh_build_ms": round(rebuild_ms, 1) if rebuild_ms is not None else None,
+                       "upload_ms": round(reupload_ms, 1) if reupload_ms is not None else None,
                        "bvh_build_first_upload_ms": round(first_build_ms, 1), "first_upload_ms": round(first_upload_ms, 1),
                        "scene_gen_s": round(t_scene, 2), "workload_key": key},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "spp1024": spp1024,

@@ -145,11 +145,11 @@ def _bench_line(args, env_extra, timeout=600):
 
 def test_bench_rehearsal_four_ranks_on_one_gpu():
     """bench.py's N > 1 flow end to end, four ranks on this one GPU (BENCH_REHEARSE=gloo: RCCL refuses two ranks on one device, so the film sum
-    goes through the host; never a judged number).  The line must vouch for itself: one per_rank entry per rank, the ranks' tiles add up to the
+    goes through the host; never a judged number).  With --full the line must vouch for itself: one per_rank entry per rank, the ranks' tiles add up to the
     frame's, the reduced film holds every camera sample exactly once on every rank, and the oracle agrees with the REDUCED film on tiles of the
     first and of the last rank.  (Four ranks, not eight: a GPU box allows six processes on its card, this test process included; the
     eight-rank deal runs as threads of one process in test_cpp_driver_two_ranks_on_one_device.)"""
-    d = _bench_line(["--gpus", "4", "--triangles", "20000", "--res", "256", "--spp", "16", "--steps", "1", "--warmup", "1", "--no-spp1024"], {"BENCH_REHEARSE": "gloo"})
+    d = _bench_line(["--gpus", "4", "--triangles", "20000", "--res", "256", "--spp", "16", "--steps", "1", "--warmup", "1", "--no-spp1024", "--full"], {"BENCH_REHEARSE": "gloo"})
     assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["value"] > 0
     pr = d["per_rank"]
     assert [e["rank"] for e in pr] == [0, 1, 2, 3]
@@ -187,6 +187,27 @@ def test_bench_dump_outputs_is_the_rendered_film(gpu_ctx, tmp_path):
         assert np.allclose(got, want, rtol=2e-6, atol=1e-7)          # two renders: edge-split samples (float atomics) may differ in the last bits
         if name == "film_xyzw":
             assert np.array_equal(bits(got[..., 3]), bits(want[..., 3]))
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """A plain run (no --full) uploads once, warms up, times its steps and prints the line: what only --full measures or checks -- the
+    re-upload, the CPU leg, the oracle's parity, the 1024-spp frame -- is null in it."""
+    d = _bench_line(["--gpus", "1", "--triangles", "20000", "--res", "256", "--spp", "16", "--steps", "2", "--warmup", "1"], {})
+    assert d["metric"] == d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["roofline"]["launches"] > 0 and isinstance(d["config"]["first_upload_ms"], float)
+    assert d["cpu_baseline"] is None and d["parity"] is None and d["spp1024"] is None
+    assert d["config"]["bvh_build_ms"] is None and d["config"]["upload_ms"] is None
+
+
+def test_bench_full_line_at_one_gpu():
+    """bench.py --full at N = 1 still adds everything beside the headline: the rebuild timings, the CPU leg (the native oracle build, held
+    to the portable one before it is timed), the oracle's parity on the benchmarked frame and the 1024-spp frame."""
+    d = _bench_line(["--gpus", "1", "--triangles", "20000", "--res", "256", "--spp", "16", "--steps", "1", "--warmup", "1", "--full", "--cpu-tiles", "4"], {})
+    assert d["value"] > 0 and isinstance(d["config"]["bvh_build_ms"], float) and isinstance(d["config"]["upload_ms"], float)
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["sample"].startswith("4 of ")
+    assert d["parity"]["rel_l2"] <= 1e-3 and d["parity"]["n_pixels"] > 0
+    assert d["spp1024"]["spp"] == 1024 and d["spp1024"]["rays"] > 0
 
 
 def test_cpp_driver_eight_ranks_deal_the_full_frame(tmp_path):

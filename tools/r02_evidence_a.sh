@@ -17,7 +17,7 @@ for f in glob.glob(sys.argv[1] + "/calib/**/*counter_collection.csv", recursive=
         print("%-14s %s = %s" % (r["Kernel_Name"].split("(")[0], r["Counter_Name"], r["Counter_Value"]))
 PY
 echo "== bench (default flags)"
-timeout -k 10 600 python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
+timeout -k 10 600 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
 cut -c1-600 "$out/bench.json"
 echo "== rocprofv3 --kernel-trace --stats"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$out/prof" --output-format csv -- python3 bench.py --no-cpu-baseline --no-spp1024 > "$out/bench_under_rocprof.json" 2> "$out/bench_under_rocprof.err" || { echo "rocprof run failed"; tail -5 "$out/bench_under_rocprof.err"; exit 1; }

@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 if [ "$part" = a ]; then
   # counters first: the bench lines behind them then quote the traffic measured on this very source (bench.py checks the stamp)
   bash tools/pmc_traffic_workload.sh r04_default && cp gpurun_out/pmc_r04_default/traffic_entry.json "$out/traffic_entry_default.json" && cp gpurun_out/pmc_r04_default/summary.txt "$out/pmc_fetch_write_default.txt" && python3 tools/r04_stamp.py "$out/traffic_entry_default.json"
-  timeout -k 10 600 python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
   cut -c1-300 "$out/bench.json"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$out/prof" --output-format csv -- python3 bench.py --no-cpu-baseline --no-spp1024 > "$out/bench_under_rocprof.json" 2> "$out/bench_under_rocprof.err" || { echo "rocprof run failed"; tail -5 "$out/bench_under_rocprof.err"; exit 1; }
   find "$out/prof" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$out/kernel_stats.csv"
@@ -22,11 +22,11 @@ if [ "$part" = a ]; then
   head -8 "$out/kernel_stats.csv" | cut -c1-140
 elif [ "$part" = b ]; then
   PBRTGPU_TRACE_FAR=1 bash tools/pmc_traffic_workload.sh r04_16m_sparse --triangles 16000000 --tri-size 0.00125 && cp gpurun_out/pmc_r04_16m_sparse/traffic_entry.json "$out/traffic_entry_16m_sparse.json" && cp gpurun_out/pmc_r04_16m_sparse/summary.txt "$out/pmc_fetch_write_16m_sparse.txt" && python3 tools/r04_stamp.py "$out/traffic_entry_16m_sparse.json" "PBRTGPU_TRACE_FAR=1 for the whole frame (what the library's trial picks for this scene)"
-  timeout -k 10 600 python3 bench.py --triangles 3500000 --materials textured --spp 1024 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_crown_class.json" 2> "$out/bench_crown_class.err"
-  timeout -k 10 600 python3 bench.py --triangles 16000000 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_16m.json" 2> "$out/bench_16m.err"
-  timeout -k 10 600 python3 bench.py --triangles 16000000 --tri-size 0.00125 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_16m_sparse.json" 2> "$out/bench_16m_sparse.err"
-  timeout -k 10 600 python3 bench.py --materials mixed --light sphere --sampler halton --spp 512 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_killeroo_class.json" 2> "$out/bench_killeroo_class.err"
-  timeout -k 10 600 python3 bench.py --materials mixed --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_mixed.json" 2> "$out/bench_mixed.err"
+  timeout -k 10 600 python3 bench.py --full --triangles 3500000 --materials textured --spp 1024 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_crown_class.json" 2> "$out/bench_crown_class.err"
+  timeout -k 10 600 python3 bench.py --full --triangles 16000000 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_16m.json" 2> "$out/bench_16m.err"
+  timeout -k 10 600 python3 bench.py --full --triangles 16000000 --tri-size 0.00125 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_16m_sparse.json" 2> "$out/bench_16m_sparse.err"
+  timeout -k 10 600 python3 bench.py --full --materials mixed --light sphere --sampler halton --spp 512 --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_killeroo_class.json" 2> "$out/bench_killeroo_class.err"
+  timeout -k 10 600 python3 bench.py --full --materials mixed --steps 1 --warmup 1 --no-spp1024 --cpu-tiles 16 > "$out/bench_mixed.json" 2> "$out/bench_mixed.err"
   for f in crown_class 16m 16m_sparse killeroo_class mixed; do python3 -c "import json,sys; d=json.load(open('$out/bench_$f.json')); r=d['roofline']; print('%-14s %8.1f Mrays/s  alg frac %.3f | l1 %.3f hbm_measured %s | trace share %.3f shade %.3f | parity %.1e | upload %.1f+%.1f ms' % ('$f', d['value'], r['frac'], r['l1_req']['frac'], r['hbm_measured'] and r['hbm_measured']['frac'], r['trace_share_of_render'], r['shade_share_of_render'], d['parity']['rel_l2'], d['config']['bvh_build_ms'], d['config']['upload_ms']))"; done
   for v in "--integrator ao" "--sampler halton --spp 64" "--integrator directlighting --spp 64" "--integrator whitted --spp 64" "--light sphere --spp 64" "--materials textured --spp 64" "--integrator directlighting" "--integrator whitted"; do
     name=$(echo "$v" | tr -d '-' | tr ' ' '_')
@@ -36,7 +36,7 @@ elif [ "$part" = b ]; then
 elif [ "$part" = c ]; then
   timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q > "$out/pytest_gpu.txt" 2>&1; echo "pytest rc=$?"; tail -4 "$out/pytest_gpu.txt"
 else
-  BENCH_REHEARSE=gloo timeout -k 10 900 python3 bench.py --gpus 4 --steps 1 --warmup 1 > "$out/bench_rehearse_4ranks_one_gpu_gloo.json" 2> "$out/bench_rehearse_4ranks.err" || { echo "rehearsal failed"; tail -5 "$out/bench_rehearse_4ranks.err"; exit 1; }
+  BENCH_REHEARSE=gloo timeout -k 10 900 python3 bench.py --full --gpus 4 --steps 1 --warmup 1 > "$out/bench_rehearse_4ranks_one_gpu_gloo.json" 2> "$out/bench_rehearse_4ranks.err" || { echo "rehearsal failed"; tail -5 "$out/bench_rehearse_4ranks.err"; exit 1; }
   python3 -c "import json; d=json.load(open('$out/bench_rehearse_4ranks_one_gpu_gloo.json')); print('4 ranks on one GPU: %.1f Mrays/s, reduced_film_ok %s, parity %.1e, tiles %s' % (d['value'], d['reduced_film_ok'], d['parity']['rel_l2'], [e['tiles'] for e in d['per_rank']]))"
   exe=pbrt-r3_amd/csrc/pbrt_gpu
   sed 's/"integer xresolution" \[64\] "integer yresolution" \[64\]/"integer xresolution" [1024] "integer yresolution" [1024]/' tests/scenes/cornell.pbrt > "$out/cornell_1024.pbrt"; cp tests/scenes/cornell_blocks.pbrt "$out/"

@@ -17,7 +17,7 @@ W[direct]="--integrator directlighting"
 W[whitted]="--integrator whitted"
 W[head]=""
 for w in ${WORKLOADS:-killeroo crown mixed direct whitted}; do
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$out/prof_$w" --output-format csv -- python3 bench.py ${W[$w]} --spp ${SPP:-64} --steps 1 --warmup 1 --no-cpu-baseline --no-spp1024 > "$out/bench_$w.json" 2> "$out/bench_$w.err" || { echo "$w failed"; tail -5 "$out/bench_$w.err"; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$out/prof_$w" --output-format csv -- python3 bench.py --full ${W[$w]} --spp ${SPP:-64} --steps 1 --warmup 1 --no-cpu-baseline --no-spp1024 > "$out/bench_$w.json" 2> "$out/bench_$w.err" || { echo "$w failed"; tail -5 "$out/bench_$w.err"; exit 1; }
   find "$out/prof_$w" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$out/kernel_stats_$w.csv"; rm -rf "$out/prof_$w"
   python3 - "$out/bench_$w.json" "$out/kernel_stats_$w.csv" "$w" <<'PY'
 import csv, json, sys
