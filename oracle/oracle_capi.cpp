@@ -32,10 +32,12 @@ extern "C" {
 
 const char* orc_header(void) { return "oracle: CPU restatement of pbrt-r3 (test infrastructure, not the product)"; }
 
-// n infinite lights (pt_scene_set_infinite_lights' layout) with the scene; orc_scene_create is the call with none
-int orc_scene_create_env(const pt_scene_desc* d, const char* data_dir, uint32_t n, const pt_infinite_light* lights, orc_scene** out) {
+// n infinite lights (pt_scene_set_infinite_lights' layout) and n_masks alpha masks (pt_scene_set_alpha_masks' layout) with the scene;
+// orc_scene_create_env is the call without masks, orc_scene_create the call with neither
+int orc_scene_create_masked(const pt_scene_desc* d, const char* data_dir, uint32_t n, const pt_infinite_light* lights, uint32_t n_masks, const pt_alpha_mask* masks,
+                            orc_scene** out) {
     orc_scene* s = new orc_scene;
-    if (!s->sc.build(*d, data_dir, &s->err, n, lights)) {
+    if (!s->sc.build(*d, data_dir, &s->err, n, lights, n_masks, masks)) {
         std::fprintf(stderr, "orc_scene_create: %s\n", s->err.c_str());
         delete s;
         return 1;
@@ -43,6 +45,9 @@ int orc_scene_create_env(const pt_scene_desc* d, const char* data_dir, uint32_t 
     s->ld.init(&s->sc);
     *out = s;
     return 0;
+}
+int orc_scene_create_env(const pt_scene_desc* d, const char* data_dir, uint32_t n, const pt_infinite_light* lights, orc_scene** out) {
+    return orc_scene_create_masked(d, data_dir, n, lights, 0, nullptr, out);
 }
 int orc_scene_create(const pt_scene_desc* d, const char* data_dir, orc_scene** out) { return orc_scene_create_env(d, data_dir, 0, nullptr, out); }
 

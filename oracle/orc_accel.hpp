@@ -57,6 +57,14 @@ namespace orc {
 static const uint32_t PRIM_SPHERE = 0x80000000u;
 static const uint32_t PRIM_INSTANCE = 0x40000000u;
 struct QBVH;
+// AlphaMaskShape::new (shapes/alphamask.rs:19-62) for the triangles of one mesh: create_triangle_mesh_shape wraps every triangle when
+// "alpha" or "shadowalpha" is given (shapes/triangle.rs:852-862; a texture name or a float, :654-694).  A constant only ever switches
+// the tests off (<= 0); a texture is kept and evaluated at each candidate hit.
+struct AlphaMask {
+    bool wrapped = false;                                        // the mesh's triangles are AlphaMaskShapes
+    bool test_intersection = true, test_intersection_p = true;
+    int32_t alpha_texture = -1, shadow_texture = -1;             // index into the scene's textures, -1: none
+};
 // ObjectInstance -> TransformedPrimitive (core/primitive/transformed_primitive.rs) with a static transform
 struct Instance { Mat4 m, minv; uint32_t object = 0; };
 struct Geometry {
@@ -69,6 +77,10 @@ struct Geometry {
     std::vector<Instance> instances;
     std::vector<const QBVH*> object_bvh;     // per object: the accelerator over its primitives (owned by the Scene)
     std::vector<uint32_t> prim_ref;   // empty = triangles only, prim == triangle index
+    std::vector<AlphaMask> mesh_alpha;       // per mesh; empty: no mesh of the scene is masked
+    // Texture<Float>::evaluate(&si) of a mask texture: the texture code sits above this header, so the Scene that owns it installs the call
+    Float (*mask_eval)(const void* ctx, int32_t texture, const SurfHit& si) = nullptr;
+    const void* mask_ctx = nullptr;
     size_t n_tris() const { return idx.size() / 3; }
     size_t n_prims() const { return prim_ref.empty() ? n_tris() : prim_ref.size(); }
     uint32_t ref(size_t prim) const { return prim_ref.empty() ? (uint32_t)prim : prim_ref[prim]; }
@@ -291,19 +303,46 @@ struct TriRef {
     }
 };
 
+// A triangle as the scene holds it: bare, or inside an AlphaMaskShape (alphamask.rs:73-113).  The mask sees the interaction the triangle's
+// own intersect built, in the space the ray is in (an instance hands its object-space ray down, transformed_primitive.rs:26-45), and a
+// SurfaceInteraction carries no ray differentials at that point.  Triangle::intersect leaves r.t_max alone here (the caller sets it from
+// *t on a hit), so "r.t_max.set(t_max)" of :81 and :96 is a rejected candidate simply not reported.  area / sample / sample_from / pdf /
+// pdf_from of the wrapper go to the bare shape (:115-141): TriRef's own, which the lights keep calling.
+inline bool tri_shape_intersect(const Geometry* g, uint32_t tri, const Ray& r, Float* t, SurfHit* si) {
+    TriRef tr(g, tri);
+    if (g->mesh_alpha.empty() || !g->mesh_alpha[g->tri_mesh[tri]].wrapped) return tr.intersect(r, t, si);
+    const AlphaMask& am = g->mesh_alpha[g->tri_mesh[tri]];
+    if (!am.test_intersection) return false;                                                                // :74
+    if (!tr.intersect(r, t, si)) return false;                                                              // :77
+    if (am.alpha_texture >= 0 && g->mask_eval(g->mask_ctx, am.alpha_texture, *si) <= 0.0f) return false;    // :78-84
+    return true;
+}
+inline bool tri_shape_intersect_p(const Geometry* g, uint32_t tri, const Ray& r) {
+    TriRef tr(g, tri);
+    if (g->mesh_alpha.empty() || !g->mesh_alpha[g->tri_mesh[tri]].wrapped) return tr.intersect_p(r);
+    const AlphaMask& am = g->mesh_alpha[g->tri_mesh[tri]];
+    if (!am.test_intersection_p) return false;                                                              // :92
+    Float t;
+    SurfHit si;
+    if (!tr.intersect(r, &t, &si)) return false;                         // :95: the full intersect, so a triangle without dpdu / dpdv is a miss
+    if (am.alpha_texture >= 0 && g->mask_eval(g->mask_ctx, am.alpha_texture, si) <= 0.0f) return false;     // :97-102
+    if (am.shadow_texture >= 0 && g->mask_eval(g->mask_ctx, am.shadow_texture, si) <= 0.0f) return false;   // :103-108
+    return true;
+}
+
 // Primitive dispatch (the reference's Arc<dyn Primitive> -> GeometricPrimitive -> dyn Shape chain).
 bool instance_intersect(const Geometry* g, uint32_t inst, const Ray& r, Float* t, SurfHit* si, BvhStats* st);
 bool instance_intersect_p(const Geometry* g, uint32_t inst, const Ray& r, BvhStats* st);
 Bounds3 instance_world_bound(const Geometry* g, uint32_t inst);
 inline bool ref_intersect(const Geometry* g, uint32_t ref, const Ray& r, Float* t, SurfHit* si, BvhStats* st) {
     if (ref & PRIM_INSTANCE) return instance_intersect(g, ref & ~PRIM_INSTANCE, r, t, si, st);
-    bool hit = (ref & PRIM_SPHERE) ? g->spheres[ref & ~PRIM_SPHERE].intersect(r, t, si) : TriRef(g, ref).intersect(r, t, si);
+    bool hit = (ref & PRIM_SPHERE) ? g->spheres[ref & ~PRIM_SPHERE].intersect(r, t, si) : tri_shape_intersect(g, ref, r, t, si);
     if (hit) si->shape_ref = ref;
     return hit;
 }
 inline bool ref_intersect_p(const Geometry* g, uint32_t ref, const Ray& r, BvhStats* st) {
     if (ref & PRIM_INSTANCE) return instance_intersect_p(g, ref & ~PRIM_INSTANCE, r, st);
-    return (ref & PRIM_SPHERE) ? g->spheres[ref & ~PRIM_SPHERE].intersect_p(r) : TriRef(g, ref).intersect_p(r);
+    return (ref & PRIM_SPHERE) ? g->spheres[ref & ~PRIM_SPHERE].intersect_p(r) : tri_shape_intersect_p(g, ref, r);
 }
 inline Bounds3 ref_world_bound(const Geometry* g, uint32_t ref) {
     if (ref & PRIM_INSTANCE) return instance_world_bound(g, ref & ~PRIM_INSTANCE);

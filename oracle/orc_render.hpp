@@ -263,7 +263,8 @@ struct Scene {
     }
     Float rr_threshold = 1.0f;
 
-    bool build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env = 0, const pt_infinite_light* env = nullptr);
+    bool build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env = 0, const pt_infinite_light* env = nullptr,
+               uint32_t n_alpha = 0, const pt_alpha_mask* alpha = nullptr);
     // what every infinite light returns for a ray that leaves the scene, summed in list order (path.rs:86-98, directlighting.rs:117-129,
     // whitted.rs:96-105; an area light's le is zero)
     RGB env_le_all(V3 d) const {
@@ -1124,7 +1125,17 @@ inline void render(const Scene& sc, LightDistribution& ldist, const pt_tile* til
 }
 
 // ---- scene assembly from the flattened description
-inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env, const pt_infinite_light* env) {
+// Geometry::mask_eval: a mask texture at a candidate hit.  alphamask.rs:79 / :98 / :104 call Texture::evaluate on the interaction that
+// Triangle::intersect returned: compute_differentials has not run on it, so every footprint is zero -- the TexHit of a ray without
+// differentials (an image map then reads level 0 bilinearly, mipmap.rs:620-629; fbm takes its octaves from log2(0)).
+inline Float scene_mask_eval(const void* ctx, int32_t texture, const SurfHit& si) {
+    const Scene& sc = *(const Scene*)ctx;
+    TexHit th = compute_differentials(si, RayDiff());
+    return texture_eval(sc.textures.data(), texture, th, sc.images.data()).c[0];
+}
+
+inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, std::string* err, uint32_t n_env, const pt_infinite_light* env, uint32_t n_alpha,
+                         const pt_alpha_mask* alpha) {
     if (!sobol.load(data_dir + "/sobol_tables.bin")) { *err = "cannot load sobol_tables.bin from " + data_dir; return false; }
     geom.P.resize(d.n_vertices);
     for (uint32_t i = 0; i < d.n_vertices; i++) geom.P[i] = V3(d.P[3 * i], d.P[3 * i + 1], d.P[3 * i + 2]);
@@ -1158,6 +1169,29 @@ inline bool Scene::build(const pt_scene_desc& d, const std::string& data_dir, st
         const uint32_t refs[13] = {m.tex_kd, m.tex_ks, m.tex_kr, m.tex_kt, m.tex_opacity, m.tex_sigma, m.tex_metal_eta, m.tex_metal_k, m.tex_bump,
                                    m.tex_roughness, m.tex_uroughness, m.tex_vroughness, m.tex_eta};
         for (uint32_t r : refs) if (r > d.n_textures) { if (err) *err = "material texture index out of range"; return false; }
+    }
+    // "alpha" / "shadowalpha" of the meshes (pt_alpha_mask, the layout pt_scene_set_alpha_masks takes): AlphaMaskShape::new.  Spheres have
+    // no such parameters (quirk Q30) and the light list below is built from the bare shapes (Q37).
+    if (n_alpha) {
+        geom.mesh_alpha.assign(d.n_meshes, AlphaMask());
+        geom.mask_eval = &scene_mask_eval;
+        geom.mask_ctx = this;
+        for (uint32_t k = 0; k < n_alpha; k++) {
+            const pt_alpha_mask& a = alpha[k];
+            if (a.mesh >= d.n_meshes) { if (err) *err = "alpha mask: mesh index out of range"; return false; }
+            const int32_t kinds[2] = {a.alpha_kind, a.shadow_kind}, texs[2] = {a.alpha_texture, a.shadow_texture};
+            for (int j = 0; j < 2; j++) {
+                if (kinds[j] < PT_ALPHA_NONE || kinds[j] > PT_ALPHA_TEXTURE) { if (err) *err = "alpha mask: unknown kind"; return false; }
+                if (kinds[j] == PT_ALPHA_TEXTURE && (texs[j] < 0 || (uint32_t)texs[j] >= d.n_textures)) { if (err) *err = "alpha mask: texture index out of range"; return false; }
+            }
+            AlphaMask& m = geom.mesh_alpha[a.mesh];
+            m = AlphaMask();
+            m.wrapped = a.alpha_kind != PT_ALPHA_NONE || a.shadow_kind != PT_ALPHA_NONE;            // triangle.rs:854
+            if (a.alpha_kind == PT_ALPHA_TEXTURE) m.alpha_texture = a.alpha_texture;                // alphamask.rs:29-41
+            else if (a.alpha_kind == PT_ALPHA_CONSTANT && a.alpha_value <= 0.0f) { m.test_intersection = false; m.test_intersection_p = false; }
+            if (a.shadow_kind == PT_ALPHA_TEXTURE) m.shadow_texture = a.shadow_texture;             // :42-53
+            else if (a.shadow_kind == PT_ALPHA_CONSTANT && a.shadow_value <= 0.0f) m.test_intersection_p = false;
+        }
     }
     // spheres and object instances, spliced into the primitive lists at before_triangle (ties: creation order)
     geom.spheres.resize(d.n_spheres);

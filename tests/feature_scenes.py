@@ -776,3 +776,180 @@ def scene_env_golden():
     plastic quad, directlighting "all" with samples 3, Halton."""
     return scene_env("directlighting", "all", ("mirror", "glass", "plastic"), env_map="image", transform="rotated", order="before",
                      sampler="halton", nsamples=3, res=32, spp=4, depth=4)
+
+
+# ---- alpha masks that vary inside their triangles (shapes/alphamask.rs) for the device-against-oracle parity tests and the masked fixture
+ALPHA_MASKS = ("image16_repeat", "image16_black", "image64_clamp_trilinear", "checker_closedform", "checker_none", "bilerp", "scale", "mix",
+               "fbm", "wrinkled", "windy", "checker3d", "planar", "spherical", "cylindrical")
+
+
+def alpha_mask_texture(b, kind):
+    """A float texture that crosses zero inside the triangles it masks.  The names of alpha_mask_ref.cases() (uv-mapped image maps,
+    checkerboards, bilerp, scale, mix), the noise textures (their octave count comes from log2 of a zero footprint), a 3-D checkerboard,
+    and image / bilerp / checkerboard textures under the planar, spherical and cylindrical mappings."""
+    import alpha_mask_ref as am
+    T = scenes
+    tw = T.transform_mul(T.transform_translate(0.3, -0.2, 0.1), T.transform_mul(T.transform_rotate_x(35.0), T.transform_scale(0.8, 1.3, 0.6)))
+    if kind == "fbm":
+        return b.texture_fbm(octaves=6, roughness=0.6, to_world=tw)
+    if kind == "wrinkled":
+        return b.texture_mix(-0.4, 0.6, amount=b.texture_wrinkled(octaves=5, roughness=0.5))
+    if kind == "windy":
+        return b.texture_windy(to_world=tw)
+    if kind == "checker3d":
+        return b.texture_checkerboard(0.5, -0.5, dimension=3, to_world=T.transform_mul(T.transform_rotate_x(20.0), T.transform_scale(0.45, 0.6, 0.35)))
+    if kind == "planar":
+        return b.texture_imagemap(b.image_pyramid(am.noise_image(16)), wrap="repeat", mapping="planar", v1=(0.31, 0.1, -0.05), v2=(-0.08, 0.27, 0.12), udelta=0.2, vdelta=-0.1)
+    if kind == "spherical":
+        return b.texture_bilerp(-1.0, 0.8, 0.6, -0.7, mapping="spherical", to_world=T.transform_translate(4.0, 4.0, 0.0))
+    if kind == "cylindrical":
+        return b.texture_checkerboard(0.5, -0.5, mapping="cylindrical", to_world=T.transform_mul(T.transform_translate(4.0, 4.0, 0.0), T.transform_scale(8.0, 8.0, 0.7)))
+    return am.cases()[kind].tex(b)
+
+
+def _alpha_material(b, m):
+    if m == "matte":
+        b.material_matte((0.25, 0.6, 0.3))
+    elif m == "mirror":
+        b.material_mirror(Kr=(0.9, 0.9, 0.85))
+    elif m == "glass":
+        b.material_glass(Kr=(1.0, 1.0, 1.0), Kt=(1.0, 1.0, 1.0), eta=1.5)
+    else:
+        b.material_plastic(Kd=(0.3, 0.4, 0.5), Ks=(0.4, 0.4, 0.4), roughness=0.15)
+
+
+def leaf_quads(n=6, z=2.0, size=0.55, seed=9):
+    """n x n small tilted quads over [0.5, 7.5]^2, each carrying the whole [0, 1]^2 of its mask: P, indices, uv."""
+    rng = np.random.default_rng(seed)
+    P, idx, uv = [], [], []
+    for j in range(n):
+        for i in range(n):
+            c = np.array([0.5 + 7.0 * (i + 0.5) / n, 0.5 + 7.0 * (j + 0.5) / n, z]) + rng.uniform(-0.15, 0.15, 3)
+            ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+            u = np.cross(ax, [0.0, 0.0, 1.0]); u /= np.linalg.norm(u)
+            v = np.cross(ax, u) * 0.7 + np.array([0.0, 0.0, 0.3])
+            k = len(P)
+            P += [c - size * u - size * v, c + size * u - size * v, c + size * u + size * v, c - size * u + size * v]
+            uv += [(0, 0), (1, 0), (1, 1), (0, 1)]
+            idx += [k, k + 1, k + 2, k, k + 2, k + 3]
+    return np.array(P, np.float32), np.array(idx), np.array(uv, np.float32)
+
+
+def scene_alpha(integrator="path", strategy="spatial", on="matte", under="matte", sampler="sobol", extra=None, mask="image16_repeat", shadow=None,
+                emitter=None, split="sah", maxnodeprims=4, res=24, spp=4, depth=4):
+    """A room (floor, two walls, an emitter above) around a masked canopy -- one large quad whose mask varies across it, uv running past
+    [0, 1] -- and masked foliage above it: small tilted quads each carrying the whole mask.  on / under: the material of the masked
+    meshes and of the floor beneath them.  shadow: a second mask as "shadowalpha".  emitter: the mask of a masked area light
+    (sampled everywhere, seen only where it passes).  extra: "sphere", "instance" (the foliage as an object under a rotated, non-uniformly
+    scaled and mirrored instance: the masks see object space), "env"."""
+    T = scenes
+    b = scenes.SceneBuilder()
+    b.look_at((4, -3, 7), (4, 4, 0.5), (0, 0, 1))
+    b.camera_perspective(fov=60)
+    b.film(xresolution=res, yresolution=res)
+    b.pixel_filter_box()
+    (b.sampler_sobol if sampler == "sobol" else b.sampler_halton)(pixelsamples=spp)
+    if integrator == "path":
+        b.integrator_path(maxdepth=depth, lightsamplestrategy=strategy)
+    elif integrator == "directlighting":
+        b.integrator_directlighting(maxdepth=depth, strategy=strategy)
+    elif integrator == "whitted":
+        b.integrator_whitted(maxdepth=depth)
+    else:
+        b.integrator_ao(nsamples=4)
+    b.accelerator_bvh(splitmethod=split, maxnodeprims=maxnodeprims)
+    a_tex = alpha_mask_texture(b, mask)
+    kw = {"alpha": a_tex}
+    if shadow is not None:
+        kw["shadowalpha"] = alpha_mask_texture(b, shadow)
+    _alpha_material(b, under)
+    b.shape_trianglemesh([-1, -1, 0, 9, -1, 0, 9, 9, 0, -1, 9, 0], [0, 1, 2, 0, 2, 3])
+    b.material_matte(Kd=(0.5, 0.45, 0.4))
+    b.shape_trianglemesh([-1, 9, 0, 9, 9, 0, 9, 9, 4, -1, 9, 4], [0, 1, 2, 0, 2, 3])
+    b.shape_trianglemesh([9, -1, 0, 9, 9, 0, 9, 9, 4, 9, -1, 4], [0, 1, 2, 0, 2, 3])
+    if integrator != "ao":
+        b.area_light_source_diffuse(L=(6, 6, 5))
+        b.shape_trianglemesh([2, 2, 3.9, 6, 2, 3.9, 6, 6, 3.9, 2, 6, 3.9], [0, 2, 1, 0, 3, 2])
+        b.no_area_light()
+        if emitter is not None:
+            b.area_light_source_diffuse(L=(3, 2, 1), twosided=True, nsamples=2)
+            b.shape_trianglemesh([0.5, 7.5, 0.4, 3.5, 7.5, 0.4, 3.5, 8.2, 2.6, 0.5, 8.2, 2.6], [0, 1, 2, 0, 2, 3], uv=[(0, 0), (1, 0), (1, 1), (0, 1)],
+                                 alpha=alpha_mask_texture(b, emitter))
+            b.no_area_light()
+    _alpha_material(b, on)
+    b.shape_trianglemesh([0.5, 0.5, 1.2, 7.5, 0.5, 1.0, 7.5, 7.5, 1.2, 0.5, 7.5, 1.4], [0, 1, 2, 0, 2, 3], uv=[(-0.25, -0.25), (1.25, -0.25), (1.25, 1.25), (-0.25, 1.25)], **kw)
+    P, idx, uv = leaf_quads()
+    if extra == "instance":
+        m = T.transform_mul(T.transform_translate(4.0, 4.2, 2.1), T.transform_mul(T.transform_rotate_x(25.0), T.transform_scale(0.8, -1.1, 0.6)))
+        Po = (np.concatenate([P, np.ones((len(P), 1), np.float32)], 1) @ np.asarray(m[1], np.float64).reshape(4, 4).T)[:, :3].astype(np.float32)
+        b.object_begin("foliage")
+        b.shape_trianglemesh(Po, idx, uv=uv, **kw)
+        b.shape_trianglemesh(Po[:12] + np.float32([0.0, 0.0, 0.4]), idx[:18])            # unmasked triangles in the same object tree
+        b.object_end()
+        b.object_instance("foliage", m)
+    else:
+        b.shape_trianglemesh(P, idx, uv=uv, **kw)
+        b.shape_trianglemesh(P[:24] + np.float32([0.1, 0.1, 0.5]), idx[:36])                # a mesh without uv: the default (0,0), (1,0), (1,1)
+        b.shape_trianglemesh(P[24:48] + np.float32([0.1, 0.1, 0.5]), idx[:36], **kw)
+    if extra == "sphere":
+        _alpha_material(b, "glass" if on != "glass" else "matte")
+        t = T.transform_translate(6.5, 2.5, 2.0)
+        b.shape_sphere(radius=0.6, object_to_world=t[0], world_to_object=t[1])
+    if extra == "env":
+        b.light_infinite(L=(0.3, 0.35, 0.4))
+    return b.build()
+
+
+def scene_alpha_golden():
+    """The masked fixture (tools/make_golden.py): image-masked canopy and foliage with a checkerboard "shadowalpha", a masked emitter,
+    a mirror floor, path tracing with Halton."""
+    return scene_alpha("path", "spatial", on="plastic", under="mirror", sampler="halton", mask="image16_repeat", shadow="checker_closedform",
+                       emitter="bilerp", res=32, spp=4, depth=4)
+
+
+# The render matrix of tests/test_gpu_alpha_mask_parity.py: (integrator, strategy, on, under, sampler, extra, mask, shadowalpha, emitter).
+# The first five columns -- integrator with its strategy (7 values), the material on the masked meshes and the one under them (4 each),
+# sampler (2), extra (4) -- are pairwise: every pair of values of any two of them is in some row (28 rows, the least that 7 x 4 allows;
+# tests/test_alpha_mask_oracle.py::test_render_matrix_is_pairwise counts them).  The 15 mask kinds appear as "alpha" at least once each,
+# not paired with the other columns; "shadowalpha" and the masked emitter's mask (none under ao, which has no lights) vary freely.
+ALPHA_RENDERS = [
+    ("path", "uniform", "matte", "plastic", "sobol", None, "image16_repeat", None, "bilerp"),
+    ("path", "uniform", "mirror", "mirror", "halton", "sphere", "image16_black", "checker3d", None),
+    ("path", "uniform", "glass", "glass", "halton", "instance", "image64_clamp_trilinear", "image16_repeat", "wrinkled"),
+    ("path", "uniform", "plastic", "matte", "sobol", "env", "checker_closedform", None, "checker3d"),
+    ("path", "power", "matte", "glass", "sobol", None, "checker_none", "fbm", "spherical"),
+    ("path", "power", "mirror", "plastic", "halton", "sphere", "bilerp", "planar", None),
+    ("path", "power", "glass", "matte", "halton", "env", "scale", None, "image64_clamp_trilinear"),
+    ("path", "power", "plastic", "mirror", "halton", "instance", "mix", "bilerp", "checker_none"),
+    ("path", "spatial", "matte", "mirror", "halton", "env", "fbm", "wrinkled", "scale"),
+    ("path", "spatial", "mirror", "matte", "sobol", "instance", "wrinkled", None, None),
+    ("path", "spatial", "glass", "glass", "sobol", None, "windy", "image64_clamp_trilinear", "windy"),
+    ("path", "spatial", "plastic", "plastic", "halton", "sphere", "checker3d", "scale", "planar"),
+    ("directlighting", "all", "matte", "mirror", "sobol", "env", "planar", None, "cylindrical"),
+    ("directlighting", "all", "mirror", "glass", "halton", "sphere", "spherical", "cylindrical", None),
+    ("directlighting", "all", "glass", "plastic", "halton", None, "cylindrical", "checker_closedform", "checker_closedform"),
+    ("directlighting", "all", "plastic", "matte", "halton", "instance", "image16_repeat", None, "bilerp"),
+    ("directlighting", "one", "matte", "glass", "halton", "env", "image16_black", "checker3d", "mix"),
+    ("directlighting", "one", "mirror", "plastic", "halton", "instance", "image64_clamp_trilinear", "image16_repeat", None),
+    ("directlighting", "one", "glass", "mirror", "sobol", "sphere", "checker_closedform", None, "checker3d"),
+    ("directlighting", "one", "plastic", "matte", "halton", None, "checker_none", "fbm", "spherical"),
+    ("whitted", None, "matte", "matte", "sobol", "sphere", "bilerp", "planar", "image16_repeat"),
+    ("whitted", None, "mirror", "mirror", "halton", None, "scale", None, None),
+    ("whitted", None, "glass", "plastic", "halton", "instance", "mix", "bilerp", "checker_none"),
+    ("whitted", None, "plastic", "glass", "sobol", "env", "fbm", "wrinkled", "scale"),
+    ("ao", None, "matte", "mirror", "halton", "instance", "wrinkled", None, None),
+    ("ao", None, "mirror", "plastic", "sobol", "env", "windy", "image64_clamp_trilinear", None),
+    ("ao", None, "glass", "glass", "halton", None, "checker3d", "scale", None),
+    ("ao", None, "plastic", "matte", "halton", "sphere", "planar", None, None),
+]
+
+
+def alpha_render_name(row):
+    integ, strat, on, under, sampler, extra = row[:6]
+    return "%s_%s_on_%s_%s_%s" % (integ if strat is None else integ + "_" + strat, on, under, sampler, extra or "plain")
+
+
+def alpha_render_scene(row):
+    integ, strat, on, under, sampler, extra, mask, shadow, emitter = row
+    return scene_alpha(integ, strat, on=on, under=under, sampler=sampler, extra=extra, mask=mask, shadow=shadow, emitter=emitter,
+                       spp=8 if sampler == "sobol" else 6)

@@ -1,4 +1,5 @@
-"""ctypes loader for oracle/liboracle.so -- the CPU restatement used as the checker.
+"""ctypes loader for oracle/liboracle.so -- the CPU restatement used as the checker.  OracleScene hands the oracle everything a SceneDesc
+carries beside its descriptor: the infinite lights and the alpha masks ("alpha" / "shadowalpha", restated in orc_accel.hpp).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this."""
 import ctypes as C
 import importlib
@@ -30,6 +31,7 @@ class Oracle:
         vp, u32 = C.c_void_p, C.c_uint32
         lib.orc_scene_create.argtypes = [C.POINTER(capi.pt_scene_desc), C.c_char_p, C.POINTER(vp)]
         lib.orc_scene_create_env.argtypes = [C.POINTER(capi.pt_scene_desc), C.c_char_p, u32, C.POINTER(capi.pt_infinite_light), C.POINTER(vp)]
+        lib.orc_scene_create_masked.argtypes = [C.POINTER(capi.pt_scene_desc), C.c_char_p, u32, C.POINTER(capi.pt_infinite_light), u32, C.POINTER(capi.pt_alpha_mask), C.POINTER(vp)]
         lib.orc_light_sample_li.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
         lib.orc_light_pdf_li.argtypes = [vp, u32, u32, vp, vp]
         lib.orc_light_le.argtypes = [vp, u32, u32, vp, vp]
@@ -110,7 +112,9 @@ class OracleScene:
         self.h = C.c_void_p()
         inf = list(getattr(sd, "infinite_lights", None) or [])        # LightSource "infinite": rendered by the oracle too, never dropped
         arr = (capi.pt_infinite_light * max(1, len(inf)))(*inf)
-        rc = self.lib.orc_scene_create_env(C.byref(sd.desc), DATA_DIR.encode(), len(inf), arr, C.byref(self.h))
+        am = list(getattr(sd, "alpha_masks", None) or [])             # "alpha" / "shadowalpha" of the meshes: honoured by every trace and render, never dropped
+        am_arr = (capi.pt_alpha_mask * max(1, len(am)))(*am)
+        rc = self.lib.orc_scene_create_masked(C.byref(sd.desc), DATA_DIR.encode(), len(inf), arr, len(am), am_arr, C.byref(self.h))
         assert rc == 0, "orc_scene_create failed"
         self.info = capi.pt_scene_info()
         self.lib.orc_scene_info(self.h, C.byref(self.info))

@@ -1,10 +1,13 @@
-"""Alpha masks on the GPU (shapes/alphamask.rs).  The oracle has no masks, so a masked scene never goes to it: every masked triangle lies
-strictly inside one region of constant mask value, which makes "alpha <= 0" mean exactly "these triangles are absent", and exact truth
-comes from the equivalent scene without them.
+"""Alpha masks on the GPU (shapes/alphamask.rs) where exact truth needs no mask evaluation at all: every masked triangle lies strictly
+inside one region of constant mask value, which makes "alpha <= 0" mean exactly "these triangles are absent", and the truth comes from the
+equivalent scene without them.  That proves the plumbing (flags, the per-mesh table, t_max restored, shadowalpha for any-hit rays only,
+lights ignoring masks); masks that vary inside a triangle are held in test_gpu_alpha_mask_parity.py, and the oracle's own masks in
+test_alpha_mask_oracle.py.
 
   * hooks: rays aimed into the masked quads through pt_trace_closest / pt_trace_any against the expected hit / occlusion;
-  * removal: the masked scene rendered on the device equals the oracle's render of the scene without the cut-out triangles, per sample and
-    film weight, bit for bit, over integrators, materials, samplers, spheres, object instances (mask in object space) and an environment;
+  * removal: the masked scene rendered on the device equals the oracle's render of the scene without the cut-out triangles AND the oracle's
+    render of the masked scene itself, per sample and film weight, bit for bit, over integrators, materials, samplers, spheres, object
+    instances (mask in object space) and an environment;
   * shadowalpha 0 under whitted, an invisible emitter (alpha 0 on an area light), and the command-line front end."""
 import os
 import subprocess
@@ -27,9 +30,8 @@ def _clean_counters(gpu_ctx):
 
 
 def oracle_scene(sd):
-    """The oracle renders unmasked scenes only (tests/oracle_lib.OracleScene does not forward alpha_masks)."""
+    """The oracle's scene, masks included (tests/oracle_lib.OracleScene forwards sd.alpha_masks)."""
     import oracle_lib
-    assert not sd.alpha_masks
     return oracle_lib.load().scene(sd)
 
 
@@ -181,6 +183,18 @@ def check_equivalent(ctx, sd_masked, sd_cut):
     assert np.allclose(gx[..., :3], ox[..., :3], rtol=1e-6, atol=1e-7)
     for k in ("camera_rays", "regular_rays", "shadow_rays"):
         assert gc[k] == oc[k], (k, gc[k], oc[k])
+    # the third side: the oracle's render of the masked scene itself -- the same tree, so the traversal counters agree as well
+    osc = oracle_scene(sd_masked)
+    try:
+        ms = osc.radiance_samples(tuple(info.sample_bounds))
+        mx, mc, _ = osc.render(threads=8)
+    finally:
+        osc.close()
+    assert np.array_equal(bits(gs), bits(ms)), np.abs(gs - ms).max()
+    assert np.array_equal(bits(gx[..., 3]), bits(mx[..., 3]))
+    assert np.allclose(gx[..., :3], mx[..., :3], rtol=1e-6, atol=1e-7)
+    for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices", "nodes_visited", "tris_tested"):
+        assert gc[k] == mc[k], (k, gc[k], mc[k])
 
 
 def removal_scene(cut, integ, material, sampler, extra, mask="checker"):

@@ -138,15 +138,17 @@ def _soup(rng, n, center, radius, size):
     return (c[:, None, :] + off).reshape(-1, 3), np.arange(3 * n)
 
 
-def _shape(b, rng, where):
+def _shape(b, rng, where, mesh=None):
+    """mesh: the call that emits a triangle mesh (b.shape_trianglemesh, or _masked_mesh's)."""
+    mesh = mesh or b.shape_trianglemesh
     kind = int(rng.integers(0, 5))
     if kind == 0:
         P, idx = _soup(rng, int(rng.integers(1, 600)), where, float(rng.uniform(0.1, 0.5)), float(rng.uniform(0.02, 0.25)))
-        b.shape_trianglemesh(P, idx, twosided=bool(rng.random() < 0.8))
+        mesh(P, idx, twosided=bool(rng.random() < 0.8))
     elif kind == 1:
         P, N, UV, idx = fs.uv_sphere(where, float(rng.uniform(0.2, 0.8)), int(rng.integers(2, 9)), int(rng.integers(3, 12)))
         tang = np.tile(np.asarray(rng.uniform(-1, 1, 3), np.float32), (len(P), 1)) if rng.random() < 0.3 else None
-        b.shape_trianglemesh(P, idx, N=N if rng.random() < 0.7 else None, uv=UV if rng.random() < 0.7 else None, S=tang, twosided=bool(rng.random() < 0.8))
+        mesh(P, idx, N=N if rng.random() < 0.7 else None, uv=UV if rng.random() < 0.7 else None, S=tang, twosided=bool(rng.random() < 0.8))
     elif kind == 2:
         m = _xform(rng, where)
         r = float(rng.uniform(0.2, 0.7))
@@ -155,11 +157,11 @@ def _shape(b, rng, where):
                        phimax=float(rng.uniform(60, 360)) if partial else 360.0, object_to_world=m[0], world_to_object=m[1])
     elif kind == 3:
         q = np.asarray(where, np.float32) + rng.uniform(-0.7, 0.7, (4, 3)).astype(np.float32)
-        b.shape_trianglemesh(q, [0, 1, 2, 0, 2, 3], uv=[(0, 0), (1, 0), (1, 1), (0, 1)] if rng.random() < 0.5 else None, twosided=bool(rng.random() < 0.8))
+        mesh(q, [0, 1, 2, 0, 2, 3], uv=[(0, 0), (1, 0), (1, 1), (0, 1)] if rng.random() < 0.5 else None, twosided=bool(rng.random() < 0.8))
     else:
         b.reverse_orientation = True
         q = np.asarray(where, np.float32) + rng.uniform(-0.6, 0.6, (3, 3)).astype(np.float32)
-        b.shape_trianglemesh(q, [0, 1, 2], twosided=False)
+        mesh(q, [0, 1, 2], twosided=False)
         b.reverse_orientation = False
 
 
@@ -179,13 +181,40 @@ def _env_lights(b, erng):
                      world_to_light=m[1].reshape(4, 4), nsamples=int(erng.integers(1, 5)))
 
 
-def random_scene(seed, env=False):
+def _masked_mesh(b, mrng):
+    """masks=True: what _shape and the light loop call instead of b.shape_trianglemesh.  Every triangle mesh they emit -- world meshes,
+    meshes inside ObjectBegin, mesh lights -- asks a generator of its own whether it carries "alpha", "shadowalpha", both or neither, each a
+    constant (<= 0 or > 0) or a float texture remapped to straddle zero, mix(-c, +c, amount = texture).  The first mesh asked always gets a
+    texture "alpha".  The room is built by fs.room and never comes here."""
+    first = [True]
+
+    def one(force_texture):
+        if force_texture or mrng.random() < 0.7:
+            c = float(mrng.uniform(0.2, 1.0))
+            return b.texture_mix(-c, c, amount=_float_texture(b, mrng, 1))
+        return float(mrng.choice([-1.0, 0.0, 0.5, 2.0]))
+
+    def mesh(P, indices, **kw):
+        which = 1 if first[0] else int(mrng.integers(0, 5))           # 0: none, 1: alpha, 2: shadowalpha, 3-4: both
+        if which in (1, 3, 4):
+            kw["alpha"] = one(first[0])
+        if which in (2, 3, 4):
+            kw["shadowalpha"] = one(False)
+        first[0] = False
+        return b.shape_trianglemesh(P, indices, **kw)
+
+    return mesh
+
+
+def random_scene(seed, env=False, masks=False):
     """env: the same scene (every draw of the main generator unchanged) plus one or two infinite lights, drawn from a generator of their own,
-    before or after the area lights, and sometimes a room without its ceiling."""
+    before or after the area lights, and sometimes a room without its ceiling.  masks: the same scene with alpha masks on its triangle
+    meshes, drawn from a third generator (_masked_mesh)."""
     erng = np.random.default_rng((seed, 0xE)) if env else None
     env_where = [int(erng.integers(0, 2)) for _ in range(1 if erng.random() < 0.7 else 2)] if env else []    # 0: before the lights, 1: after
     rng = np.random.default_rng(1000 + seed)
     b = scenes.SceneBuilder()
+    mesh = _masked_mesh(b, np.random.default_rng((seed, 0xA))) if masks else b.shape_trianglemesh
     eye = (float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)), -6.5 + float(rng.uniform(-0.5, 0.5)))
     b.look_at(eye, (0, 0, 0), (0, 1, 0))
     lens = rng.random() < 0.25
@@ -229,7 +258,7 @@ def random_scene(seed, env=False):
         b.object_begin(name)
         for _ in range(int(rng.integers(1, 4))):
             _material(b, rng, ao)
-            _shape(b, rng, (0.0, 0.0, 0.0))
+            _shape(b, rng, (0.0, 0.0, 0.0), mesh)
         b.object_end()
         names.append(name)
     for _ in range(env_where.count(0)):
@@ -237,7 +266,7 @@ def random_scene(seed, env=False):
     fs.room(b, light_L=_rgb(rng, 3.0, 12.0), two_sided_light=bool(rng.random() < 0.3), open_top=bool(env and erng.random() < 0.5))
     for _ in range(int(rng.integers(1, 6))):
         _material(b, rng, ao)
-        _shape(b, rng, tuple(float(x) for x in rng.uniform(-1.4, 1.4, 3)))
+        _shape(b, rng, tuple(float(x) for x in rng.uniform(-1.4, 1.4, 3)), mesh)
     for name in names:
         for _ in range(int(rng.integers(1, 3))):
             b.object_instance(name, _xform(rng, tuple(float(x) for x in rng.uniform(-1.3, 1.3, 3))))
@@ -249,10 +278,10 @@ def random_scene(seed, env=False):
         k = int(rng.integers(0, 3))
         if k == 0:
             q = np.asarray(c, np.float32) + rng.uniform(-0.3, 0.3, (4, 3)).astype(np.float32)
-            b.shape_trianglemesh(q, [0, 1, 2, 0, 2, 3])
+            mesh(q, [0, 1, 2, 0, 2, 3])
         elif k == 1:
             P, N, UV, idx = fs.uv_sphere(c, float(rng.uniform(0.1, 0.3)), 3, 5)
-            b.shape_trianglemesh(P, idx, N=N if rng.random() < 0.5 else None)
+            mesh(P, idx, N=N if rng.random() < 0.5 else None)
         else:
             m = _xform(rng, c)
             b.shape_sphere(radius=float(rng.uniform(0.1, 0.3)), object_to_world=m[0], world_to_object=m[1])
@@ -306,16 +335,48 @@ def test_random_env_scene_pairwise_node_fetch(fuzz_ctx_far, oracle, seed):
 
 
 @pytest.mark.parametrize("seed", _seeds())
-def test_random_scene(fuzz_ctx, oracle, seed, env=False):
-    sd, exact_film = random_scene(seed, env)
+def test_random_masked_scene(fuzz_ctx, oracle, seed):
+    """The same scenes with alpha masks drawn onto their triangle meshes (shapes/alphamask.rs, oracle restatement in orc_accel.hpp):
+    k_trace_alpha / k_trace_batch_alpha against the oracle."""
+    test_random_scene(fuzz_ctx, oracle, seed, masks=True)
+
+
+@pytest.mark.parametrize("seed", _seeds()[:int(os.environ.get("FUZZ_FAR_N", "16"))])
+def test_random_masked_env_scene(fuzz_ctx, oracle, seed):
+    test_random_scene(fuzz_ctx, oracle, seed, env=True, masks=True)
+
+
+def test_masked_scene_ignores_trace_far(fuzz_ctx, fuzz_ctx_far):
+    """Masked scenes never run k_trace_far: with PBRTGPU_TRACE_FAR=1 set or unset a masked scene renders the same
+    samples, film and counters."""
+    from helpers import bits
+    sd, exact_film = random_scene(1, masks=True)
+    assert exact_film and any(m.alpha_kind == pkg.capi.PT_ALPHA_TEXTURE for m in sd.alpha_masks)
+    out = []
+    for ctx in (fuzz_ctx, fuzz_ctx_far):
+        info = ctx.upload(sd)
+        sb = list(info.sample_bounds)
+        cx, cy = (sb[0] + sb[2]) // 2, (sb[1] + sb[3]) // 2
+        rs = ctx.radiance_samples((cx - 8, cy - 8, cx + 8, cy + 8))
+        ctx.film_clear(); ctx.reset_counters(); ctx.render()
+        out.append((rs, ctx.film_xyzw(), ctx.counters()))
+    assert np.array_equal(bits(out[0][0]), bits(out[1][0]))
+    assert np.array_equal(bits(out[0][1][..., 3]), bits(out[1][1][..., 3])) and np.allclose(out[0][1], out[1][1], rtol=1e-5, atol=1e-6)
+    for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices", "nodes_visited", "tris_tested"):
+        assert out[0][2][k] == out[1][2][k], k
+
+
+@pytest.mark.parametrize("seed", _seeds())
+def test_random_scene(fuzz_ctx, oracle, seed, env=False, masks=False):
+    sd, exact_film = random_scene(seed, env, masks)
     fuzz_ctx.set_bvh_build(DEVICE if seed % 3 == 0 else (HOST if seed % 3 == 1 else AUTO))
     osc = oracle.scene(sd)
     oracle.reference_panics()          # cleared
     try:
         fuzz_ctx.upload(sd)
         d = sd.desc
-        what = "%d triangles %d spheres %d instances %d lights, integrator %d split %d leaf %d" % (
-            d.n_triangles, d.n_spheres, d.n_instances, fuzz_ctx.info.n_lights, d.integrator, d.split_method, d.max_node_prims)
+        what = "%d triangles %d spheres %d instances %d lights %d masked meshes, integrator %d split %d leaf %d" % (
+            d.n_triangles, d.n_spheres, d.n_instances, fuzz_ctx.info.n_lights, len(sd.alpha_masks), d.integrator, d.split_method, d.max_node_prims)
         try:
             err, frac = _compare(fuzz_ctx, osc, exact_film, weight_tol=1e-5)
         except pkg.capi.PtError as e:

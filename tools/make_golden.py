@@ -10,6 +10,7 @@ against accidental change and give the GPU tests a committed target:
   tests/golden/{directlighting_all_ns3,whitted_depth4,ao_16cos_cornell}_*.npz   the other integrators: film, per-sample radiance of the
                                                       middle tile, ray counters (tests/feature_scenes.py::GOLDEN_INTEGRATORS)
   tests/golden/env_directlighting_halton_32x32_4spp.npz   the same for an environment-lit scene (feature_scenes.scene_env_golden)
+  tests/golden/alpha_path_halton_32x32_4spp.npz   the same for a scene of alpha-masked meshes (feature_scenes.scene_alpha_golden)
 """
 import importlib, os, sys
 import numpy as np
@@ -62,4 +63,11 @@ xyzw_e, cnt_e, _ = sce.render(threads=1)
 np.savez_compressed(os.path.join(G, "env_directlighting_halton_32x32_4spp.npz"), xyzw=xyzw_e, radiance=sce.radiance_samples(fs.golden_tile(sce.info)),
                     counters=np.array([cnt_e[k] for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices")], np.int64))
 sce.close()
+# alpha masks that vary inside their triangles ("alpha" an image map, "shadowalpha" a checkerboard, a masked emitter), path, Halton
+sda = fs.scene_alpha_golden()
+sca = orc.scene(sda)
+xyzw_a, cnt_a, _ = sca.render(threads=1)
+np.savez_compressed(os.path.join(G, "alpha_path_halton_32x32_4spp.npz"), xyzw=xyzw_a, radiance=sca.radiance_samples(fs.golden_tile(sca.info)),
+                    counters=np.array([cnt_a[k] for k in ("camera_rays", "regular_rays", "shadow_rays", "path_vertices")], np.int64))
+sca.close()
 print("golden written:", os.listdir(G))
