@@ -83,6 +83,24 @@ int orc_light_le(const orc_scene* s, uint32_t light, uint32_t n, const float* d,
     }
     return 0;
 }
+// Texture::evaluate of texture `texture_index` on n caller-given interactions: p, dpdx, dpdy (3 floats each) and uv (2) per
+// interaction, the four uv derivatives one float each.  The oracle only: the product has no such entry point (tests/texture_ref.py
+// holds this to float64; the device meets the same truth through rendered radiance).
+int orc_texture_eval(const orc_scene* s, uint32_t texture_index, uint32_t n, const float* p, const float* uv, const float* dpdx, const float* dpdy,
+                     const float* dudx, const float* dvdx, const float* dudy, const float* dvdy, float* rgb_out) {
+    if (texture_index >= s->sc.textures.size()) return 1;
+    for (uint32_t i = 0; i < n; i++) {
+        TexHit th;
+        th.p = V3(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+        th.dpdx = V3(dpdx[3 * i], dpdx[3 * i + 1], dpdx[3 * i + 2]);
+        th.dpdy = V3(dpdy[3 * i], dpdy[3 * i + 1], dpdy[3 * i + 2]);
+        th.uv = V2(uv[2 * i], uv[2 * i + 1]);
+        th.dudx = dudx[i]; th.dvdx = dvdx[i]; th.dudy = dudy[i]; th.dvdy = dvdy[i];
+        RGB c = texture_eval(s->sc.textures.data(), (int32_t)texture_index, th, s->sc.images.data());
+        rgb_out[3 * i] = c.c[0]; rgb_out[3 * i + 1] = c.c[1]; rgb_out[3 * i + 2] = c.c[2];
+    }
+    return 0;
+}
 void orc_scene_destroy(orc_scene* s) { delete s; }
 
 void orc_scene_info(const orc_scene* s, pt_scene_info* o) {

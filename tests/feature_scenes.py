@@ -953,3 +953,196 @@ def alpha_render_scene(row):
     integ, strat, on, under, sampler, extra, mask, shadow, emitter = row
     return scene_alpha(integ, strat, on=on, under=under, sampler=sampler, extra=extra, mask=mask, shadow=shadow, emitter=emitter,
                        spp=8 if sampler == "sobol" else 6)
+
+
+# ---- textures held to float64 (tests/texture_ref.py): one description drives the scene builder and the float64 evaluator.
+# A spec is a dict {"type": ..., parameters under the scene file's names}; children ("tex1", "tex2", "amount") are specs, numbers or RGB
+# triples; an imagemap carries its level-0 image under "image"; "to_world" is a (m, m_inv) pair as the transform_* helpers return.
+_SPEC_2D = ("mapping", "uscale", "vscale", "udelta", "vdelta", "v1", "v2", "to_world")
+
+
+def texture_from_spec(b, spec):
+    """The builder's texture for a spec (recursively): a Tex handle, or the constant itself."""
+    if not isinstance(spec, dict):
+        return tuple(spec) if isinstance(spec, (tuple, list)) else float(spec)
+    ch = lambda k, d: texture_from_spec(b, spec.get(k, d))
+    kw = {k: spec[k] for k in _SPEC_2D if k in spec}
+    kind = spec["type"]
+    if kind == "scale":
+        return b.texture_scale(ch("tex1", 1.0), ch("tex2", 1.0))
+    if kind == "mix":
+        return b.texture_mix(ch("tex1", 1.0), ch("tex2", 1.0), ch("amount", 0.5))
+    if kind == "checkerboard":
+        if spec.get("dimension", 2) == 3:
+            return b.texture_checkerboard(ch("tex1", 1.0), ch("tex2", 0.0), dimension=3, to_world=spec.get("to_world"))
+        return b.texture_checkerboard(ch("tex1", 1.0), ch("tex2", 0.0), aamode=spec.get("aamode", "closedform"), **kw)
+    if kind == "dots":
+        return b.texture_dots(ch("tex1", 1.0), ch("tex2", 0.0), **kw)
+    if kind == "imagemap":
+        names = {0: "repeat", 1: "black", 2: "clamp"}
+        return b.texture_imagemap(b.image_pyramid(spec["image"]), trilinear=spec.get("trilinear", False), maxanisotropy=spec.get("maxanisotropy", 8.0),
+                                  swrap=names[spec.get("swrap", spec.get("wrap", 0))], twrap=names[spec.get("twrap", spec.get("wrap", 0))], **kw)
+    if kind == "uv":
+        return b.texture_uv(**kw)
+    if kind == "bilerp":
+        return b.texture_bilerp(spec["v00"], spec["v01"], spec["v10"], spec["v11"], **kw)
+    if kind in ("fbm", "wrinkled"):
+        return getattr(b, "texture_" + kind)(octaves=spec.get("octaves", 8), roughness=spec.get("roughness", 0.5), to_world=spec.get("to_world"))
+    if kind == "windy":
+        return b.texture_windy(to_world=spec.get("to_world"))
+    if kind == "marble":
+        return b.texture_marble(octaves=spec.get("octaves", 8), roughness=spec.get("roughness", 0.5), scale=spec.get("scale", 1.0),
+                                variation=spec.get("variation", 0.2), to_world=spec.get("to_world"))
+    raise ValueError(kind)
+
+
+def texture_ref_spec(spec, pyramid):
+    """The same spec as texture_ref.evaluate reads it: the image replaced by its pyramid (`pyramid`: texture_ref.pyramid), to_world by
+    the matrix the texture maps points with -- the inverse for the 2-D mappings (mapping2d.rs:190-198), tex2world itself for the 3-D
+    ones (IdentityMapping3D::new(tex2world): fbm.rs:42, wrinkled.rs:42, windy.rs:38, marble.rs:87, checkerboard.rs:152)."""
+    if not isinstance(spec, dict):
+        return spec
+    out = {k: (texture_ref_spec(v, pyramid) if k in ("tex1", "tex2", "amount") else v) for k, v in spec.items() if k not in ("image", "to_world")}
+    if "image" in spec:
+        out["levels"] = pyramid(spec["image"])
+    if spec.get("to_world") is not None:
+        three_d = spec["type"] in ("fbm", "wrinkled", "windy", "marble") or (spec["type"] == "checkerboard" and spec.get("dimension", 2) == 3)
+        out["world_to_texture"] = np.asarray(spec["to_world"][0 if three_d else 1], np.float32).astype(np.float64).reshape(4, 4)
+    return out
+
+
+# ---- the observable of the filtered texture value (tests/test_gpu_texture_truth.py, test_texture_oracle.py): one planar quad with
+# explicit uv, tilted against the view so that the footprint runs from mildly to strongly anisotropic across the tile, a Mirror whose
+# Kr is the texture under test, and one light of radiance 1 in every direction: a constant infinite light ("env" rows; the reflected ray
+# escapes) or a closed box of two-sided diffuse emitters around camera and quad ("box" rows; the reflected ray ends on an emitter,
+# whose matte Kd is 0).  Either way the radiance of a sample is Kr (clamped at zero, mirror.rs:32) as filtered with that camera ray's
+# differentials.  The two lights select different shading kernels on the device: with an infinite light the wavefront shades every
+# material in k_shade_env / k_shade_env_inst (ptk_shade returns before the material sort and the textured split), which call the
+# __noinline__ instantiation of the texture code; without one, and without instances, the textured hits of `path` go through
+# k_tex_resolve -- the __forceinline__ instantiation with its value buffer in LDS -- and k_shade_general_res, and an instanced scene
+# through k_shade_general_inst.
+TRUTH_RES, TRUTH_TILE = 20, (2, 2, 18, 18)
+TRUTH_EYE, TRUTH_LOOK, TRUTH_UP, TRUTH_FOV = (0.0, 2.4, -1.6), (0.0, 0.0, 0.6), (0.0, 1.0, 0.0), 80.0
+TRUTH_QUAD = [(-4.0, -0.3, -2.5), (4.0, -0.3, -2.5), (4.0, 0.6, 6.5), (-4.0, 0.6, 6.5)]
+TRUTH_UV = [(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)]
+TRUTH_LENS = (0.05, 3.5)          # lensradius, focaldistance of the thin-lens rows
+
+
+_TRUTH_IMAGES = {}
+
+
+def truth_image(channels):
+    """1024 x 512 texels in [0.1, 0.9]: one or two periods of a sine across the image.  The quad shows a fraction of a period (the uv
+    scales below are < 1), so the texels under one footprint differ by a few hundredths of the range: what a texel that takes the
+    neighbouring entry of the EWA weight table can change is proportional to that difference, and so is what a wrong filter changes,
+    while the line below which a derived bound counts (1e-3 of the range) is not."""
+    if channels not in _TRUTH_IMAGES:
+        y, x = np.mgrid[0:512, 0:1024]
+        out = np.empty((512, 1024, channels), np.float32)
+        for k in range(channels):
+            out[:, :, k] = 0.5 + 0.4 * np.sin(2 * np.pi * ((1 + k % 2) * x / 1024.0 + (1 + (k + 1) % 2) * y / 512.0) + k)
+        _TRUTH_IMAGES[channels] = out
+    return _TRUTH_IMAGES[channels]
+
+
+def truth_texture_spec(name):
+    rgb, mono = truth_image(3), truth_image(1)
+    dense = dict(uscale=0.25, vscale=0.4)                               # a footprint of a few texels at the tile's centre
+    edge = dict(uscale=0.5, vscale=0.8, udelta=-0.2, vdelta=-0.2)       # st runs from -0.05 to 0.43: the image's corner is in view
+    tw = scenes.transform_mul(scenes.transform_translate(0.3, 0.1, -0.2), scenes.transform_mul(scenes.transform_rotate_x(-40.0), scenes.transform_scale(2.0, 3.5, 0.6)))
+    checker = dict(type="checkerboard", tex1=(0.9, 0.8, 0.1), tex2=(0.1, 0.2, 0.7), uscale=15.0, vscale=13.0)
+    return {
+        "ewa1": dict(type="imagemap", image=rgb, maxanisotropy=1.0, wrap=0, **dense),
+        "ewa8": dict(type="imagemap", image=rgb, maxanisotropy=8.0, wrap=0, **dense),
+        "ewa16": dict(type="imagemap", image=rgb, maxanisotropy=16.0, wrap=0, uscale=0.25, vscale=1.2),
+        "trilinear": dict(type="imagemap", image=rgb, trilinear=True, wrap=0, **dense),
+        "mono_ewa": dict(type="scale", tex1=dict(type="imagemap", image=mono, maxanisotropy=8.0, wrap=0, **dense), tex2=(0.9, 0.5, 0.7)),
+        "mono_trilinear": dict(type="scale", tex1=dict(type="imagemap", image=mono, trilinear=True, wrap=2, **dense), tex2=(0.4, 0.8, 0.6)),
+        "ewa_black": dict(type="imagemap", image=rgb, maxanisotropy=8.0, wrap=1, **edge),
+        "ewa_clamp": dict(type="imagemap", image=rgb, maxanisotropy=8.0, wrap=2, **edge),
+        "ewa_deltas": dict(type="imagemap", image=rgb, maxanisotropy=8.0, wrap=0, uscale=1.5, vscale=0.3, udelta=0.25, vdelta=-0.5),
+        "planar": dict(type="imagemap", image=rgb, trilinear=True, wrap=0, mapping="planar", v1=(0.5, 0.1, 0.0), v2=(0.1, 0.2, 0.6), udelta=0.2, vdelta=0.1),
+        "spherical": dict(type="imagemap", image=rgb, trilinear=True, wrap=0, mapping="spherical", to_world=scenes.transform_translate(0.3, 1.5, 0.2)),
+        "checker": checker,
+        "checker_none": dict(checker, aamode="none"),
+        "fbm": dict(type="fbm", octaves=6, roughness=0.6, to_world=tw),
+        "wrinkled": dict(type="wrinkled", octaves=5, roughness=0.5, to_world=tw),
+        "windy": dict(type="windy", to_world=tw),
+        "marble": dict(type="marble", octaves=6, roughness=0.5, scale=2.0, variation=0.4),
+        "dots": dict(type="dots", tex1=(0.9, 0.1, 0.1), tex2=(0.1, 0.9, 0.9), uscale=8.0, vscale=8.0),
+        "mix": dict(type="mix", tex1=dict(type="imagemap", image=rgb, maxanisotropy=8.0, wrap=0, **dense), tex2=checker, amount=dict(type="fbm", octaves=3, roughness=0.5, to_world=tw)),
+    }[name]
+
+
+TRUTH_TEXTURES = ["ewa1", "ewa8", "ewa16", "trilinear", "mono_ewa", "mono_trilinear", "ewa_black", "ewa_clamp", "ewa_deltas", "planar", "spherical",
+                  "checker", "checker_none", "fbm", "wrinkled", "windy", "marble", "dots", "mix"]
+
+
+def _truth_rows():
+    """(texture, camera, sampler, spp, placement, light).  Every texture twice under the infinite light, the second time with the four
+    middle columns flipped, the first time with the bits of a counter; then once more in world space inside the emitting box -- the
+    only rows `path` shades through k_tex_resolve, see scene_texture_truth -- and every fourth texture inside the box as an instance.
+    Every pair of values of any two columns occurs (test_texture_oracle.py counts them)."""
+    cols = (("pinhole", "lens"), ("sobol", "halton"), (4, 1), ("world", "instance"))
+    rows = []
+    for i, t in enumerate(TRUTH_TEXTURES):
+        bits = [(i >> k) & 1 for k in range(4)]
+        rows.append((t,) + tuple(c[b] for c, b in zip(cols, bits)) + ("env",))
+        rows.append((t,) + tuple(c[1 - b] for c, b in zip(cols, bits)) + ("env",))
+    for i, t in enumerate(TRUTH_TEXTURES):
+        bits = [((5 * i + 3) >> k) & 1 for k in range(3)]
+        rows.append((t,) + tuple(c[b] for c, b in zip(cols, bits)) + ("world", "box"))
+        if i % 4 == 0:
+            rows.append((t,) + tuple(c[1 - b] for c, b in zip(cols, bits)) + ("instance", "box"))
+    return rows
+
+
+TEXTURE_TRUTH = _truth_rows()
+TRUTH_INTEGRATORS = ("path", "whitted")
+TRUTH_DIRECTLIGHTING_ROWS = (2, 23)                                      # "directlighting" renders these two rows as well
+
+
+def truth_instance_transform():
+    T = scenes
+    return T.transform_mul(T.transform_translate(0.2, -0.1, 0.3), T.transform_mul(T.transform_rotate_x(12.0), T.transform_scale(1.3, 0.8, 1.1)))
+
+
+def truth_quad(placement):
+    """The quad's vertices as the scene file gives them (float32) and in world space (float64, through the float32 matrix)."""
+    P = np.asarray(TRUTH_QUAD, np.float32)
+    if placement == "world":
+        return P, P.astype(np.float64), None
+    xf = truth_instance_transform()                                     # the object-space quad is the world one carried back, so both rows see one picture
+    m, mi = (np.asarray(x, np.float32).astype(np.float64).reshape(4, 4) for x in xf)
+    P = (P.astype(np.float64) @ mi[:3, :3].T + mi[:3, 3]).astype(np.float32)
+    return P, P.astype(np.float64) @ m[:3, :3].T + m[:3, 3], xf
+
+
+def scene_texture_truth(row, integrator):
+    texture, camera, sampler, spp, placement, light = row
+    b = scenes.SceneBuilder()
+    b.look_at(TRUTH_EYE, TRUTH_LOOK, TRUTH_UP)
+    lens = TRUTH_LENS if camera == "lens" else (0.0, 1e6)
+    b.camera_perspective(fov=TRUTH_FOV, lensradius=lens[0], focaldistance=lens[1])
+    b.film(xresolution=TRUTH_RES, yresolution=TRUTH_RES)
+    b.pixel_filter_box()
+    (b.sampler_halton if sampler == "halton" else b.sampler_sobol)(spp)
+    {"path": b.integrator_path, "whitted": b.integrator_whitted, "directlighting": b.integrator_directlighting}[integrator](maxdepth=3)
+    if light == "env":
+        b.light_infinite(L=(1.0, 1.0, 1.0))
+    else:                                                               # a closed box of two-sided emitters of radiance 1 around camera and quad
+        b.material_matte(Kd=(0.0, 0.0, 0.0))
+        b.area_light_source_diffuse(L=(1.0, 1.0, 1.0), twosided=True)
+        c = [(x, y, z) for x in (-16.0, 16.0) for y in (-16.0, 16.0) for z in (-16.0, 16.0)]
+        for f in ((0, 1, 3, 2), (4, 5, 7, 6), (0, 1, 5, 4), (2, 3, 7, 6), (0, 2, 6, 4), (1, 3, 7, 5)):
+            scenes._quad(b, *[c[k] for k in f])
+        b.no_area_light()
+    P, _, xf = truth_quad(placement)
+    if xf is not None:
+        b.object_begin("quad")
+    b.material_mirror(Kr=texture_from_spec(b, truth_texture_spec(texture)))
+    b.shape_trianglemesh(P, [0, 1, 2, 0, 2, 3], uv=TRUTH_UV)
+    if xf is not None:
+        b.object_end()
+        b.object_instance("quad", xf)
+    return b.build()

@@ -35,6 +35,7 @@ class Oracle:
         lib.orc_light_sample_li.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
         lib.orc_light_pdf_li.argtypes = [vp, u32, u32, vp, vp]
         lib.orc_light_le.argtypes = [vp, u32, u32, vp, vp]
+        lib.orc_texture_eval.argtypes = [vp, u32, u32] + [vp] * 9
         lib.orc_scene_destroy.argtypes = [vp]
         lib.orc_scene_destroy.restype = None
         lib.orc_scene_info.argtypes = [vp, C.POINTER(capi.pt_scene_info)]
@@ -234,6 +235,21 @@ class OracleScene:
         d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
         out = np.empty((len(d), 3), np.float32)
         assert self.lib.orc_light_le(self.h, light, len(d), _p(d), _p(out)) == 0, "not an infinite light"
+        return out
+
+    def texture_eval(self, texture, p=None, uv=None, dpdx=None, dpdy=None, dudx=None, dvdx=None, dudy=None, dvdy=None):
+        """Texture::evaluate of texture `texture` (a Tex handle or an index) on caller-given interactions: RGB (n, 3); a float texture
+        has three equal channels.  Whatever is not given is zero."""
+        given = [a for a in (p, uv, dpdx, dpdy, dudx, dvdx, dudy, dvdy) if a is not None]
+        n = len(given[0])
+
+        def arr(a, k):
+            a = np.zeros((n, k), np.float32) if a is None else np.ascontiguousarray(a, np.float32).reshape(n, k)
+            return a
+        a = [arr(p, 3), arr(uv, 2), arr(dpdx, 3), arr(dpdy, 3), arr(dudx, 1), arr(dvdx, 1), arr(dudy, 1), arr(dvdy, 1)]
+        out = np.empty((n, 3), np.float32)
+        rc = self.lib.orc_texture_eval(self.h, C.c_uint32(int(getattr(texture, "index", texture))), C.c_uint32(n), *[_p(x) for x in a], _p(out))
+        assert rc == 0, "not a texture"
         return out
 
     def light_distribution(self, p):
