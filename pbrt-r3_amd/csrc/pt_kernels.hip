@@ -1316,6 +1316,16 @@ PT_DEV uint32_t wave_ticket(uint32_t* ticket) {
 #ifndef PT_WALK_BATCH
 #define PT_WALK_BATCH 1              // 1: a leaf's owner reads its results from LDS four at a time instead of one per loop iteration
 #endif
+#ifndef PT_LEAF_HELPER_ACCEPT
+#define PT_LEAF_HELPER_ACCEPT 1      // 1 (2: the sphere-capable kernel too): every helper applies tri_accept itself, with its owner's t_max as the round starts; one ballot is the round's candidate mask and
+                                     // an owner only walks the candidates among its leaf's items (most leaves have none: no LDS read, no loop).  Exact because tri_accept
+                                     // is monotone in t_max and a ray's t_max never grows: a test that fails against the round's t_max fails against every later one, and the
+                                     // first candidate of a leaf sees exactly the round's t_max (tests/test_accept_monotone.py).  0: the owner walks all of its leaf's results
+#endif
+#ifndef PT_RETIRE_AT_HANDOUT
+#define PT_RETIRE_AT_HANDOUT 1       // 1 (pooled-leaf kernels): a finished ray's result is stored in the block that hands out new rays (and in every iteration of the drain)
+                                     // instead of in the iteration it finishes in: the three store branches ran for one or two lanes in most iterations
+#endif
 #ifndef PT_SPH_LANES_MIN
 #define PT_SPH_LANES_MIN 8           // scenes with spheres: a sphere round once this many lanes are parked on a leaf that holds a sphere (2 / 4 / 6 / 8 / 10 / 16 / 24 / 32:
                                      // 46.9 / 45.2 / 44.6 / 44.4 / 44.5 / 44.9 / 48.6 / 54.2 ms per launch, RT1M lit by a sphere, 64 spp)
@@ -1454,18 +1464,28 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         const long long pt_pf = __builtin_readcyclecounter();
         prof[14] += (unsigned long long)(pt_pf - pt_iter);       // the prefetch state machine
 #endif
-        // ---- retire finished rays: stores only
-        if (kind != 0 && ray_done(r)) {
-            if (kind == 1) { P.hit_t[p] = r.ray_tmax; P.hit_rec[p] = r.best; if (INST && (!ALPHA || sc.n_instances)) P.hit_inst[p] = r.best_inst; }
-            else if (kind == 2) P.occluded[p] = r.best >= 0 ? 1 : 0;
-            else P.probe_rec[p] = r.best;
-            kind = 0;
+        // ---- retire finished rays: stores only.  Pooled-leaf kernels (PT_RETIRE_AT_HANDOUT): a finished lane needs nothing until it is refilled, so it keeps
+        // its result (kind != 0, ray_done) and counts as idle; the stores run where rays are handed out -- once PT_REFILL_MIN lanes are idle, not in every iteration
+        // in which one or two lanes finish -- and in every iteration once the queue is dry (the loop only ends from there: every ray is stored exactly once).
+        constexpr bool LATE_RETIRE = DIST && PT_RETIRE_AT_HANDOUT;
+#define PT_RETIRE()                                                                                                                                      \
+        if (kind != 0 && ray_done(r)) {                                                                                                                  \
+            if (kind == 1) { P.hit_t[p] = r.ray_tmax; P.hit_rec[p] = r.best; if (INST && (!ALPHA || sc.n_instances)) P.hit_inst[p] = r.best_inst; }      \
+            else if (kind == 2) P.occluded[p] = r.best >= 0 ? 1 : 0;                                                                                     \
+            else P.probe_rec[p] = r.best;                                                                                                                \
+            kind = 0;                                                                                                                                    \
+        }
+        if constexpr (LATE_RETIRE) {
+            if (!more) { PT_RETIRE() }
+        } else {
+            PT_RETIRE()
         }
         // ---- hand prefetched rays to idle lanes (one ray_begin site: it is long)
         {
-            const unsigned long long idle = __ballot(kind == 0);
+            const unsigned long long idle = LATE_RETIRE ? __ballot(kind == 0 || ray_done(r)) : __ballot(kind == 0);
             const uint32_t n_idle = (uint32_t)__popcll(idle);
             if (pf_stage == 3 && (n_idle >= PT_REFILL_MIN || idle == ~0ull || (!more && n_idle != 0))) {
+                if constexpr (LATE_RETIRE) { PT_RETIRE() }
                 const uint32_t take = min(n_idle, pf_count - pf_used);
                 const uint32_t rank = (uint32_t)__popcll(idle & below);
                 const int src = (int)((pf_used + rank) & 63u);
@@ -1484,10 +1504,11 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 if (pf_used == pf_count) pf_stage = 0;
             }
         }
+#undef PT_RETIRE
 #ifdef PT_PROFILE_PHASES
         prof[15] += (unsigned long long)(__builtin_readcyclecounter() - pt_pf);       // retiring and handing out rays
 #endif
-        if (__ballot(kind != 0) == 0) {
+        if ((LATE_RETIRE ? __ballot(kind != 0 && !ray_done(r)) : __ballot(kind != 0)) == 0) {      // nothing to traverse (late retire: with the queue dry everything finished was stored above)
             if (!more && pf_stage == 0) break;
             continue;
         }
@@ -1536,10 +1557,12 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             // issue: owners are served in lane order while their whole leaf fits (the others stay parked); lane w becomes the helper
             // of triangle k of owner o, takes the owner's ray constants by ds_bpermute and starts the 48-byte record's load.
             const uint32_t wbase = threadIdx.x & ~63u;
+            // (the sphere-capable kernel keeps the owner's full walk: with the candidate walk it spills 16 registers)
+            constexpr bool HACC = PT_LEAF_HELPER_ACCEPT == 2 || (PT_LEAF_HELPER_ACCEPT == 1 && !SPH);
             uint32_t lf_pre = 0, lf_items = 0;
             bool lf_served = false, lf_valid = false;
             int lf_kk = 0;
-            float lf_tmax = PT_INF;             // sphere rounds: the owner's t_max when the round starts (an upper bound of what its leaf walk will compare with)
+            float lf_tmax = PT_INF;             // (PT_LEAF_HELPER_ACCEPT: every round) the owner's t_max when the round starts (an upper bound of what its leaf walk will compare with)
             RayPre lf_rp;
             TriVerts lf_tv;
             auto leaf_issue = [&](auto sr_tag) {
@@ -1565,7 +1588,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 lf_rp.o = mk3(__shfl(r.rp.o.x, o, 64), __shfl(r.rp.o.y, o, 64), __shfl(r.rp.o.z, o, 64));
                 lf_rp.d = mk3(0.0f, 0.0f, 0.0f);        // only the one-sided test (and a sphere) reads the direction
                 if ((SPH && SR) || sc.any_one_sided) lf_rp.d = mk3(__shfl(r.rp.d.x, o, 64), __shfl(r.rp.d.y, o, 64), __shfl(r.rp.d.z, o, 64));     // (no sphere is tested outside a sphere round)
-                if constexpr (SPH && SR) lf_tmax = __shfl(r.ray_tmax, o, 64);
+                if constexpr ((SPH && SR) || HACC) lf_tmax = __shfl(r.ray_tmax, o, 64);
                 lf_kk = __shfl(r.rp.kx | (r.rp.ky << 2) | (r.rp.kz << 4) | ((kind == 2 ? 1 : 0) << 6), o, 64);
                 lf_rp.kx = lf_kk & 3; lf_rp.ky = (lf_kk >> 2) & 3; lf_rp.kz = (lf_kk >> 4) & 3;
                 lf_rp.sx = __shfl(r.rp.sx, o, 64); lf_rp.sy = __shfl(r.rp.sy, o, 64); lf_rp.sz = __shfl(r.rp.sz, o, 64);
@@ -1582,6 +1605,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 if constexpr (SPH) sphere_rec = lf_valid && (lf_tv.flags & PT_TRI_SPHERE) != 0;
                 unsigned long long m_sitems = 0;            // normal round: the items that are spheres (item i is helper lane i)
                 if constexpr (SPHDEF && !SR) { m_sitems = __ballot(sphere_rec); }
+                bool cand = false;          // PT_LEAF_HELPER_ACCEPT: this item passes everything, the t_max comparison against the round's t_max included
                 if (lf_valid) {
                     // The triangle test runs for EVERY item, a sphere's record included (its fields are not vertices: the result is thrown
                     // away).  With the test behind `if (!sphere)` the compiler moved the record's loads into the two branches, behind the
@@ -1590,6 +1614,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                     TriCore tc;
                     const bool tri_ok = tri_core(lf_rp, lf_tv.p0, lf_tv.p1, lf_tv.p2, lf_tv.flags, tc);
                     float4 res = make_float4(tri_ok ? 1.0f : 0.0f, tc.t_scaled, tc.det, tc.t);
+                    if constexpr (HACC) cand = tri_ok && tri_accept(tc.t_scaled, tc.det, lf_tmax);      // at full width, once for the round's 60 tests
                     if (SR && sphere_rec) {       // Sphere::intersect(_p) against the owner's t_max as the round starts; the owner applies the t_max tests again, in
                         // leaf order, with the t_max each item would have seen (never larger: a test that fails here fails there, and the value-lane
                         // reject inside sph_hit_test_inl ends nearly every shadow ray's test before the interval arithmetic starts)
@@ -1597,10 +1622,13 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         sh.t = 0.0f; sh.a_hi = 0.0f; sh.b_hi = 0.0f;
                         const bool ok = sph_hit_test_inl(sc.spheres[__float_as_uint(lf_tv.p0.x)], lf_rp.o, lf_rp.d, lf_tmax, (lf_kk & 64) ? 2.0f * PT_PI : PT_PI, &sh);
                         res = make_float4(ok ? 2.0f : 0.0f, sh.a_hi, sh.b_hi, sh.t);
+                        cand = ok;              // a sphere's hit is always a candidate: its owner keeps its own comparison
                     }
                     // (a sphere in a normal round: the owner sees the item in m_sitems and leaves its leaf parked for a sphere round)
-                    s_res[wbase + lane] = res;
+                    if (!HACC || cand) s_res[wbase + lane] = res;      // (only a candidate's result is ever read)
                 }
+                const unsigned long long m_cand = HACC ? __ballot(cand) : 0ull;        // the round's candidates (item i is helper lane i)
+                (void)m_cand;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1614,6 +1642,27 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                     const bool any_hit = kind == 2;
                     bool leaf_hit = false;
                     uint32_t tested = tcnt;
+                    if constexpr (HACC) {
+                    // The owner cuts its leaf's bits out of the round's candidate mask.  No bit (nearly every leaf: a ray makes 40 tests and accepts
+                    // one to three): nothing to read.  Otherwise the candidates in leaf order: the first saw the round's t_max, which is what the helper
+                    // compared with, and is accepted as it is; a later one is compared again, with the t_max the hits before it have left.
+                    uint32_t bits = (uint32_t)(m_cand >> lf_pre) & ((1u << tcnt) - 1u);
+                    bool first = true;
+                    while (bits != 0u) {
+                        const uint32_t k = (uint32_t)__builtin_ctz(bits);
+                        bits &= bits - 1u;
+                        const float4 v = s_res[wbase + lf_pre + k];
+                        bool acc;
+                        if (SPH && SR && v.x == 2.0f) acc = !(v.y > r.ray_tmax) && !(v.z > r.ray_tmax);      // (a sphere's result: only a sphere round makes one)
+                        else acc = first || tri_accept(v.y, v.z, r.ray_tmax);
+                        first = false;
+                        if (acc) {
+                            r.best = (int32_t)(rec0 + k); leaf_hit = true;
+                            if (any_hit) { r.sa = c.lane_base; r.top = PT_EMPTY_REF; tested = k + 1u; break; }
+                            r.ray_tmax = v.w;
+                        }
+                    }
+                    } else {
 #if PT_WALK_BATCH
                     // The results come four at a time: the loop's one LDS read per item was a round trip per item for the owner with the
                     // fullest leaf, and the whole wave waits for that owner.  (Slots past the leaf's own are read and ignored: they lie in
@@ -1649,6 +1698,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         }
                     }
 #endif
+                    }
                     c.n_tris += tested;
                     if (leaf_hit && !any_hit) r.tmax = r.ray_tmax;
                 }
