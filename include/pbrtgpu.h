@@ -127,7 +127,9 @@ typedef enum {
     PT_MATERIAL_GLASS = 4,     /* materials/glass.rs:46-110     Kr, Kt, eta, uroughness, vroughness, remaproughness */
     PT_MATERIAL_METAL = 5,     /* materials/metal.rs:51-85      eta (spectrum -> RGB), k, roughness | uroughness/vroughness */
     PT_MATERIAL_UBER = 6,      /* materials/uber.rs:63-127      Kd, Ks, Kr, Kt, opacity, eta, roughness | u/v roughness */
-    PT_MATERIAL_SUBSTRATE = 7  /* materials/substrate.rs:34-68  Kd, Ks, uroughness, vroughness */
+    PT_MATERIAL_SUBSTRATE = 7, /* materials/substrate.rs:34-68  Kd, Ks, uroughness, vroughness */
+    PT_MATERIAL_TRANSLUCENT = 8 /* materials/translucent.rs:38-107  Kd, Ks, reflect (in kr / tex_kr), transmit (in kt / tex_kt), roughness,
+                                 * remaproughness; eta is the constant 1.5 ("eta" / "index" are not read, translucent.rs:48) */
 } pt_material_type;
 
 #define PT_ROUGHNESS_UNSET (-1.0f)   /* "uroughness"/"vroughness" not given: Metal and Uber fall back to "roughness" */
@@ -136,14 +138,14 @@ typedef enum {
  * read is ignored.  164 bytes. */
 typedef struct {
     int32_t type;           /* pt_material_type */
-    float kd[3];            /* "Kd": matte 0.5, plastic/uber 0.25, substrate 0.5 */
+    float kd[3];            /* "Kd": matte 0.5, plastic/uber/translucent 0.25, substrate 0.5 */
     float sigma;            /* matte "sigma" degrees, clamped to [0,90]; 0 => Lambertian */
-    float ks[3];            /* "Ks": plastic/uber 0.25, substrate 0.5 */
-    float kr[3];            /* "Kr": mirror 0.9, glass 1, uber 0 */
-    float kt[3];            /* "Kt": glass 1, uber 0 */
+    float ks[3];            /* "Ks": plastic/uber/translucent 0.25, substrate 0.5 */
+    float kr[3];            /* "Kr": mirror 0.9, glass 1, uber 0; translucent: "reflect", 0.5 (translucent.rs:113) */
+    float kt[3];            /* "Kt": glass 1, uber 0; translucent: "transmit", 0.5 (translucent.rs:114) */
     float opacity[3];       /* uber "opacity", default 1 */
     float eta;              /* glass/uber "eta" (alias "index"), default 1.5 */
-    float roughness;        /* plastic 0.1, metal 0.01, uber 0.1 */
+    float roughness;        /* plastic 0.1, metal 0.01, uber 0.1, translucent 0.1 */
     float uroughness;       /* glass 0, substrate 0.1; metal/uber: PT_ROUGHNESS_UNSET unless given */
     float vroughness;
     int32_t remap_roughness;/* "remaproughness", default true */

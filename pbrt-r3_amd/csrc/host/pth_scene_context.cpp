@@ -620,8 +620,14 @@ public:
             set3(m.kd, 0.5f); set3(m.ks, 0.5f); m.uroughness = m.vroughness = 0.1f;
             lookup_rgb(geom, mp, "Kd", m.kd, &m.tex_kd); lookup_rgb(geom, mp, "Ks", m.ks, &m.tex_ks);
             lookup_float(geom, mp, "uroughness", &m.uroughness, &m.tex_uroughness); lookup_float(geom, mp, "vroughness", &m.vroughness, &m.tex_vroughness);
+        } else if (mi.name == "translucent") {                      // translucent.rs:110-127: "reflect" rides in kr, "transmit" in kt; no "eta" / "index"
+            m.type = PT_MATERIAL_TRANSLUCENT;
+            set3(m.kd, 0.25f); set3(m.ks, 0.25f); set3(m.kr, 0.5f); set3(m.kt, 0.5f); m.roughness = 0.1f;
+            lookup_rgb(geom, mp, "Kd", m.kd, &m.tex_kd); lookup_rgb(geom, mp, "Ks", m.ks, &m.tex_ks);
+            lookup_rgb(geom, mp, "reflect", m.kr, &m.tex_kr); lookup_rgb(geom, mp, "transmit", m.kt, &m.tex_kt);
+            lookup_float(geom, mp, "roughness", &m.roughness, &m.tex_roughness);
         } else {
-            fail("Material \"" + mi.name + "\": outside the accelerated path (matte, plastic, mirror, glass, metal, uber, substrate are supported)");
+            fail("Material \"" + mi.name + "\": outside the accelerated path (matte, plastic, mirror, glass, metal, uber, substrate, translucent are supported)");
             return -1;
         }
         {   // "bumpmap": get_float_texture_or_null (texture_params.rs:107-116) -- a named float texture, else a number

@@ -273,7 +273,11 @@ __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
 
 __device__ __noinline__ float globe_pdf(const PtLobe& l, V3 wo, V3 wi) {
     switch (l.kind) {
-        case PT_LOBE_LAMBERT: case PT_LOBE_OREN_NAYAR: return bx_same_hemisphere(wo, wi) ? fabsf(wi.z) * PT_INV_PI : 0.0f;
+        // LambertianTransmission (lambertian.rs:80-86) is PT_LOBE_LAMBERT with the transmission bit: the other hemisphere, and no INV_PI
+        case PT_LOBE_LAMBERT: case PT_LOBE_OREN_NAYAR: {
+            const bool trans = (l.type & PT_BSDF_TRANSMISSION) != 0;
+            return bx_same_hemisphere(wo, wi) != trans ? fabsf(wi.z) * (trans ? 1.0f : PT_INV_PI) : 0.0f;
+        }
         case PT_LOBE_MF_REFL: {
             if (!bx_same_hemisphere(wo, wi)) return 0.0f;
             V3 wh = normalize(wo + wi);
@@ -307,11 +311,11 @@ __device__ __noinline__ bool globe_sample_f(const PtLobe& l, V3 wo, V2 u, V3* f,
     switch (l.kind) {
         case PT_LOBE_LAMBERT: case PT_LOBE_OREN_NAYAR: {
             V3 wi = cosine_sample_hemisphere(u);
-            if (wo.z < 0.0f) wi.z *= -1.0f;
+            if ((l.type & PT_BSDF_TRANSMISSION) ? wo.z > 0.0f : wo.z < 0.0f) wi.z *= -1.0f;      // lambertian.rs:68-71: transmission leaves on the far side
             *pdf = globe_pdf(l, wo, wi);
             *f = globe_f(l, wo, wi);
             *wi_out = wi;
-            return true;
+            return true;                    // (a pdf that is not positive is turned away by the caller, bsdf.rs:133-135)
         }
         case PT_LOBE_SPEC_REFL: {
             V3 wi = mk3(-wo.x, -wo.y, wo.z);

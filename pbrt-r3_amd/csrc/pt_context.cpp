@@ -597,7 +597,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         if (d->meshes[m].area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "area light index out of range");
 
         int32_t mi = d->meshes[m].material;
-        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_SUBSTRATE))
+        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_TRANSLUCENT))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
     }
     for (uint32_t i = 0; i < d->n_materials; i++) {
@@ -630,7 +630,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         const pt_sphere& sp = d->spheres[i];
         if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere material index out of range");
         if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere area light index out of range");
-        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_SUBSTRATE))
+        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_TRANSLUCENT))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
         if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere before_triangle exceeds n_triangles");
         if (!(sp.radius > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere radius must be positive");

@@ -103,6 +103,7 @@ struct PtTriInfo {
 // the same BxDFs at every hit, so the host evaluates it once per material (pt_context.cpp build_lobes).
 enum { PT_LOBE_LAMBERT = 0, PT_LOBE_OREN_NAYAR = 1, PT_LOBE_SPEC_REFL = 2, PT_LOBE_SPEC_TRANS = 3, PT_LOBE_FRESNEL_SPEC = 4,
        PT_LOBE_MF_REFL = 5, PT_LOBE_MF_TRANS = 6, PT_LOBE_FRESNEL_BLEND = 7 };
+// (LambertianTransmission, lambertian.rs:49-99, is PT_LOBE_LAMBERT whose `type` carries BSDF_TRANSMISSION instead of BSDF_REFLECTION: pt_bxdf.h)
 enum { PT_FR_NOOP = 0, PT_FR_DIELECTRIC = 1, PT_FR_CONDUCTOR = 2 };
 struct PtLobe {                  // 80 bytes
     uint32_t kind;               // PT_LOBE_*
@@ -125,7 +126,7 @@ struct PtMaterial {
     float sigma;
     float oren_a, oren_b;        // OrenNayar::new (oren_nayar.rs:16-23), precomputed on the host
     uint32_t n_lobes;
-    uint32_t has_bsdf;           // 0: compute_scattering_functions leaves bsdf = None (glass with Kr = Kt = 0)
+    uint32_t has_bsdf;           // 0: compute_scattering_functions leaves bsdf = None (glass with Kr = Kt = 0, translucent with reflect = transmit = 0)
     uint32_t nonspecular;        // num_components(BSDF_ALL & !BSDF_SPECULAR)
     float bsdf_eta;              // BSDF::eta
     uint32_t sort_bin;           // shade-queue bin: [0,128) Matte materials, [128,256) the others

@@ -144,6 +144,33 @@ PT_HD inline void build_lobes(const pt_material& in, float a_r, float a_u, float
             }
             break;
         }
+        case PT_MATERIAL_TRANSLUCENT: {                 // translucent.rs:38-107 ("reflect" in kr, "transmit" in kt; eta is the constant 1.5)
+            float r[3], t[3], k[3], c[3];
+            cz(in.kr, r); cz(in.kt, t);
+            if (black(r) && black(t)) { m.has_bsdf = 0; break; }           // returns before si.bsdf is set (:56-58)
+            m.bsdf_eta = 1.5f;
+            cz(in.kd, k);
+            if (!black(k)) {
+                if (!black(r)) { mul(r, k, c); push_lobe(m, PT_LOBE_LAMBERT, kRefl | kDiffuse, c); }
+                if (!black(t)) { mul(t, k, c); push_lobe(m, PT_LOBE_LAMBERT, kTrans | kDiffuse, c); }        // LambertianTransmission: the kTrans bit selects it
+            }
+            cz(in.ks, k);
+            if (!black(k)) {
+                if (!black(r)) {
+                    mul(r, k, c);
+                    PtLobe* l = push_lobe(m, PT_LOBE_MF_REFL, kRefl | kGlossy, c);
+                    set_distribution(l, a_r, a_r);
+                    l->fresnel = PT_FR_DIELECTRIC; l->fr_eta_i = 1.0f; l->fr_eta_t = 1.5f;
+                }
+                if (!black(t)) {
+                    mul(t, k, c);
+                    PtLobe* l = push_lobe(m, PT_LOBE_MF_TRANS, kTrans | kGlossy, c);
+                    set_distribution(l, a_r, a_r);
+                    l->eta_a = 1.0f; l->eta_b = 1.5f;
+                }
+            }
+            break;
+        }
         default: break;
     }
     for (uint32_t i = 0; i < m.n_lobes; i++) {

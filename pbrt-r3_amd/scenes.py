@@ -533,6 +533,18 @@ class SceneBuilder:
         self.cur_material = self._add_material(capi.PT_MATERIAL_SUBSTRATE, Kd, ks=Ks, uroughness=self._ft(uroughness),
                                                vroughness=self._ft(vroughness), remap_roughness=int(remaproughness))
 
+    def material_translucent(self, Kd=(0.25,) * 3, Ks=(0.25,) * 3, reflect=(0.5,) * 3, transmit=(0.5,) * 3, roughness=0.1, remaproughness=True,
+                             bumpmap=None):
+        """materials/translucent.rs:110-127: "reflect" travels in kr, "transmit" in kt; eta is the constant 1.5.  A parameter behind a
+        texture keeps the reference's default as its (unused) constant, as the front end leaves it."""
+        given = {"kd": Kd, "ks": Ks, "kr": reflect, "kt": transmit, "roughness": self._ft(roughness)}
+        default = {"kd": (0.25,) * 3, "ks": (0.25,) * 3, "kr": (0.5,) * 3, "kt": (0.5,) * 3, "roughness": 0.1}
+        const = {k: (default[k] if isinstance(v, Tex) else v) for k, v in given.items()}
+        self.cur_material = self._add_material(capi.PT_MATERIAL_TRANSLUCENT, const.pop("kd"), remap_roughness=int(remaproughness), bump=bumpmap, **const)
+        for k, v in given.items():
+            if isinstance(v, Tex):
+                setattr(self.materials[self.cur_material], "tex_" + k, v.index + 1)
+
     def material_none(self):
         self.cur_material = -1
 
