@@ -2146,7 +2146,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
 #ifdef PT_PROFILE_PHASES
     {   // diagnostic build (tools/tune_trace.sh "prof:-DPT_PROFILE_PHASES:3"): where a traversal wave's clocks go
-        unsigned long long pr[16];
+        unsigned long long pr[24];
         PT_HIP(hipMemcpy(pr, ctx->d_spill.p, sizeof(pr), hipMemcpyDeviceToHost));
         PT_HIP(hipMemsetAsync(ctx->d_spill.p, 0, sizeof(pr), ctx->stream)); PT_HIP(hipStreamSynchronize(ctx->stream));
         const double tot = (double)pr[11];
@@ -2156,6 +2156,13 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                      100.0 * pr[7] / tot, pr[8] ? (double)(pr[5] + pr[6] + pr[7]) / (double)pr[8] : 0.0, pr[13], 100.0 * pr[12] / tot, 100.0 * pr[10] / tot);
         std::fprintf(stderr, "[phases] service in parts: prefetch state machine %.1f%%, retiring + handing out rays %.1f%% (%.0f + %.0f clocks per iteration)\n", 100.0 * pr[14] / tot,
                      100.0 * pr[15] / tot, (double)pr[14] / (double)(pr[3] + pr[8] + pr[13] + 1), (double)pr[15] / (double)(pr[3] + pr[8] + pr[13] + 1));
+        // The counter's own cost: an empty timed section (two reads back to back, every 64th iteration) is taken off each section, once per iteration.
+        const double iters = (double)pr[16] + 1.0, empty = pr[19] ? (double)pr[20] / (double)pr[19] : 0.0, n_ho = (double)pr[17], n_no = iters - n_ho;
+        std::fprintf(stderr, "[phases] loop iterations %llu (%.2f node rounds per pass with one), empty timed section %.0f clocks; less that: prefetch state machine %.0f clocks per iteration = %.1f%%, "
+                     "retiring + handing out %.0f = %.1f%%; iterations with a hand-out %.1f%%: %.0f clocks each, without: %.0f clocks each = %.1f%% of wave clocks\n",
+                     pr[16], (double)pr[3] / (double)(pr[16] - pr[8] - pr[13] + 1), empty, (double)pr[14] / iters - empty, 100.0 * ((double)pr[14] - empty * iters) / tot,
+                     (double)pr[15] / iters - empty, 100.0 * ((double)pr[15] - empty * iters) / tot, 100.0 * n_ho / iters, n_ho > 0 ? (double)pr[18] / n_ho - empty : 0.0,
+                     n_no > 0 ? ((double)pr[15] - (double)pr[18]) / n_no - empty : 0.0, 100.0 * ((double)pr[15] - (double)pr[18] - empty * n_no) / tot);
     }
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go

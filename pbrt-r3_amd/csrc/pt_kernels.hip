@@ -1326,6 +1326,9 @@ PT_DEV uint32_t wave_ticket(uint32_t* ticket) {
 #define PT_RETIRE_AT_HANDOUT 1       // 1 (pooled-leaf kernels): a finished ray's result is stored in the block that hands out new rays (and in every iteration of the drain)
                                      // instead of in the iteration it finishes in: the three store branches ran for one or two lanes in most iterations
 #endif
+#ifndef PT_PF_BYPASS
+#define PT_PF_BYPASS 1               // 1 (k_trace, k_trace_sph_dist): a complete reservation (stage 3) branches past the prefetch state machine instead of falling through its if / else-if chain
+#endif
 #ifndef PT_SPH_LANES_MIN
 #define PT_SPH_LANES_MIN 8           // scenes with spheres: a sphere round once this many lanes are parked on a leaf that holds a sphere (2 / 4 / 6 / 8 / 10 / 16 / 24 / 32:
                                      // 46.9 / 45.2 / 44.6 / 44.4 / 44.5 / 44.9 / 48.6 / 54.2 ms per launch, RT1M lit by a sphere, 64 spp)
@@ -1409,13 +1412,21 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     float4 pf_o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pf_d = pf_o;
 #ifdef PT_PROFILE_PHASES
     // pooled-leaf kernels: 0 node issue clk, 1 node wait clk, 2 node finish clk, 3 node rounds, 4 node lanes, 5 leaf issue clk, 6 leaf wait clk,
-    // 7 leaf finish clk, 8 leaf rounds, 9 leaf items, 10 service clk, 11 wave total clk, 12 general-visit clk, 13 general-visit rounds
-    unsigned long long prof[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // 7 leaf finish clk, 8 leaf rounds, 9 leaf items, 10 service clk, 11 wave total clk, 12 general-visit clk, 13 general-visit rounds, 14 prefetch state machine clk,
+    // 15 retire + hand-out clk, 16 loop iterations, 17 iterations with a hand-out, 18 retire + hand-out clk of those, 19 empty timed sections, 20 their clk (the counter's own cost)
+    unsigned long long prof[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long prof_t0 = __builtin_readcyclecounter();
 #endif
     for (;;) {
 #ifdef PT_PROFILE_PHASES
         long long pt_iter = __builtin_readcyclecounter();
+        bool pt_handout = false;
+        if ((prof[16]++ & 63ull) == 0ull) {          // calibration: two counter reads back to back, what every timed section above and below includes
+            const long long e0 = __builtin_readcyclecounter();
+            const long long e1 = __builtin_readcyclecounter();
+            prof[19] += 1; prof[20] += (unsigned long long)(e1 - e0);
+            pt_iter = __builtin_readcyclecounter();
+        }
 #endif
         // ---- ray prefetch pipeline.  A refill used to be three dependent round trips (ticket atomic, path id, ray
         // record) with the whole wave waiting; now the wave keeps the next 64 rays in registers, one per lane, and
@@ -1423,7 +1434,15 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         //   0 -> 1  reserve 64 items (atomic)        1 -> 2  load the path ids        2 -> 3  load origin / direction
         // Idle lanes then take their ray from the reservation lane by ds_bpermute, so refills are cheap enough to
         // happen as soon as PT_REFILL_MIN lanes are free.
-        if (pf_stage == 0) {
+        // A complete reservation (stage 3, nine iterations in ten) takes one scalar branch past the state machine.  As one if / else-if chain the compiler merges
+        // the reservation's registers (pf_o, pf_d, pf_p, pf_kind) in a block every iteration runs through: fourteen register copies and two waits for all
+        // loads, advanced or not.  The empty asm keeps the compiler from folding this test back into the chain's own.
+        // (k_trace and k_trace_sph_dist, where it was measured to gain; k_trace_far's one run on 16 M sparse triangles lost 1 %: DESIGN.md section 9.)
+        constexpr bool PF_BYPASS = DIST && TOUCH == 0 && PT_PF_BYPASS;
+        int pf_gate = pf_stage;
+        if constexpr (PF_BYPASS) asm volatile("" : "+s"(pf_gate));
+        if (PF_BYPASS && pf_gate == 3) {
+        } else if (pf_stage == 0) {
             if (more) {
                 if (lane == 0) pf_raw = atomicAdd(&Q.counts[PT_Q_SEG_TICKET0 + 32u * seg], 64u);
                 pf_stage = 1;
@@ -1485,6 +1504,9 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             const unsigned long long idle = LATE_RETIRE ? __ballot(kind == 0 || ray_done(r)) : __ballot(kind == 0);
             const uint32_t n_idle = (uint32_t)__popcll(idle);
             if (pf_stage == 3 && (n_idle >= PT_REFILL_MIN || idle == ~0ull || (!more && n_idle != 0))) {
+#ifdef PT_PROFILE_PHASES
+                pt_handout = true;
+#endif
                 if constexpr (LATE_RETIRE) { PT_RETIRE() }
                 const uint32_t take = min(n_idle, pf_count - pf_used);
                 const uint32_t rank = (uint32_t)__popcll(idle & below);
@@ -1506,7 +1528,11 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         }
 #undef PT_RETIRE
 #ifdef PT_PROFILE_PHASES
-        prof[15] += (unsigned long long)(__builtin_readcyclecounter() - pt_pf);       // retiring and handing out rays
+        {
+            const unsigned long long dt = (unsigned long long)(__builtin_readcyclecounter() - pt_pf);       // retiring and handing out rays
+            prof[15] += dt;
+            if (pt_handout) { prof[17] += 1; prof[18] += dt; }
+        }
 #endif
         if ((LATE_RETIRE ? __ballot(kind != 0 && !ray_done(r)) : __ballot(kind != 0)) == 0) {      // nothing to traverse (late retire: with the queue dry everything finished was stored above)
             if (!more && pf_stage == 0) break;
@@ -1832,7 +1858,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     }
 #ifdef PT_PROFILE_PHASES
     prof[11] = (unsigned long long)(__builtin_readcyclecounter() - prof_t0);
-    if (lane == 0) for (int i = 0; i < 16; i++) atomicAdd(reinterpret_cast<unsigned long long*>(spill) + i, prof[i]);   // diagnostic build only: the buffer's diagnostic words
+    if (lane == 0) for (int i = 0; i < 24; i++) atomicAdd(reinterpret_cast<unsigned long long*>(spill) + i, prof[i]);   // diagnostic build only: the buffer's diagnostic words
 #endif
     if (c.overflow) atomicOr(err, 1u);
     flush_counters(cnt, s_cnt, regular, shadow, c.n_nodes, c.n_tris);
