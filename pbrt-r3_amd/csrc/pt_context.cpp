@@ -2400,7 +2400,7 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
     hipEvent_t a = get_event(ctx, 0), b = get_event(ctx, 1);
     PT_HIP(hipEventRecord(a, ctx->stream));
     PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, ctx->sc, P, Q, ctx->d_counters.as<PtCounters>(), ctx->d_spill.as<uint32_t>(), ctx->spill_depth,
-                     ctx->d_err.as<uint32_t>(), 0, ctx->scene_alpha ? 1 : 0));
+                     ctx->d_err.as<uint32_t>(), ctx->trace_far > 0 ? 1 : 0, ctx->scene_alpha ? 1 : 0));      // PBRTGPU_TRACE_FAR=1 forces k_trace_far here too (no trial: the caller's rays are not a bounce)
     PT_HIP(hipEventRecord(b, ctx->stream));
     PT_HIP(ptk_wavefront_results(ctx->stream, ctx->grid_wide, ctx->sc, P, n, d_kind.as<uint8_t>(), d_out.as<pt_hit>(), d_occ.as<uint8_t>()));
     PT_HIP(hipMemsetAsync(Q.counts, 0, PT_COUNTS_WORDS * 4, ctx->stream));
