@@ -2132,20 +2132,9 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
         return ctx->fail(PT_ERR_UNSUPPORTED, "a path asked the Halton sampler for more than its 1000 dimensions: the reference panics there (halton.rs:103-107); "
                                              "lower maxdepth or use the Sobol' sampler");
     }
-#ifdef PT_STACK_HIST
-    {   // diagnostic build: histogram of the traversal stack depth at node visits (k_trace's lean visit)
-        uint32_t hist[64];
-        PT_HIP(hipMemcpy(hist, ctx->d_spill.as<uint32_t>() + 1024, sizeof(hist), hipMemcpyDeviceToHost));
-        PT_HIP(hipMemsetAsync(ctx->d_spill.as<uint32_t>() + 1024, 0, sizeof(hist), ctx->stream)); PT_HIP(hipStreamSynchronize(ctx->stream));
-        double tot = 0, cum = 0;
-        for (uint32_t v : hist) tot += v;
-        std::fprintf(stderr, "[stack depth at node visits]");
-        for (int k = 0; k < 64; k++) { cum += hist[k]; if (hist[k]) std::fprintf(stderr, " %d:%.4f", k, cum / tot); }
-        std::fprintf(stderr, "\n");
-    }
-#endif
 #ifdef PT_PROFILE_PHASES
-    {   // diagnostic build (tools/tune_trace.sh "prof:-DPT_PROFILE_PHASES:3"): where a traversal wave's clocks go
+    {   // diagnostic build (tools/tune_trace.sh "prof:-DPT_PROFILE_PHASES:3"): where a traversal wave's clocks go (the slots: PhaseProf in pt_kernels.hip;
+        // a node round's "issue" and "wait" were the staged node fetch's halves and read 0: the slots keep their numbers so that profiles/r05, r06 stay comparable)
         unsigned long long pr[24];
         PT_HIP(hipMemcpy(pr, ctx->d_spill.p, sizeof(pr), hipMemcpyDeviceToHost));
         PT_HIP(hipMemsetAsync(ctx->d_spill.p, 0, sizeof(pr), ctx->stream)); PT_HIP(hipStreamSynchronize(ctx->stream));

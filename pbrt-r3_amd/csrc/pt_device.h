@@ -18,12 +18,6 @@
 #endif
 #define PT_TBLOCK (PT_TRACE_WIDE ? 1024 : PT_BLOCK)      // threads per block of the pooled-leaf traversal kernels
 #define PT_SLOT (PT_TBLOCK * 4u)   // bytes between two entries of a lane's LDS traversal stack ([entry][lane] layout; pooled-leaf kernels)
-// PT_NODE_STAGED 1: the pooled-leaf traversal kernels fetch a round's nodes cooperatively through LDS (global_load_lds_dwordx4;
-// a quarter of the L1 requests, but 49 KB of LDS per block = three blocks per CU and a longer round); 0: every lane loads its
-// own node (four blocks per CU).  Measured on RT1M: 0 is the faster one.
-#ifndef PT_NODE_STAGED
-#define PT_NODE_STAGED 0
-#endif
 // PT_TOP_NODES > 0: the pooled-leaf traversal kernels keep the first PT_TOP_NODES nodes of the world tree (the upload numbers the top
 // of the tree breadth-first, so these are its top levels: 85 = levels 0..3) in LDS, 112 bytes each, and visits to them read LDS instead
 // of going through the vector L1, whose request rate bounds the kernel.  Paid for with 8 of the 32 stack slots.
@@ -36,9 +30,7 @@
 #endif
 #define PT_TOP_BFS_NODES 1365u   // what the upload renumbers breadth-first (levels 0..5), whatever PT_TOP_NODES the kernels were built with
 // LDS stack slots per lane of the pooled-leaf traversal kernels (slot 0 holds a sentinel; deeper entries spill to HBM)
-#if PT_NODE_STAGED
-#define PT_FS_SLOTS (PT_LDS_STACK < 16 ? PT_LDS_STACK : 16)
-#elif PT_TOP_NODES > 0
+#if PT_TOP_NODES > 0
 #define PT_FS_SLOTS (PT_LDS_STACK < 24 ? PT_LDS_STACK : 24)
 #else
 #define PT_FS_SLOTS PT_LDS_STACK

@@ -42,9 +42,6 @@
 #ifndef PT_TEX_NOUNROLL
 #define PT_TEX_NOUNROLL 0
 #endif
-#ifndef PT_TOUCH_VARIANT
-#define PT_TOUCH_VARIANT 3       // k_trace_far built with PT_NODE_COOP 0 (its first form): which pushed children node_step_lean touches (see there)
-#endif
 
 // ============================================================ Sobol' sampler
 PT_DEV uint64_t sobol_interval_to_index(const PtSobol& sb, uint64_t frame, int32_t px, int32_t py) {
@@ -451,11 +448,10 @@ struct TravCtx {
     uint32_t lane_base;      // pooled-leaf kernels: LDS byte address of this lane's slot 0 (see FsStack)
     uint32_t top_lds, top_bytes;   // pooled-leaf kernels: LDS byte address of the cached top of the tree; 128 x the number of nodes cached
     uint32_t n_nodes_lds;          // node visits served from that copy
-    // pooled-leaf kernels, staged node fetch (node_round_staged): LDS addresses
-    uint32_t stage_wave;     // this wave's 8 KB staging area (wave-uniform)
-    uint32_t stage_own;      // this lane's staged node: stage_wave + (lane >> 3) * 1024 + (lane & 7) * 128
-    uint32_t idx_pub, idx_ld;// where the lane publishes its node index / reads the eight indices it loads for
-    PT_DEV uint32_t stage_chunk(uint32_t q) const { return stage_own + ((q ^ (threadIdx.x & 7u)) << 4); }
+    // Not read any more (they addressed the LDS areas of a cooperative node fetch that has left the source).  They stay, with their zeroes in trace_body,
+    // because the context lives in scratch memory where it is passed to a called function (instance_rec_test): four words fewer move those kernels' frames,
+    // and the change that retired the fetch was held to identical device code (profiles/r07_switch_retirement_isa.txt).
+    uint32_t stage_wave, stage_own, idx_pub, idx_ld;
 };
 // The stack lives in LDS (entries 0..PT_LDS_STACK-1, then the HBM spill area); `sp` is its depth and `top` a register
 // copy of entry sp-1 (PT_EMPTY_REF when empty), so a pop has its reference at once and the read that refreshes `top`
@@ -601,18 +597,12 @@ PT_DEV void ray_begin_fs(const PtScene& sc, LaneRay& r, const TravCtx& c, V3 o, 
     ray_begin(sc, r, o, d, t_max);
     r.sa = c.lane_base + (r.top != PT_EMPTY_REF ? PT_SLOT : 0u);
     if (r.idir.x == 0.0f || r.idir.y == 0.0f || r.idir.z == 0.0f) r.sbits |= 8u;      // infinite direction component: 0 * inf in the slabs
-    // rows of a node: chunks 0..2 = bmin x / y / z, 3..5 = bmax x / y / z; near / far by the direction signs; as LDS addresses of
-    // this lane's staged node (chunk q sits at q ^ own_i, see node_round_staged)
+    // rows of a node: 16-byte chunks 0..2 = bmin x / y / z, 3..5 = bmax x / y / z; near / far by the direction signs, as byte offsets
+    // inside the node (in HBM, or in the LDS copy of the top of the tree: same layout)
     const uint32_t ox = (r.sbits & 1u) ? 3u : 0u, oy = (r.sbits & 2u) ? 3u : 0u, oz = (r.sbits & 4u) ? 3u : 0u;
-#if PT_NODE_STAGED
-    r.o_nx = c.stage_chunk(ox); r.o_fx = c.stage_chunk(3u - ox);
-    r.o_ny = c.stage_chunk(1u + oy); r.o_fy = c.stage_chunk(4u - oy);
-    r.o_nz = c.stage_chunk(2u + oz); r.o_fz = c.stage_chunk(5u - oz);
-#else       // byte offsets of the rows inside the node in HBM
     r.o_nx = ox << 4; r.o_fx = (3u - ox) << 4;
     r.o_ny = (1u + oy) << 4; r.o_fy = (4u - oy) << 4;
     r.o_nz = (2u + oz) << 4; r.o_fz = (5u - oz) << 4;
-#endif
     const uint32_t oct = r.sbits & 7u;
     r.m_t = 1u << oct; r.m_l = 256u << oct; r.m_r = 65536u << oct;
     r.sa_limit = (r.sbits & 8u) ? 0u : c.lane_base + (PT_FS_SLOTS - 3u) * PT_SLOT;
@@ -792,9 +782,6 @@ PT_DEV void ray_step(const PtScene& sc, LaneRay& r, bool any_hit, TravCtx& c) {
 // tests, t_max updates and counters are the blocking form's: a leaf cut in two behaves like the whole one because nothing reads the world-space slab
 // interval while the ray is inside the object (a hit among the leaf's earlier records shrinks it before it is saved, a hit inside the object after it is
 // restored, the leaf's later records at their own end).  Objects hold no instances (scene_context.rs:1352-1357), so one level is all there is.
-#ifndef PT_INST_LEAF_PREFETCH
-#define PT_INST_LEAF_PREFETCH 0     // the next record asked for before this one is tested: 172 registers (two waves per SIMD) or, held to 168, no faster (637 / 1 060 / 432 against 628 / 1 184 / 440 Mrays/s on three instanced scenes)
-#endif
 #define PT_INST_EXIT_REF (PT_LEAF_BIT | PT_LEAF_FIRST_MASK)          // the marker: a leaf reference no scene can hold (fewer than 2^26 - 16 primitives)
 PT_DEV void ray_set_direction_state(LaneRay& r, V3 o, V3 d) {        // what ray_begin derives from (o, d), without touching hit, t_max or stack
     r.o = o; r.d = d;
@@ -809,9 +796,6 @@ PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, Trav
     bool leaf_hit = false;
     TriVerts t0 = load_tri(sc.tris, rec);
     for (;; rec++) {
-#if PT_INST_LEAF_PREFETCH
-        const TriVerts t_next = load_tri(sc.tris, rec + 1u);          // on its way while this record is tested (the array is padded by one record)
-#endif
         TriHit h;
         c.n_tris++;
         bool hit = false;
@@ -849,11 +833,7 @@ PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, Trav
             r.ray_tmax = h.t;
         }
         if (last) break;
-#if PT_INST_LEAF_PREFETCH
-        t0 = t_next;
-#else
         t0 = load_tri(sc.tris, rec + 1u);
-#endif
     }
     if (leaf_hit) r.tmax = r.ray_tmax;
 }
@@ -973,83 +953,14 @@ PT_DEV void fs_push4_exec(uint32_t& sa, uint32_t& top, uint32_t c0, uint32_t c1,
         : [e0] "s"(e0), [e1] "s"(e1), [e2] "s"(e2), [e3] "s"(e3), [c0] "v"(c0), [c1] "v"(c1), [c2] "v"(c2), [c3] "v"(c3), [slot] "s"(PT_SLOT)
         : "memory");
 }
-// One node round of the whole wave.  The kernel is bound by the vector L1's request rate, not by arithmetic: with one ray per lane
-// every lane's 128-byte node is a line of its own, and the eight loads of the first version were 8 x 64 tag look-ups per round
-// (tools/ubench/node_fetch.hip: 77 G node visits/s is all the chip can do that way, k_trace sat at 61 G beside its triangle
-// loads).  Here the wave fetches the up-to-64 nodes TOGETHER: in load j, lane l fetches 16-byte chunk of the node of lane
-// 8 j + (l >> 3) -- eight neighbouring lanes cover one whole line -- straight into LDS (global_load_lds_dwordx4, no VGPR round
-// trip; one instruction lands 1 KiB = 8 nodes), and each owner then reads its rows from LDS.  164-171 G node visits/s in the
-// micro-benchmark.  Chunk c of sub-node i of a piece is stored at position c ^ i (the swizzle is applied to the SOURCE address,
-// the LDS image of an LDS-DMA is lane-linear), so the eight owners of a piece read any one row from eight different bank groups.
-//   w_node  this lane has a node to visit (its reference is r.top)
-typedef __attribute__((address_space(3))) void* pt_lds_void;
-typedef const __attribute__((address_space(1))) void* pt_global_cvoid;
+// 16-byte LDS reads (the rows of a top node, lean and pairwise visit)
 typedef float pt_v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t pt_v4u __attribute__((ext_vector_type(4)));
 PT_DEV float4 lds_load4(uint32_t a) { const pt_v4f v = *(__attribute__((address_space(3))) const pt_v4f*)(size_t)a; return make_float4(v.x, v.y, v.z, v.w); }
 PT_DEV uint4 lds_load4u(uint32_t a) { const pt_v4u v = *(__attribute__((address_space(3))) const pt_v4u*)(size_t)a; return make_uint4(v.x, v.y, v.z, v.w); }
-// issue half: pops, publishes and starts the LDS-DMA fetches; returns the entry below the popped one (the fall-back `top`)
-PT_DEV uint32_t node_round_issue(const PtScene& sc, LaneRay& r, TravCtx& c, bool w_node) {
-    // owners: pop, publish the node index (transposed: the eight indices a loader lane needs are contiguous)
-    uint32_t ref = PT_EMPTY_REF, top = PT_EMPTY_REF;
-    if (w_node) {
-#ifdef PT_STACK_HIST
-        atomicAdd(c.spill - ((size_t)blockIdx.x * PT_BLOCK + threadIdx.x) - PT_DIAG_WORDS + 1024u + min(fs_slot(c, r.sa), 63u), 1u);   // diagnostic build: stack depth at each node visit
-#endif
-        ref = r.top;
-        r.sa -= PT_SLOT;
-        top = lds_load(r.sa);                 // the entry below (slot 0: PT_EMPTY_REF)
-        c.n_nodes++;
-    }
-    lds_store(c.idx_pub, ref);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    {   // loaders
-        const uint4 ia = lds_load4u(c.idx_ld), ib = lds_load4u(c.idx_ld + 16u);
-        const uint32_t ids[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
-        const uint32_t lane = threadIdx.x & 63u;
-        const uint32_t coff = ((lane & 7u) ^ (lane >> 3)) << 4;
-        const char* nb = reinterpret_cast<const char*>(sc.nodes);
-        const uint32_t piece0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c.stage_wave);
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++)
-            if (ids[j] != PT_EMPTY_REF)
-                __builtin_amdgcn_global_load_lds((pt_global_cvoid)(nb + ((ids[j] << 7) + coff)), (pt_lds_void)(size_t)(piece0 + j * 1024u), 16, 0, 0);
-    }
-    return top;
-}
-// finish half, after `s_waitcnt vmcnt(0)`: rows from LDS, four slab tests, ordered EXEC-predicated pushes
-PT_DEV void node_round_finish(LaneRay& r, TravCtx& c, bool w_node, uint32_t top) {
-    if (w_node) {
-        const float4 nx = lds_load4(r.o_nx), fx = lds_load4(r.o_fx), ny = lds_load4(r.o_ny), fy = lds_load4(r.o_fy), nz = lds_load4(r.o_nz), fz = lds_load4(r.o_fz);
-        const uint4 ch = lds_load4u(c.stage_chunk(6u));
-        const uint32_t lut = lds_load(c.stage_chunk(7u) + 4u);
-        const float ox = r.o.x, oy = r.o.y, oz = r.o.z, ix = r.idir.x, iy = r.idir.y, iz = r.idir.z;
-#define PT_SLAB(C) (v_min3(v_min(r.tmax, (fx.C - ox) * ix), (fy.C - oy) * iy, (fz.C - oz) * iz) >= v_max3(v_max(r.tmin, (nx.C - ox) * ix), (ny.C - oy) * iy, (nz.C - oz) * iz))
-        const bool h0 = PT_SLAB(x), h1 = PT_SLAB(y), h2 = PT_SLAB(z), h3 = PT_SLAB(w);
-#undef PT_SLAB
-        // ORDER_TABLE in closed form: pops visit {0,1} before {2,3} iff the ray is non-negative along axis_top, 0 before 1 iff along
-        // axis_left, 2 before 3 iff along axis_right; pushes run in the reverse of the visit order
-        const bool T = (lut & r.m_t) != 0u, L = (lut & r.m_l) != 0u, R = (lut & r.m_r) != 0u;
-        const uint32_t l0 = L ? ch.x : ch.y, l1 = L ? ch.y : ch.x, r0 = R ? ch.z : ch.w, r1 = R ? ch.w : ch.z;
-        const uint32_t c0 = T ? l0 : r0, c1 = T ? l1 : r1, c2 = T ? r0 : l0, c3 = T ? r1 : l1;
-        // the same selects on the hit conditions, as 64-bit lane masks on the scalar unit (a ? x : y == y ^ (a & (x ^ y))); lanes
-        // outside EXEC are zero in every v_cmp result, so each push condition lies inside EXEC
-        const unsigned long long H0 = __ballot(h0), H1 = __ballot(h1), H2 = __ballot(h2), H3 = __ballot(h3), Tm = __ballot(T), Lm = __ballot(L), Rm = __ballot(R);
-        const unsigned long long yl = Lm & (H0 ^ H1), el0 = H1 ^ yl, el1 = H0 ^ yl;
-        const unsigned long long yr = Rm & (H2 ^ H3), er0 = H3 ^ yr, er1 = H2 ^ yr;
-        const unsigned long long y0 = Tm & (el0 ^ er0), e0 = er0 ^ y0, e2 = el0 ^ y0;
-        const unsigned long long y1 = Tm & (el1 ^ er1), e1 = er1 ^ y1, e3 = el1 ^ y1;
-        fs_push4_exec(r.sa, top, c0, c1, c2, c3, e0, e1, e2, e3);
-        r.top = top;
-    }
-}
-
-// The lean visit with per-lane loads (PT_NODE_STAGED == 0): every lane fetches its own node, SGPR base + 32-bit offset with the
-// sign-dependent row offsets hoisted per ray.  Keeps the 32-slot LDS stack and four blocks per CU; bound by the vector L1's
-// request rate (eight requests per lane and visit).
-template <int TOUCH>
+// The lean visit (k_trace, k_trace_sph_dist): every lane fetches its own node, SGPR base + 32-bit offset with the sign-dependent row
+// offsets hoisted per ray; a visit to one of the top nodes reads the block's LDS copy instead.  Bound by the vector L1's request rate
+// (seven requests per lane and visit).
 PT_DEV void node_step_lean(const PtScene& sc, LaneRay& r, TravCtx& c) {
     const uint32_t ref = r.top;
     r.sa -= PT_SLOT;
@@ -1095,45 +1006,8 @@ PT_DEV void node_step_lean(const PtScene& sc, LaneRay& r, TravCtx& c) {
     const unsigned long long y1 = Tm & (el1 ^ er1), e1 = er1 ^ y1, e3 = el1 ^ y1;
     fs_push4_exec(r.sa, top, c0, c1, c2, c3, e0, e1, e2, e3);
     r.top = top;
-    if constexpr (TOUCH != 0) {
-        // k_trace_far's first form (PT_NODE_COOP 0; superseded by node_step_coop below, which gains more on the same scenes).  Every reference pushed here IS
-        // visited later -- the reference's stack holds no distances --, so a pushed LEAF that is not the next visit has its first record's line
-        // touched now: one 4-byte load into a register nobody reads.  A leaf round waits for the slowest of up to 64 record fetches, each the
-        // first access to a line of its own; touched at push time the line is on its way (or in L2) when the round comes.  Loads return in
-        // order, so the touch is paid for by this lane's next fetch waiting behind it -- which is why it loses wherever the records hit the
-        // caches anyway (RT1M -20 %, a 3.5 M-triangle scene -7 %) and is not the default.  Measured variants (16 M sparse triangles, 130 node visits
-        // per ray, Mrays/s at 64 spp; TOUCH = the variant number): none 361; 3 not-next leaves 421; 2 not-next interior nodes 356; 1 both 353;
-        // 4 every pushed leaf, the next visit too 352; 5 = 4 + the second line of leaves of three records and more 284.
-        unsigned long long p0, p1, p2, p3 = 0ull;
-        if (TOUCH >= 4) { p0 = e0; p1 = e1; p2 = e2; p3 = e3; }
-        else { p0 = e0 & (e1 | e2 | e3); p1 = e1 & (e2 | e3); p2 = e2 & e3; }
-        const unsigned long long me = 1ull << (threadIdx.x & 63u);
-        const char* tb = reinterpret_cast<const char*>(sc.tris);
-        auto touch = [&](uint32_t cref) {
-            if (TOUCH == 2 && (cref & PT_LEAF_BIT)) return;
-            if (TOUCH >= 3 && !(cref & PT_LEAF_BIT)) return;
-            const char* a = (cref & PT_LEAF_BIT) ? tb + (size_t)(cref & PT_LEAF_FIRST_MASK) * 48u : nb + (size_t)(cref << 7);
-            uint32_t v = *reinterpret_cast<const uint32_t*>(a);
-            asm volatile("" :: "v"(v));
-            if (TOUCH == 5 && ((cref >> PT_LEAF_COUNT_SHIFT) & 7u) >= 2u) {
-                uint32_t w = *reinterpret_cast<const uint32_t*>(a + 128);
-                asm volatile("" :: "v"(w));
-            }
-        };
-        if (p0 & me) touch(c0);
-        if (p1 & me) touch(c1);
-        if (p2 & me) touch(c2);
-        if (p3 & me) touch(c3);
-    }
 }
 
-#ifndef PT_NODE_COOP
-#define PT_NODE_COOP 1           // k_trace_far fetches nodes pairwise (node_step_coop); 2 = k_trace too (experiment)
-#endif
-#ifndef PT_COOP_TOUCH
-#define PT_COOP_TOUCH 0          // ... and touches pushed leaves as node_step_lean<TOUCH> does (slower with the pairwise fetch: 16 M sparse triangles 440 vs 485 Mrays/s)
-#endif
-#if PT_NODE_COOP
 // k_trace_far's visit, for scenes whose rays miss the caches (chosen per scene by a timed trial, pt_context.cpp): the lean visit with the two lanes of a
 // PAIR fetching each other's node together (tools/ubench/visit_quad.hip `coop`).  Node A belongs to the
 // even lane, node B to the odd one.  In loads 1-3 both lanes read node A (its owner the three near rows, the partner A's three far rows, at the addresses
@@ -1146,7 +1020,6 @@ PT_DEV void node_step_lean(const PtScene& sc, LaneRay& r, TravCtx& c) {
 // 4 M triangles 1288 / 1241), hence the trial.
 #define PT_PAIR_U(x) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), 0xB1, 0xF, 0xF, false))
 #define PT_PAIR_F(x) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (x)), 0xB1, 0xF, 0xF, false))
-template <int TOUCH>
 PT_DEV void node_step_coop(const PtScene& sc, LaneRay& r, TravCtx& c, bool w_node, unsigned long long m_node) {
     constexpr unsigned long long kEven = 0x5555555555555555ull, kOdd = 0xAAAAAAAAAAAAAAAAull;
     const unsigned long long ev = m_node & kEven, od = m_node & kOdd;
@@ -1205,21 +1078,8 @@ PT_DEV void node_step_coop(const PtScene& sc, LaneRay& r, TravCtx& c, bool w_nod
         const unsigned long long y1 = Tm & (el1 ^ er1), e1 = er1 ^ y1, e3 = el1 ^ y1;
         fs_push4_exec(r.sa, top, c0, c1, c2, c3, e0, e1, e2, e3);
         if (w_node) r.top = top;
-        if constexpr (TOUCH != 0 && PT_COOP_TOUCH) {         // (as in node_step_lean)
-            const unsigned long long p0 = e0 & (e1 | e2 | e3), p1 = e1 & (e2 | e3), p2 = e2 & e3;
-            const char* tb = reinterpret_cast<const char*>(sc.tris);
-            auto touch = [&](uint32_t cref) {
-                if (!(cref & PT_LEAF_BIT)) return;
-                uint32_t v = *reinterpret_cast<const uint32_t*>(tb + (size_t)(cref & PT_LEAF_FIRST_MASK) * 48u);
-                asm volatile("" :: "v"(v));
-            };
-            if (__builtin_amdgcn_inverse_ballot_w64(p0)) touch(c0);
-            if (__builtin_amdgcn_inverse_ballot_w64(p1)) touch(c1);
-            if (__builtin_amdgcn_inverse_ballot_w64(p2)) touch(c2);
-        }
     }
 }
-#endif
 
 // intersect_simd (qbvh_x86.rs:230-287): closest hit.  Returns record index or -1.
 template <bool SPH, bool INST, bool ALPHA = false>
@@ -1278,12 +1138,63 @@ PT_DEV uint32_t wave_ticket(uint32_t* ticket) {
 // node (4 slab tests, ordered pushes) or a leaf, whose triangle tests are pooled over the wave
 // (DIST) or walked by the owning lane (leaves of more than 8 triangles).  The order of pops,
 // tests and t_max updates per ray is exactly the reference's, whatever the interleaving across lanes.
+// trace_body's phase profile: where a traversal wave's clocks go.  Only in the diagnostic build -DPT_PROFILE_PHASES (which also adds a wait for the
+// loads between the halves of a leaf round); otherwise PT_PROF(...) is an empty statement -- as a macro, not as an object with empty methods:
+// that form changed the compiled code of k_trace_far and k_trace_seq.  The waves' sums land in the diagnostic words of the spill buffer and
+// pt_context.cpp prints them as the [phases] lines.  Clocks are taken between the last mark() / lap() and the next lap().
 #ifdef PT_PROFILE_PHASES
-#define PT_PROF_T(name) const unsigned long long name = (unsigned long long)__builtin_readcyclecounter()
-#define PT_PROF_SET(name) name = (unsigned long long)__builtin_readcyclecounter()
+#define PT_PROF_BEGIN() PhaseProf prof; prof.start()
+#define PT_PROF(call) prof.call
+struct PhaseProf {
+    enum {                                                // slots (0 and 1 were the staged node fetch's issue and wait clocks: never written)
+        NODE = 2, NODE_ROUNDS = 3, NODE_LANES = 4,        // lean / pairwise node rounds: clocks, rounds, visiting lanes (those of the general visits too)
+        LEAF_ISSUE = 5, LEAF_WAIT = 6, LEAF_FINISH = 7, LEAF_ROUNDS = 8, LEAF_ITEMS = 9,      // (the per-lane kernels: the leaf step's clocks in LEAF_FINISH, its lanes in LEAF_ITEMS)
+        SERVICE = 10,                                     // everything in an iteration before the phase decision
+        TOTAL = 11,                                       // the wave's clocks
+        GENERAL = 12, GENERAL_ROUNDS = 13,                // general-visit rounds (the per-lane kernels: every node round)
+        PREFETCH = 14, HANDOUT = 15,                      // service in parts: the prefetch state machine, retiring + handing out rays
+        ITERATIONS = 16, HANDOUTS = 17, HANDOUTS_CLK = 18,      // loop iterations, those with a hand-out, HANDOUT's clocks of those
+        EMPTY = 19, EMPTY_CLK = 20,                       // empty timed sections and their clocks: the counter's own cost
+        SLOTS = 24
+    };
+    unsigned long long slot[SLOTS];
+    long long t_start, t_iter, t_mark;
+    bool handout;
+    static PT_DEV long long now() { return (long long)__builtin_readcyclecounter(); }
+    PT_DEV void start() { for (int i = 0; i < SLOTS; i++) slot[i] = 0; t_start = now(); }
+    PT_DEV void iteration() {
+        t_iter = now();
+        handout = false;
+        if ((slot[ITERATIONS]++ & 63ull) == 0ull) {          // calibration: two counter reads back to back, what every timed section includes
+            const long long e0 = now();
+            const long long e1 = now();
+            slot[EMPTY] += 1; slot[EMPTY_CLK] += (unsigned long long)(e1 - e0);
+            t_iter = now();
+        }
+        t_mark = t_iter;
+    }
+    PT_DEV void mark() { t_mark = now(); }
+    PT_DEV void lap(int s) { const long long t = now(); slot[s] += (unsigned long long)(t - t_mark); t_mark = t; }
+    PT_DEV void hand_out() { handout = true; }
+    PT_DEV void handed_out() {               // the end of retiring and handing out rays, whether any were
+        const unsigned long long dt = (unsigned long long)(now() - t_mark);
+        slot[HANDOUT] += dt;
+        if (handout) { slot[HANDOUTS] += 1; slot[HANDOUTS_CLK] += dt; }
+    }
+    PT_DEV void serviced() { t_mark = now(); slot[SERVICE] += (unsigned long long)(t_mark - t_iter); }      // the phase decision starts
+    PT_DEV void round(int clk, int rounds, int items, unsigned long long n) { lap(clk); slot[rounds] += 1; slot[items] += n; }
+    PT_DEV void node_round(unsigned long long lanes) { round(NODE, NODE_ROUNDS, NODE_LANES, (unsigned long long)__popcll(lanes)); }
+    PT_DEV void general_round(unsigned long long lanes) { round(GENERAL, GENERAL_ROUNDS, NODE_LANES, (unsigned long long)__popcll(lanes)); }
+    PT_DEV void leaf_round(unsigned long long items) { round(LEAF_FINISH, LEAF_ROUNDS, LEAF_ITEMS, items); }
+    PT_DEV void leaf_issued() { lap(LEAF_ISSUE); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lap(LEAF_WAIT); }      // the record loads' wait, timed on its own
+    PT_DEV void finish(uint32_t* diag, uint32_t lane) {
+        slot[TOTAL] = (unsigned long long)(now() - t_start);
+        if (lane == 0) for (int i = 0; i < SLOTS; i++) atomicAdd(reinterpret_cast<unsigned long long*>(diag) + i, slot[i]);
+    }
+};
 #else
-#define PT_PROF_T(name) do { } while (0)
-#define PT_PROF_SET(name) do { } while (0)
+#define PT_PROF_BEGIN() ((void)0)
+#define PT_PROF(call) ((void)0)
 #endif
 #ifndef PT_REFILL_MIN
 #define PT_REFILL_MIN 8
@@ -1298,64 +1209,33 @@ PT_DEV uint32_t wave_ticket(uint32_t* ticket) {
 #define PT_TRACE_WAVES 4        // waves per SIMD the register allocator must leave room for (k_trace_seq)
 #endif
 #ifndef PT_TRACE_DIST_WAVES
-#if PT_NODE_STAGED
-#define PT_TRACE_DIST_WAVES 3   // pooled-leaf kernels with staged node fetch: 49 KB of LDS per block => three blocks per CU
-#else
 #define PT_TRACE_DIST_WAVES 4
 #endif
-#endif
 
-#ifndef PT_LEAF_TRIS_MIN
-#define PT_LEAF_TRIS_MIN 56          // distributed leaf phase on its own (general visit in the wave): once this many triangle tests are parked
-#endif
 #ifndef PT_LEAF_LANES_MIN
-#define PT_LEAF_LANES_MIN 18         // > 0: a leaf round once this many LANES are parked on a leaf, instead of PT_LEAF_TRIS_MIN parked tests (0).  The exact
-                                     // test count costs four ballots + popcounts in EVERY iteration's phase decision; RT1M at 64 spp, k_trace ms per launch:
+#define PT_LEAF_LANES_MIN 18         // a leaf round once this many LANES are parked on a leaf.  (The exact count of parked TESTS cost four ballots + popcounts in
+                                     // EVERY iteration's phase decision.)  RT1M at 64 spp, k_trace ms per launch:
                                      // tests >= 56: 39.66; lanes >= 12 / 16 / 18 / 20 / 22 / 24 / 28 / 32: 40.88 / 39.39 / 39.34 / 39.43 / 40.00 / 40.52 / 41.79 / 43.50
 #endif
-#ifndef PT_WALK_BATCH
-#define PT_WALK_BATCH 1              // 1: a leaf's owner reads its results from LDS four at a time instead of one per loop iteration
-#endif
-#ifndef PT_LEAF_HELPER_ACCEPT
-#define PT_LEAF_HELPER_ACCEPT 1      // 1 (2: the sphere-capable kernel too): every helper applies tri_accept itself, with its owner's t_max as the round starts; one ballot is the round's candidate mask and
-                                     // an owner only walks the candidates among its leaf's items (most leaves have none: no LDS read, no loop).  Exact because tri_accept
-                                     // is monotone in t_max and a ray's t_max never grows: a test that fails against the round's t_max fails against every later one, and the
-                                     // first candidate of a leaf sees exactly the round's t_max (tests/test_accept_monotone.py).  0: the owner walks all of its leaf's results
-#endif
-#ifndef PT_RETIRE_AT_HANDOUT
-#define PT_RETIRE_AT_HANDOUT 1       // 1 (pooled-leaf kernels): a finished ray's result is stored in the block that hands out new rays (and in every iteration of the drain)
-                                     // instead of in the iteration it finishes in: the three store branches ran for one or two lanes in most iterations
-#endif
-#ifndef PT_PF_BYPASS
-#define PT_PF_BYPASS 1               // 1 (k_trace, k_trace_sph_dist): a complete reservation (stage 3) branches past the prefetch state machine instead of falling through its if / else-if chain
-#endif
+static_assert(PT_LEAF_LANES_MIN > 0, "the leaf round is triggered by the number of parked lanes");
 #ifndef PT_SPH_LANES_MIN
 #define PT_SPH_LANES_MIN 8           // scenes with spheres: a sphere round once this many lanes are parked on a leaf that holds a sphere (2 / 4 / 6 / 8 / 10 / 16 / 24 / 32:
                                      // 46.9 / 45.2 / 44.6 / 44.4 / 44.5 / 44.9 / 48.6 / 54.2 ms per launch, RT1M lit by a sphere, 64 spp)
 #endif
-#ifndef PT_LEAF_TRIS_FUSED
-#define PT_LEAF_TRIS_FUSED 0         // > 0: a leaf round rides along a staged node round once this many tests are parked (experiment)
-#endif
 // DIST: every leaf holds at most 8 triangles and its reference carries the count, so a leaf phase can pool the
 // triangles of all parked lanes and hand one (ray, triangle) test to each lane of the wave.
-template <bool DIST, bool SPH, bool INST = false, int TOUCH = 0, bool ALPHA = false>
+// FAR: k_trace_far, the pooled-leaf kernel that fetches nodes pairwise (node_step_coop).
+template <bool DIST, bool SPH, bool INST = false, bool FAR = false, bool ALPHA = false>
 PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
-    // LDS per block.  Pooled-leaf kernels: 16 stack slots x 1 KB + 8 KB node staging per wave + node-index exchange = 49 KB, three
-    // blocks per CU (RT1M: 99.98 % of node visits find the stack at 13 entries or fewer; deeper lanes spill to HBM); a leaf round's
-    // 64 test results and owner map live in the wave's staging area, which a node round of the same wave never uses at the same time.
+    // LDS per block.  Pooled-leaf kernels (PT_TRACE_WIDE: one 1024-thread block per CU): PT_FS_SLOTS = 24 stack slots x 4 KB = 96 KB (deeper
+    // lanes spill to HBM), a leaf round's 64 test results and owner map per wave (17 KB) and the top of the tree (341 nodes x 112 bytes = 38 KB):
+    // 153.9 of the CU's 160 KB.
     constexpr uint32_t TB = DIST ? PT_TBLOCK : PT_BLOCK;          // threads per block (PT_TRACE_WIDE: the pooled-leaf kernels run 1024)
     __shared__ uint32_t s_stack[(DIST ? PT_FS_SLOTS : PT_LDS_STACK) * TB];
     __shared__ unsigned long long s_cnt[4];
-#if PT_NODE_STAGED
-    __shared__ __attribute__((aligned(16))) unsigned char s_stage[DIST ? (PT_BLOCK / 64) * 8192 : 16];
-    __shared__ uint32_t s_idx[DIST ? PT_BLOCK + PT_BLOCK / 4 : 1];       // per wave: 64 node indices, then the leaf round's 64-byte owner map
-    float4* const s_res = reinterpret_cast<float4*>(s_stage + (threadIdx.x >> 6) * 8192u) - (threadIdx.x & ~63u);            // indexed [wbase + k]
-    unsigned char* const s_map = reinterpret_cast<unsigned char*>(&s_idx[(threadIdx.x >> 6) * 80u + 64u]) - (threadIdx.x & ~63u);
-#else
     __shared__ float4 s_res[DIST ? TB : 1];          // per wave: 64 test results (ok, t_scaled, det, t)
     __shared__ unsigned char s_map[DIST ? TB : 1];   // per wave: work item -> owner lane
-#endif
-#if PT_TOP_NODES > 0 && !PT_NODE_STAGED
+#if PT_TOP_NODES > 0
     __shared__ float4 s_top[DIST ? PT_TOP_NODES * 7 : 1];      // rows 0..6 (six plane rows, child references) of the first nodes of the tree
 #endif
     TravCtx c;
@@ -1369,15 +1249,8 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     if constexpr (DIST) {        // slot 0 of the lane's stack: the sentinel a pop of the last entry reads back (see node_step_lean)
         s_stack[threadIdx.x] = PT_EMPTY_REF;
         c.lane_base = lds_addr_of(&s_stack[threadIdx.x]);
-#if PT_NODE_STAGED
-        const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-        c.stage_wave = lds_addr_of(reinterpret_cast<const uint32_t*>(s_stage + wv * 8192u));
-        c.stage_own = c.stage_wave + (ln >> 3) * 1024u + (ln & 7u) * 128u;
-        c.idx_pub = lds_addr_of(&s_idx[wv * 80u + (ln & 7u) * 8u + (ln >> 3)]);
-        c.idx_ld = lds_addr_of(&s_idx[wv * 80u + (ln >> 3) * 8u]);
-#endif
     }
-#if PT_TOP_NODES > 0 && !PT_NODE_STAGED
+#if PT_TOP_NODES > 0
     if constexpr (DIST) {
         const uint32_t n_top = min(sc.n_top, (uint32_t)PT_TOP_NODES);
         const float4* src = reinterpret_cast<const float4*>(sc.nodes);
@@ -1410,24 +1283,9 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     uint32_t seg = blockIdx.x & 7u, seg_dry = 0;
     const uint32_t seg_len = (((total + 7u) >> 3) + 63u) & ~63u;
     float4 pf_o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pf_d = pf_o;
-#ifdef PT_PROFILE_PHASES
-    // pooled-leaf kernels: 0 node issue clk, 1 node wait clk, 2 node finish clk, 3 node rounds, 4 node lanes, 5 leaf issue clk, 6 leaf wait clk,
-    // 7 leaf finish clk, 8 leaf rounds, 9 leaf items, 10 service clk, 11 wave total clk, 12 general-visit clk, 13 general-visit rounds, 14 prefetch state machine clk,
-    // 15 retire + hand-out clk, 16 loop iterations, 17 iterations with a hand-out, 18 retire + hand-out clk of those, 19 empty timed sections, 20 their clk (the counter's own cost)
-    unsigned long long prof[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long prof_t0 = __builtin_readcyclecounter();
-#endif
+    PT_PROF_BEGIN();
     for (;;) {
-#ifdef PT_PROFILE_PHASES
-        long long pt_iter = __builtin_readcyclecounter();
-        bool pt_handout = false;
-        if ((prof[16]++ & 63ull) == 0ull) {          // calibration: two counter reads back to back, what every timed section above and below includes
-            const long long e0 = __builtin_readcyclecounter();
-            const long long e1 = __builtin_readcyclecounter();
-            prof[19] += 1; prof[20] += (unsigned long long)(e1 - e0);
-            pt_iter = __builtin_readcyclecounter();
-        }
-#endif
+        PT_PROF(iteration());
         // ---- ray prefetch pipeline.  A refill used to be three dependent round trips (ticket atomic, path id, ray
         // record) with the whole wave waiting; now the wave keeps the next 64 rays in registers, one per lane, and
         // fetches them one stage per iteration so that every wait is covered by a traversal step:
@@ -1438,7 +1296,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         // the reservation's registers (pf_o, pf_d, pf_p, pf_kind) in a block every iteration runs through: fourteen register copies and two waits for all
         // loads, advanced or not.  The empty asm keeps the compiler from folding this test back into the chain's own.
         // (k_trace and k_trace_sph_dist, where it was measured to gain; k_trace_far's one run on 16 M sparse triangles lost 1 %: DESIGN.md section 9.)
-        constexpr bool PF_BYPASS = DIST && TOUCH == 0 && PT_PF_BYPASS;
+        constexpr bool PF_BYPASS = DIST && !FAR;
         int pf_gate = pf_stage;
         if constexpr (PF_BYPASS) asm volatile("" : "+s"(pf_gate));
         if (PF_BYPASS && pf_gate == 3) {
@@ -1479,14 +1337,12 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             }
             pf_stage = 3;
         }
-#ifdef PT_PROFILE_PHASES
-        const long long pt_pf = __builtin_readcyclecounter();
-        prof[14] += (unsigned long long)(pt_pf - pt_iter);       // the prefetch state machine
-#endif
-        // ---- retire finished rays: stores only.  Pooled-leaf kernels (PT_RETIRE_AT_HANDOUT): a finished lane needs nothing until it is refilled, so it keeps
+        PT_PROF(lap(PhaseProf::PREFETCH));      // the prefetch state machine
+        // ---- retire finished rays: stores only.  Pooled-leaf kernels (LATE_RETIRE): a finished lane needs nothing until it is refilled, so it keeps
         // its result (kind != 0, ray_done) and counts as idle; the stores run where rays are handed out -- once PT_REFILL_MIN lanes are idle, not in every iteration
         // in which one or two lanes finish -- and in every iteration once the queue is dry (the loop only ends from there: every ray is stored exactly once).
-        constexpr bool LATE_RETIRE = DIST && PT_RETIRE_AT_HANDOUT;
+        // The per-lane kernels store a result in the iteration its ray finishes in.
+        constexpr bool LATE_RETIRE = DIST;
 #define PT_RETIRE()                                                                                                                                      \
         if (kind != 0 && ray_done(r)) {                                                                                                                  \
             if (kind == 1) { P.hit_t[p] = r.ray_tmax; P.hit_rec[p] = r.best; if (INST && (!ALPHA || sc.n_instances)) P.hit_inst[p] = r.best_inst; }      \
@@ -1504,9 +1360,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             const unsigned long long idle = LATE_RETIRE ? __ballot(kind == 0 || ray_done(r)) : __ballot(kind == 0);
             const uint32_t n_idle = (uint32_t)__popcll(idle);
             if (pf_stage == 3 && (n_idle >= PT_REFILL_MIN || idle == ~0ull || (!more && n_idle != 0))) {
-#ifdef PT_PROFILE_PHASES
-                pt_handout = true;
-#endif
+                PT_PROF(hand_out());
                 if constexpr (LATE_RETIRE) { PT_RETIRE() }
                 const uint32_t take = min(n_idle, pf_count - pf_used);
                 const uint32_t rank = (uint32_t)__popcll(idle & below);
@@ -1527,13 +1381,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             }
         }
 #undef PT_RETIRE
-#ifdef PT_PROFILE_PHASES
-        {
-            const unsigned long long dt = (unsigned long long)(__builtin_readcyclecounter() - pt_pf);       // retiring and handing out rays
-            prof[15] += dt;
-            if (pt_handout) { prof[17] += 1; prof[18] += dt; }
-        }
-#endif
+        PT_PROF(handed_out());
         if ((LATE_RETIRE ? __ballot(kind != 0 && !ray_done(r)) : __ballot(kind != 0)) == 0) {      // nothing to traverse (late retire: with the queue dry everything finished was stored above)
             if (!more && pf_stage == 0) break;
             continue;
@@ -1546,10 +1394,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         bool w_tri = kind != 0 && ray_wants_tri(r);
         bool w_node = kind != 0 && ray_wants_node(r);
         unsigned long long m_tri = __ballot(w_tri), m_node = __ballot(w_node);
-#ifdef PT_PROFILE_PHASES
-        long long pt0 = __builtin_readcyclecounter();
-        prof[10] += (unsigned long long)(pt0 - pt_iter);
-#endif
+        PT_PROF(serviced());
         if constexpr (DIST) {
             // triangles parked: the count rides in bits 28..30 of the leaf reference
             // Scenes with spheres: a leaf that holds a sphere waits for a round of its own.  The sphere test is ~600 instructions of interval
@@ -1558,45 +1403,42 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             // out that a leaf holds a sphere (its records are loaded anyway) and leaves it parked with `sph_wait` set; once PT_SPH_LANES_MIN
             // lanes wait like that -- or nothing else can run -- a sphere round serves exactly those leaves, spheres and triangles alike.
             // Every leaf is still tested whole, by its owner, in leaf order: results and counters do not change.
-            constexpr bool SPHDEF = SPH && !PT_NODE_STAGED && PT_LEAF_LANES_MIN > 0;      // (the experiment builds test spheres in every round, as before)
-            bool sround = SPH && !SPHDEF;              // this iteration's leaf round is a sphere round
+            bool sround = false;                       // this iteration's leaf round is a sphere round
             unsigned long long m_tri_s = 0;
-            if constexpr (SPHDEF) {
+            if constexpr (SPH) {
                 m_tri_s = __ballot(w_tri && sph_wait);
                 m_tri &= ~m_tri_s;
             }
-            const bool sph_go = SPHDEF && (uint32_t)__popcll(m_tri_s) >= (uint32_t)PT_SPH_LANES_MIN;
+            const bool sph_go = SPH && (uint32_t)__popcll(m_tri_s) >= (uint32_t)PT_SPH_LANES_MIN;
             const uint32_t tcnt = w_tri ? ((r.top >> PT_LEAF_COUNT_SHIFT) & 7u) + 1u : 0u;
             uint32_t tcnt_r = tcnt;                    // ... of the lanes the coming round serves (0 for the others)
             bool w_serve = w_tri;
-#if PT_LEAF_LANES_MIN > 0
-            // the leaf-round trigger from the number of parked LANES (experiment: the exact count of parked tests costs four ballots and
-            // popcounts per iteration, needed by every iteration's phase decision; leaf_issue computes its own prefix sums when a round runs)
+            // the leaf-round trigger, from the number of parked LANES (leaf_issue computes the prefix sums of the parked tests when a round runs):
+            // leaf_level is LEAF_DUE when a leaf round is due, else 0.  Kept as this uint32_t select: written as a bool, the same condition
+            // changes the register allocation of three kernels.
+            constexpr uint32_t LEAF_DUE = 56u;
             unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-            const uint32_t n_parked = (sph_go || (uint32_t)__popcll(m_tri) >= (uint32_t)PT_LEAF_LANES_MIN) ? (uint32_t)PT_LEAF_TRIS_MIN : 0u;
-#else
-            const unsigned long long c0 = __ballot((tcnt & 1u) != 0), c1 = __ballot((tcnt & 2u) != 0), c2 = __ballot((tcnt & 4u) != 0),
-                                     c3 = __ballot((tcnt & 8u) != 0);
-            const uint32_t n_parked = (uint32_t)(__popcll(c0) + 2 * __popcll(c1) + 4 * __popcll(c2) + 8 * __popcll(c3));
-#endif
-            // ---- distributed leaf round, in two halves so that its triangle loads can fly together with a node round's fetches.
+            const uint32_t leaf_level = (sph_go || (uint32_t)__popcll(m_tri) >= (uint32_t)PT_LEAF_LANES_MIN) ? LEAF_DUE : 0u;
+            // ---- distributed leaf round, in two halves (the record loads fly between them).
             // issue: owners are served in lane order while their whole leaf fits (the others stay parked); lane w becomes the helper
             // of triangle k of owner o, takes the owner's ray constants by ds_bpermute and starts the 48-byte record's load.
             const uint32_t wbase = threadIdx.x & ~63u;
+            // HACC, the accept test on the helper lanes: every helper applies tri_accept itself, with its owner's t_max as the round starts; one ballot is
+            // the round's candidate mask and an owner only walks the candidates among its leaf's items (most leaves have none: no LDS read, no loop).
+            // Exact because tri_accept is monotone in t_max and a ray's t_max never grows: a test that fails against the round's t_max fails against
+            // every later one, and the first candidate of a leaf sees exactly the round's t_max (tests/test_accept_monotone.py).
             // (the sphere-capable kernel keeps the owner's full walk: with the candidate walk it spills 16 registers)
-            constexpr bool HACC = PT_LEAF_HELPER_ACCEPT == 2 || (PT_LEAF_HELPER_ACCEPT == 1 && !SPH);
+            constexpr bool HACC = !SPH;
             uint32_t lf_pre = 0, lf_items = 0;
             bool lf_served = false, lf_valid = false;
             int lf_kk = 0;
-            float lf_tmax = PT_INF;             // (PT_LEAF_HELPER_ACCEPT: every round) the owner's t_max when the round starts (an upper bound of what its leaf walk will compare with)
+            float lf_tmax = PT_INF;             // (HACC: every round) the owner's t_max when the round starts (an upper bound of what its leaf walk will compare with)
             RayPre lf_rp;
             TriVerts lf_tv;
             auto leaf_issue = [&](auto sr_tag) {
                 constexpr bool SR = decltype(sr_tag)::value;      // compile-time: this copy is the sphere round (two copies: the normal round carries no sphere code)
                 (void)SR;
-#if PT_LEAF_LANES_MIN > 0
                 c0 = __ballot((tcnt_r & 1u) != 0); c1 = __ballot((tcnt_r & 2u) != 0); c2 = __ballot((tcnt_r & 4u) != 0); c3 = __ballot((tcnt_r & 8u) != 0);
-#endif
                 lf_pre = (uint32_t)(__popcll(c0 & below) + 2 * __popcll(c1 & below) + 4 * __popcll(c2 & below) + 8 * __popcll(c3 & below));
                 lf_served = w_serve && lf_pre + tcnt_r <= 64u;
                 const unsigned long long m_served = __ballot(lf_served);
@@ -1630,8 +1472,8 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 bool sphere_rec = false;
                 if constexpr (SPH) sphere_rec = lf_valid && (lf_tv.flags & PT_TRI_SPHERE) != 0;
                 unsigned long long m_sitems = 0;            // normal round: the items that are spheres (item i is helper lane i)
-                if constexpr (SPHDEF && !SR) { m_sitems = __ballot(sphere_rec); }
-                bool cand = false;          // PT_LEAF_HELPER_ACCEPT: this item passes everything, the t_max comparison against the round's t_max included
+                if constexpr (SPH && !SR) { m_sitems = __ballot(sphere_rec); }
+                bool cand = false;          // HACC: this item passes everything, the t_max comparison against the round's t_max included
                 if (lf_valid) {
                     // The triangle test runs for EVERY item, a sphere's record included (its fields are not vertices: the result is thrown
                     // away).  With the test behind `if (!sphere)` the compiler moved the record's loads into the two branches, behind the
@@ -1659,7 +1501,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 bool walk = lf_served;
-                if constexpr (SPHDEF) {
+                if constexpr (SPH) {
                     if (!SR && lf_served && ((m_sitems >> lf_pre) & ((1ull << tcnt_r) - 1ull)) != 0ull) { sph_wait = true; walk = false; }     // a sphere among this leaf's items
                     if (SR && lf_served) sph_wait = false;
                 }
@@ -1689,7 +1531,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         }
                     }
                     } else {
-#if PT_WALK_BATCH
+                    // The sphere-capable kernel's path: the owner walks ALL of its leaf's results.
                     // The results come four at a time: the loop's one LDS read per item was a round trip per item for the owner with the
                     // fullest leaf, and the whole wave waits for that owner.  (Slots past the leaf's own are read and ignored: they lie in
                     // the wave's 64 and hold other owners' results.)
@@ -1711,129 +1553,37 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         };
                         step(va, k0); step(vb, k0 + 1u); step(vc, k0 + 2u); step(vd, k0 + 3u);
                     }
-#else
-                    for (uint32_t k = 0; k < tcnt; k++) {
-                        const float4 v = s_res[wbase + lf_pre + k];
-                        bool acc;
-                        if (SPH && SR && v.x == 2.0f) acc = !(v.y > r.ray_tmax) && !(v.z > r.ray_tmax);      // (a sphere's result: only a sphere round makes one)
-                        else acc = v.x != 0.0f && tri_accept(v.y, v.z, r.ray_tmax);
-                        if (acc) {
-                            r.best = (int32_t)(rec0 + k); leaf_hit = true;
-                            if (any_hit) { r.sa = c.lane_base; r.top = PT_EMPTY_REF; tested = k + 1; break; }
-                            r.ray_tmax = v.w;
-                        }
-                    }
-#endif
                     }
                     c.n_tris += tested;
                     if (leaf_hit && !any_hit) r.tmax = r.ray_tmax;
                 }
             };
-#ifdef PT_FORCE_GENERAL_VISIT
-            const bool lean = false;                                                // experiment: the first version's visit for everyone
-#elif defined(PT_EXP_NO_GENERAL_VISIT)
-            const bool lean = true;                                                 // timing experiment (wrong for NaN-exact lanes): the general visit compiled out
-#else
             const bool lean = __ballot(w_node && r.sa >= r.sa_limit) == 0ull;      // nobody NaN-exact, nobody near the LDS part's end
-#endif
-#if !PT_NODE_STAGED
-            if (lean && m_node != 0 && n_parked < PT_LEAF_TRIS_MIN) {
-                PT_PROF_T(t0);
-#if PT_NODE_COOP
-                if constexpr (TOUCH != 0 || PT_NODE_COOP == 2) node_step_coop<TOUCH>(sc, r, c, w_node, m_node);
-                else if (w_node) node_step_lean<TOUCH>(sc, r, c);
-#else
-                if (w_node) node_step_lean<TOUCH>(sc, r, c);
-#endif
-                PT_PROF_T(t1);
-#ifdef PT_PROFILE_PHASES
-                prof[2] += t1 - t0; prof[3] += 1; prof[4] += (unsigned long long)__popcll(m_node);
-#endif
-#else
-            if (lean) {
-                // Staged node round and / or leaf round.  With PT_LEAF_TRIS_FUSED > 0 a leaf round rides along a node round once that
-                // many tests are parked, so that the node round's LDS-DMA fetches and the leaf round's record loads fly together
-                // (measured: slower -- the smaller leaf rounds cost more than the shared round trip saves; kept as an experiment switch).
-                const bool do_node = m_node != 0 && (PT_LEAF_TRIS_FUSED > 0 || n_parked < PT_LEAF_TRIS_MIN);
-                const bool do_leaf = m_tri != 0 && (!do_node || (PT_LEAF_TRIS_FUSED > 0 && n_parked >= PT_LEAF_TRIS_FUSED));
-                (void)do_leaf;
-#if PT_LEAF_TRIS_FUSED > 0
-                uint32_t below_top = PT_EMPTY_REF;
-                PT_PROF_T(t0);
-                if (do_node) below_top = node_round_issue(sc, r, c, w_node);
-                PT_PROF_T(t1);
-                if (do_leaf) leaf_issue(std::integral_constant<bool, SPH>{});
-                PT_PROF_T(t2);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the LDS-DMA writes have landed (nothing else orders a ds_read behind them)
-                __builtin_amdgcn_wave_barrier();
-                PT_PROF_T(t3);
-                if (do_node) node_round_finish(r, c, w_node, below_top);
-                PT_PROF_T(t4);
-                if (do_leaf) leaf_finish(std::integral_constant<bool, SPH>{});
-                PT_PROF_T(t5);
-#else
-                unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
-                (void)t0; (void)t1; (void)t2; (void)t3; (void)t4; (void)t5;
-                PT_PROF_SET(t0);
-                if (do_node) {
-                    const uint32_t below_top = node_round_issue(sc, r, c, w_node);
-                    PT_PROF_SET(t1); PT_PROF_SET(t2);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the LDS-DMA writes have landed (nothing else orders a ds_read behind them)
-                    __builtin_amdgcn_wave_barrier();
-                    PT_PROF_SET(t3);
-                    node_round_finish(r, c, w_node, below_top);
-                    PT_PROF_SET(t4); PT_PROF_SET(t5);
-                } else {
-                    PT_PROF_SET(t1);
-                    leaf_issue(std::integral_constant<bool, SPH>{});
-                    PT_PROF_SET(t2);
-#ifdef PT_PROFILE_PHASES
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                    PT_PROF_SET(t3); PT_PROF_SET(t4);
-                    leaf_finish(std::integral_constant<bool, SPH>{});
-                    PT_PROF_SET(t5);
-                }
-#endif
-#ifdef PT_PROFILE_PHASES
-                if (do_node) { prof[0] += t1 - t0; prof[2] += t4 - t3; prof[3] += 1; prof[4] += (unsigned long long)__popcll(m_node); }
-                if (do_leaf) { prof[5] += t2 - t1; prof[7] += t5 - t4; prof[8] += 1; prof[9] += (unsigned long long)lf_items; }
-                prof[do_node ? 1 : 6] += t3 - t2;
-#endif
-#endif
-            } else if (m_node != 0 && n_parked < PT_LEAF_TRIS_MIN) {
-                PT_PROF_T(t0);
+            if (lean && m_node != 0 && leaf_level < LEAF_DUE) {
+                PT_PROF(mark());
+                if constexpr (FAR) node_step_coop(sc, r, c, w_node, m_node);
+                else if (w_node) node_step_lean(sc, r, c);
+                PT_PROF(node_round(m_node));
+            } else if (m_node != 0 && leaf_level < LEAF_DUE) {
+                PT_PROF(mark());
                 if (w_node) node_step_general(sc, r, c);
-                PT_PROF_T(t1);
-#ifdef PT_PROFILE_PHASES
-                prof[12] += t1 - t0; prof[13] += 1; prof[4] += (unsigned long long)__popcll(m_node);
-#endif
+                PT_PROF(general_round(m_node));
             } else if ((m_tri | m_tri_s) != 0) {
-                if constexpr (SPHDEF) {
+                if constexpr (SPH) {
                     sround = sph_go || m_tri == 0;          // the sphere leaves' turn: enough of them wait, or nothing else can run
                     w_serve = w_tri && (sph_wait == sround);
                     tcnt_r = w_serve ? tcnt : 0u;
                 }
-                PT_PROF_T(t0);
-                if (SPHDEF && sround) leaf_issue(std::true_type{}); else leaf_issue(std::integral_constant<bool, SPH && !SPHDEF>{});
-#ifdef PT_PROFILE_PHASES
-                PT_PROF_T(t0b);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                PT_PROF_T(t0c);
-                prof[5] += t0b - t0; prof[6] += t0c - t0b;
-#endif
-                if (SPHDEF && sround) leaf_finish(std::true_type{}); else leaf_finish(std::integral_constant<bool, SPH && !SPHDEF>{});
-                PT_PROF_T(t1);
-#ifdef PT_PROFILE_PHASES
-                prof[7] += t1 - t0c; prof[8] += 1; prof[9] += (unsigned long long)lf_items;
-#endif
+                PT_PROF(mark());
+                if (SPH && sround) leaf_issue(std::true_type{}); else leaf_issue(std::false_type{});
+                PT_PROF(leaf_issued());
+                if (SPH && sround) leaf_finish(std::true_type{}); else leaf_finish(std::false_type{});
+                PT_PROF(leaf_round(lf_items));
             }
         } else {
         if (m_node != 0 && __popcll(m_tri) < (INST ? PT_LEAF_MIN_INST : PT_LEAF_MIN)) {
             if (w_node) ray_step_node(sc, r, c);
-#ifdef PT_PROFILE_PHASES
-            prof[12] += (unsigned long long)(__builtin_readcyclecounter() - pt0); prof[13] += 1; prof[4] += (unsigned long long)__popcll(m_node);
-#endif
+            PT_PROF(general_round(m_node));
         } else {
             if constexpr (INST) {
                 if (w_tri) {
@@ -1850,16 +1600,11 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             } else {
                 if (w_tri) ray_step_tri<SPH, INST>(sc, r, kind == 2, c);
             }
-#ifdef PT_PROFILE_PHASES
-            prof[7] += (unsigned long long)(__builtin_readcyclecounter() - pt0); prof[8] += 1; prof[9] += (unsigned long long)__popcll(m_tri);
-#endif
+            PT_PROF(leaf_round((unsigned long long)__popcll(m_tri)));
         }
         }
     }
-#ifdef PT_PROFILE_PHASES
-    prof[11] = (unsigned long long)(__builtin_readcyclecounter() - prof_t0);
-    if (lane == 0) for (int i = 0; i < 24; i++) atomicAdd(reinterpret_cast<unsigned long long*>(spill) + i, prof[i]);   // diagnostic build only: the buffer's diagnostic words
-#endif
+    PT_PROF(finish(spill, lane));
     if (c.overflow) atomicOr(err, 1u);
     flush_counters(cnt, s_cnt, regular, shadow, c.n_nodes, c.n_tris);
     {   // LDS-served node visits: one add per wave
@@ -1875,7 +1620,7 @@ extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_t
 // the same with nodes fetched pairwise (node_step_coop): scenes whose rays miss the caches, chosen per scene by a timed trial (pt_context.cpp)
 extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_far(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                    uint32_t spill_depth, uint32_t* err) {
-    trace_body<true, false, false, PT_TOUCH_VARIANT>(sc, P, Q, cnt, spill, spill_depth, err);
+    trace_body<true, false, false, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // leaves of more than 8 triangles ("maxnodeprims" > 8): every lane walks its own leaf
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_WAVES) k_trace_seq(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
@@ -1895,7 +1640,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_tr
 // candidate hit of a masked mesh (prim_test<.., true>).  Every ray kind of every integrator runs here for such a scene.
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_alpha(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                         uint32_t spill_depth, uint32_t* err) {
-    trace_body<false, true, true, 0, true>(sc, P, Q, cnt, spill, spill_depth, err);
+    trace_body<false, true, true, false, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // scenes with spheres: a leaf record may stand for a sphere
 extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_sph_dist(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
@@ -3053,14 +2798,6 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 PtMaterial tm;                     // TEX / RES: this hit's lobes
                 bool use_tm = false;
                 if constexpr (TEX) {
-#if PT_TEX_EXP == 4          // timing experiment: what the second half of a split kernel would cost -- lobes built from the unevaluated parameter block
-                    if (!no_bsdf && sc.materials[s.material].textured) {
-                        PtMatParams mp = sc.mat_params[s.material];
-                        build_lobes_call(mp.m, mp.a_r, mp.a_u, mp.a_v, tm);
-                        use_tm = true;
-                        no_bsdf = tm.has_bsdf == 0;
-                    }
-#else
                     if (!no_bsdf && sc.materials[s.material].textured) {
                         TexHit th;
                         th.p = s.p; th.uv = s.uv;
@@ -3083,7 +2820,6 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         use_tm = true;
                         no_bsdf = tm.has_bsdf == 0;
                     }
-#endif
                 }
                 if constexpr (RES) {          // k_tex_resolve has evaluated this hit's textures: the values, the alphas and the bump-mapped frame come from P.tex_res
                     if (!no_bsdf && sc.materials[s.material].textured) {

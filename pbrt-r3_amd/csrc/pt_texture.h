@@ -133,10 +133,6 @@ PT_DEV V3 mip_triangle(const MipRef& m, uint32_t l, V2 st) {                    
            mip_texel(m, l, s0 + 1, t0) * (ds * (1.0f - dt)) + mip_texel(m, l, s0 + 1, t0 + 1) * (ds * dt);
 }
 
-#ifndef PT_TEX_EXP
-#define PT_TEX_EXP 0
-#endif
-
 #define PT_TEX_FN __device__ __noinline__
 #define PT_TEXN(x) x
 #define PT_TEX_VBUF_PARAM

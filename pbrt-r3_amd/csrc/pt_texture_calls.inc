@@ -138,11 +138,6 @@ PT_TEX_FN V3 PT_TEXN(mip_lookup_delta)(const MipRef& m, V2 st, V2 dst0, V2 dst1,
 
 // One node, its children already evaluated (c0, c1, c2 = tex1, tex2, amount).
 PT_TEX_FN V3 PT_TEXN(tex_node)(const pt_texture& t, const TexHit& si, V3 c0, V3 c1, V3 c2, const PtImage* images) {
-#if PT_TEX_EXP == 2          // timing experiments only (tools/r03_gpu_q.sh): 2 = image maps answer with a constant, 3 = noise textures too
-    if (t.type == PT_TEX_IMAGEMAP) return mk3(0.5f, 0.5f, 0.5f);
-#elif PT_TEX_EXP == 3
-    if (t.type == PT_TEX_IMAGEMAP || t.type == PT_TEX_FBM || t.type == PT_TEX_WRINKLED || t.type == PT_TEX_WINDY || t.type == PT_TEX_MARBLE) return mk3(0.5f, 0.5f, 0.5f);
-#endif
     switch (t.type) {
         case PT_TEX_IMAGEMAP: {                                   // imagemap.rs:57-70
             V2 st, dx, dy;
@@ -236,9 +231,6 @@ PT_TEX_FN V3 PT_TEXN(tex_node)(const pt_texture& t, const TexHit& si, V3 c0, V3 
 // per-lane scratch memory.  The inline instantiation (k_tex_resolve) keeps the values in LDS instead -- `vbuf` is the lane's column of a
 // [3 x PT_TEX_PROG_MAX][PT_BLOCK] float array --, the out-of-line one keeps the local array.
 PT_TEX_FN V3 PT_TEXN(tex_eval)(const pt_texture* textures, const uint32_t* prog, const TexHit& si, const PtImage* images PT_TEX_VBUF_PARAM) {
-#if PT_TEX_EXP == 1          // timing experiment: no texture program runs at all
-    return mk3(0.5f, 0.5f, 0.5f);
-#endif
     PT_TEX_VBUF_DECL
     const uint32_t n = prog[0];
     V3 last = mk3(0.0f, 0.0f, 0.0f);
