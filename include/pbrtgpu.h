@@ -273,7 +273,13 @@ typedef enum {
  * ray differentials carried through the specular bounces.  PT_INTEGRATOR_WHITTED: WhittedIntegrator::li (integrators/whitted.rs:38-110):
  * one light sample per light and hit without MIS, weighted by the shading normal as it was before bump mapping, the same trees.
  * The sampler is consumed depth first (reflect subtree, then transmit), as the reference's recursion does. */
-typedef enum { PT_INTEGRATOR_PATH = 0, PT_INTEGRATOR_AO = 1, PT_INTEGRATOR_DIRECTLIGHTING = 2, PT_INTEGRATOR_WHITTED = 3 } pt_integrator_type;
+/* PT_INTEGRATOR_AOV: AOVIntegrator::li (integrators/aov.rs:100-182): the camera ray's hit, compute_scattering_functions (ray differentials,
+ * the material's bump map), then one field of the SurfaceInteraction as a colour.  Which field, and the scale, come from pt_scene_set_aov.
+ * Lights and materials play no part: a surface without a material and an emitter report like any other, a ray that escapes gives 0. */
+typedef enum { PT_INTEGRATOR_PATH = 0, PT_INTEGRATOR_AO = 1, PT_INTEGRATOR_DIRECTLIGHTING = 2, PT_INTEGRATOR_WHITTED = 3, PT_INTEGRATOR_AOV = 4 } pt_integrator_type;
+/* AOVTarget (aov.rs:6-25), in its order.  Vector-valued targets go through v2c(v) = clamp(0.5 v + 0.5, 0, 1) * scale, distance / depth / uv
+ * through clamp(x, 0, 1) * scale.  RDXC and DRODX both report rx_origin; RDYC has no match arm in the reference and reports black. */
+typedef enum { PT_AOV_DISTANCE, PT_AOV_DEPTH, PT_AOV_N, PT_AOV_NS, PT_AOV_UV, PT_AOV_RDXC, PT_AOV_RDYC, PT_AOV_DRODX, PT_AOV_DRDDX, PT_AOV_DPDX, PT_AOV_DPDY, PT_AOV_DPDU, PT_AOV_DPDV, PT_AOV_DUVDX, PT_AOV_DUVDY, PT_AOV_DPDUS, PT_AOV_DPDVS } pt_aov_target;
 typedef enum { PT_DIRECT_ALL = 0, PT_DIRECT_ONE = 1 } pt_direct_strategy;      /* directlighting "strategy" (default "all") */
 typedef enum { PT_LIGHTS_UNIFORM = 0, PT_LIGHTS_POWER = 1, PT_LIGHTS_SPATIAL = 2 } pt_light_strategy;
 
@@ -401,6 +407,10 @@ pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_inf
  * per mesh.  A bad mesh or texture index, or a texture that is not a float texture, fails the upload with PT_ERR_INVALID_ARGUMENT.  A
  * scene with a mask traces every ray with k_trace_alpha (k_trace_batch_alpha for the trace hooks). */
 pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_mask* masks);
+/* Integrator "aov": the target (a pt_aov_target) and the scale of the NEXT pt_scene_upload only, consumed like the infinite lights; read
+ * when that upload's integrator is PT_INTEGRATOR_AOV.  Not called: target uv, scale 1 (create_aov_integrator's defaults, aov.rs:200-201).
+ * A target outside the enum is PT_ERR_INVALID_ARGUMENT. */
+pt_status pt_scene_set_aov(pt_context* ctx, int32_t target, float scale);
 pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* desc);
 pt_status pt_scene_info_get(const pt_context* ctx, pt_scene_info* out);
 

@@ -60,6 +60,8 @@ const pt_scene_desc* pth_scene_get_desc(const pth_scene* s);
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n);
 /* The scene's alpha-masked meshes (for pt_scene_set_alpha_masks); *n receives their count.  Valid until pth_scene_free. */
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
+/* Integrator "aov": its "target" (a pt_aov_target, default uv) and "scale" (default 1), for pt_scene_set_aov.  Other integrators: the defaults. */
+void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale);
 /* Film "filename" parameter (default "pbrt.exr"). */
 const char* pth_scene_output_filename(const pth_scene* s);
 /* Command-line overrides of the reference CLI (src/bin/pbrt.rs:234-244). */

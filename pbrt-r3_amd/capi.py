@@ -150,7 +150,14 @@ class pt_scene_info(C.Structure):
 
 
 BVH_BUILD_AUTO, BVH_BUILD_HOST, BVH_BUILD_DEVICE = 0, 1, 2
-PT_INTEGRATOR_PATH, PT_INTEGRATOR_AO, PT_INTEGRATOR_DIRECTLIGHTING, PT_INTEGRATOR_WHITTED = 0, 1, 2, 3
+PT_INTEGRATOR_PATH, PT_INTEGRATOR_AO, PT_INTEGRATOR_DIRECTLIGHTING, PT_INTEGRATOR_WHITTED, PT_INTEGRATOR_AOV = 0, 1, 2, 3, 4
+# pt_aov_target, and the names get_aov_target gives them (integrators/aov.rs:27-56; there is no "duvdy")
+(PT_AOV_DISTANCE, PT_AOV_DEPTH, PT_AOV_N, PT_AOV_NS, PT_AOV_UV, PT_AOV_RDXC, PT_AOV_RDYC, PT_AOV_DRODX, PT_AOV_DRDDX, PT_AOV_DPDX, PT_AOV_DPDY,
+ PT_AOV_DPDU, PT_AOV_DPDV, PT_AOV_DUVDX, PT_AOV_DUVDY, PT_AOV_DPDUS, PT_AOV_DPDVS) = range(17)
+AOV_TARGETS = {"distance": PT_AOV_DISTANCE, "depth": PT_AOV_DEPTH, "n": PT_AOV_N, "ng": PT_AOV_N, "ns": PT_AOV_NS, "uv": PT_AOV_UV,
+               "rdxc": PT_AOV_RDXC, "rdyc": PT_AOV_RDYC, "drodx": PT_AOV_DRODX, "drddx": PT_AOV_DRDDX, "dpdx": PT_AOV_DPDX, "dpdy": PT_AOV_DPDY,
+               "dpdu": PT_AOV_DPDU, "dpdv": PT_AOV_DPDV, "dstdx": PT_AOV_DUVDX, "dstdy": PT_AOV_DUVDY, "duvdx": PT_AOV_DUVDX,
+               "dpdus": PT_AOV_DPDUS, "dpdvs": PT_AOV_DPDVS, "shading.n": PT_AOV_NS, "shading.dpdu": PT_AOV_DPDUS, "shading.dpdv": PT_AOV_DPDVS}
 PT_DIRECT_ALL, PT_DIRECT_ONE = 0, 1
 
 
@@ -164,6 +171,7 @@ SYMBOLS = [
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le", "pt_scene_set_alpha_masks",
+    "pt_scene_set_aov",
 ]
 
 _lib = None
@@ -186,6 +194,7 @@ def load_library(path=None):
     lib.pt_last_error.argtypes = [vp]
     lib.pt_last_error.restype = C.c_char_p
     lib.pt_set_data_dir.argtypes = [vp, C.c_char_p]
+    lib.pt_scene_set_aov.argtypes = [vp, C.c_int32, C.c_float]
     lib.pt_scene_upload.argtypes = [vp, C.POINTER(pt_scene_desc)]
     lib.pt_scene_info_get.argtypes = [vp, C.POINTER(pt_scene_info)]
     lib.pt_film_clear.argtypes = [vp]
@@ -228,7 +237,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
@@ -271,6 +280,11 @@ class ParsedScene:
         n_am = C.c_uint32()
         am = L.pth_scene_get_alpha_masks(self.h, C.byref(n_am))
         self.alpha_masks = [pt_alpha_mask.from_buffer_copy(am[i]) for i in range(n_am.value)]      # "alpha" / "shadowalpha" of the meshes (copies)
+        L.pth_scene_get_aov.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        L.pth_scene_get_aov.restype = None
+        tgt, scl = C.c_int32(), C.c_float()
+        L.pth_scene_get_aov(self.h, C.byref(tgt), C.byref(scl))
+        self.aov = (tgt.value, scl.value)         # Integrator "aov": (pt_aov_target, scale)
 
     @property
     def output_filename(self):
@@ -445,6 +459,9 @@ class Context:
         am = list(getattr(scene, "alpha_masks", None) or [])
         am_arr = (pt_alpha_mask * max(1, len(am)))(*am)
         self._check(self.lib.pt_scene_set_alpha_masks(self.h, C.c_uint32(len(am)), am_arr if am else None))
+        aov = getattr(scene, "aov", None)
+        if aov is not None:          # Integrator "aov": (target, scale); otherwise the upload takes the defaults (uv, 1)
+            self._check(self.lib.pt_scene_set_aov(self.h, C.c_int32(int(aov[0])), C.c_float(float(aov[1]))))
         self._check(self.lib.pt_scene_upload(self.h, C.byref(scene.desc)))
         info = pt_scene_info()
         self._check(self.lib.pt_scene_info_get(self.h, C.byref(info)))

@@ -71,6 +71,8 @@ struct Rendezvous {
     }
 };
 
+static int32_t g_aov_target = PT_AOV_UV;      // Integrator "aov" of the parsed scene (pth_scene_get_aov), handed to every upload
+static float g_aov_scale = 1.0f;
 static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const pt_alpha_mask* am, uint32_t n_am, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
                             double* secs_out, std::vector<RankReport>* reports, std::vector<float>* xyzw_out) {
     const int n_gpus = (int)devs.size();
@@ -106,6 +108,7 @@ static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* i
         if (!check(r, pt_context_create(devs[(size_t)r], &ctxs[(size_t)r]), "no usable HIP device")) return;
         if (!check(r, pt_scene_set_infinite_lights(ctxs[(size_t)r], n_inf, inf), "infinite lights")) return;
         if (!check(r, pt_scene_set_alpha_masks(ctxs[(size_t)r], n_am, am), "alpha masks")) return;
+        if (!check(r, pt_scene_set_aov(ctxs[(size_t)r], g_aov_target, g_aov_scale), "aov target")) return;
         check(r, pt_scene_upload(ctxs[(size_t)r], dsc), "scene upload");
     });
     double secs = 0;
@@ -218,6 +221,7 @@ int main(int argc, char** argv) {
     const pt_infinite_light* inf_lights = pth_scene_get_infinite_lights(scene, &n_inf_lights);
     uint32_t n_alpha_masks = 0;
     const pt_alpha_mask* alpha_masks = pth_scene_get_alpha_masks(scene, &n_alpha_masks);
+    pth_scene_get_aov(scene, &g_aov_target, &g_aov_scale);
     if (outfile.empty()) {
         outfile = pth_scene_output_filename(scene);
         size_t dot = outfile.find_last_of('.');
@@ -258,6 +262,7 @@ int main(int argc, char** argv) {
     auto fail = [&](const char* what) { std::fprintf(stderr, "pbrt_gpu: %s: %s\n", what, pt_last_error(ctx)); pt_context_destroy(ctx); pth_scene_free(scene); return 1; };
     if (pt_scene_set_infinite_lights(ctx, n_inf_lights, inf_lights) != PT_OK) return fail("infinite lights");
     if (pt_scene_set_alpha_masks(ctx, n_alpha_masks, alpha_masks) != PT_OK) return fail("alpha masks");
+    if (pt_scene_set_aov(ctx, g_aov_target, g_aov_scale) != PT_OK) return fail("aov target");
     if (pt_scene_upload(ctx, pth_scene_get_desc(scene)) != PT_OK) return fail("scene upload");
     pt_scene_info info;
     pt_scene_info_get(ctx, &info);

@@ -140,6 +140,8 @@ public:
     std::map<std::string, uint32_t> node_float_textures, node_spectrum_textures;   // name -> index into textures
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
+    int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
+    float aov_scale = 1.0f;
     std::vector<pt_alpha_mask> alpha_masks;                             // "alpha" / "shadowalpha" of trianglemesh / plymesh shapes, one per mesh
     uint32_t n_world_lights = 0;                                        // lights appended to the scene's list so far (area lights per primitive)
     bool any_n = false, any_s = false, any_uv = false;
@@ -985,12 +987,27 @@ public:
         desc.spp = sampler_params.find_one_int("pixelsamples", 16);
         if (quick_render) desc.spp = 1;                              // create_halton_sampler / create_sobol_sampler
         // integrator (integrators/path.rs:252-271)
-        if (integrator_name != "path" && integrator_name != "ao" && integrator_name != "directlighting" && integrator_name != "whitted") {
-            fail("Integrator \"" + integrator_name + "\": only path, ao, directlighting and whitted are on the accelerated path");
+        if (integrator_name != "path" && integrator_name != "ao" && integrator_name != "directlighting" && integrator_name != "whitted" && integrator_name != "aov") {
+            fail("Integrator \"" + integrator_name + "\": only path, ao, directlighting and whitted, and aov, are on the accelerated path");
             return;
         }
         desc.integrator = integrator_name == "ao" ? PT_INTEGRATOR_AO : (integrator_name == "directlighting" ? PT_INTEGRATOR_DIRECTLIGHTING
-                          : (integrator_name == "whitted" ? PT_INTEGRATOR_WHITTED : PT_INTEGRATOR_PATH));
+                          : (integrator_name == "whitted" ? PT_INTEGRATOR_WHITTED : (integrator_name == "aov" ? PT_INTEGRATOR_AOV : PT_INTEGRATOR_PATH)));
+        if (desc.integrator == PT_INTEGRATOR_AOV) {
+            // create_aov_integrator / get_aov_target (aov.rs:27-56, :195-214); there is no "duvdy", and "pixelbounds" is not read
+            static const struct { const char* name; int32_t target; } kAovNames[] = {
+                {"distance", PT_AOV_DISTANCE}, {"depth", PT_AOV_DEPTH}, {"n", PT_AOV_N}, {"ng", PT_AOV_N}, {"ns", PT_AOV_NS}, {"uv", PT_AOV_UV},
+                {"rdxc", PT_AOV_RDXC}, {"rdyc", PT_AOV_RDYC}, {"drodx", PT_AOV_DRODX}, {"drddx", PT_AOV_DRDDX}, {"dpdx", PT_AOV_DPDX},
+                {"dpdy", PT_AOV_DPDY}, {"dpdu", PT_AOV_DPDU}, {"dpdv", PT_AOV_DPDV}, {"dstdx", PT_AOV_DUVDX}, {"dstdy", PT_AOV_DUVDY},
+                {"duvdx", PT_AOV_DUVDX}, {"dpdus", PT_AOV_DPDUS}, {"dpdvs", PT_AOV_DPDVS}, {"shading.n", PT_AOV_NS},
+                {"shading.dpdu", PT_AOV_DPDUS}, {"shading.dpdv", PT_AOV_DPDVS}};
+            const std::string target = integrator_params.find_one_string("target", "uv");
+            aov_scale = integrator_params.find_one_float("scale", 1.0f);
+            bool known = false;
+            for (const auto& e : kAovNames)
+                if (target == e.name) { aov_target = e.target; known = true; break; }
+            if (!known) { fail("AOV target \"" + target + "\" unknown."); return; }
+        }
         if (desc.integrator == PT_INTEGRATOR_DIRECTLIGHTING || desc.integrator == PT_INTEGRATOR_WHITTED) {
             // create_direct_lighting_integrator (directlighting.rs:137-158), create_whitted_integrator (whitted.rs:112-135)
             desc.direct_strategy = integrator_params.find_one_string("strategy", "all") == "one" ? PT_DIRECT_ONE : PT_DIRECT_ALL;
@@ -1101,6 +1118,10 @@ const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint3
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.alpha_masks.size() : 0u;
     return (s && !s->ctx.alpha_masks.empty()) ? s->ctx.alpha_masks.data() : nullptr;
+}
+void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale) {
+    if (target) *target = s ? s->ctx.aov_target : (int32_t)PT_AOV_UV;
+    if (scale) *scale = s ? s->ctx.aov_scale : 1.0f;
 }
 const char* pth_scene_output_filename(const pth_scene* s) { return s ? s->ctx.out_filename.c_str() : ""; }
 void pth_scene_set_pixelsamples(pth_scene* s, int spp) { if (s && spp > 0) s->ctx.desc.spp = spp; }

@@ -67,6 +67,10 @@ struct pt_context {
     pt_scene_info info;
     std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
+    int32_t next_aov_target = PT_AOV_UV;            // pt_scene_set_aov: the next upload's AOV target and scale (create_aov_integrator's defaults)
+    float next_aov_scale = 1.0f;
+    int32_t aov_target = PT_AOV_UV;                 // of the uploaded scene (read when its integrator is PT_INTEGRATOR_AOV)
+    float aov_scale = 1.0f;
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
@@ -545,6 +549,14 @@ pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_m
     return PT_OK;
 }
 
+pt_status pt_scene_set_aov(pt_context* ctx, int32_t target, float scale) {
+    if (!ctx) return PT_ERR_INVALID_ARGUMENT;
+    if (target < PT_AOV_DISTANCE || target > PT_AOV_DPDVS) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown AOV target");
+    ctx->next_aov_target = target;
+    ctx->next_aov_scale = scale;
+    return PT_OK;
+}
+
 static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d);
 // The infinite lights set with pt_scene_set_infinite_lights belong to this upload alone: a later upload of another scene does not inherit
 // them (their image indices point into this descriptor's images[]).
@@ -553,6 +565,8 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     const pt_status st = scene_upload(ctx, d);
     ctx->inf_lights.clear();
     ctx->alpha_masks.clear();
+    ctx->next_aov_target = PT_AOV_UV;
+    ctx->next_aov_scale = 1.0f;
     return st;
 }
 
@@ -574,7 +588,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (d->n_triangles > 0 && (!d->P || !d->indices || !d->tri_mesh || !d->meshes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "triangle arrays missing");
     if (d->n_spheres > 0 && !d->spheres) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "spheres array missing");
     if (d->xres <= 0 || d->yres <= 0 || d->spp <= 0 || d->max_depth < 0 || d->max_depth > 250) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "bad film / sampler / integrator parameters");
-    if (d->integrator < PT_INTEGRATOR_PATH || d->integrator > PT_INTEGRATOR_WHITTED) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown integrator");
+    if (d->integrator < PT_INTEGRATOR_PATH || d->integrator > PT_INTEGRATOR_AOV) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown integrator");
     if (d->integrator == PT_INTEGRATOR_DIRECTLIGHTING && d->direct_strategy != PT_DIRECT_ALL && d->direct_strategy != PT_DIRECT_ONE)
         return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown directlighting strategy");
     if ((d->integrator == PT_INTEGRATOR_DIRECTLIGHTING || d->integrator == PT_INTEGRATOR_WHITTED) && d->max_depth > 16)
@@ -1447,6 +1461,8 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     } else { ctx->d_env_tabs.release(); }
     sc.max_depth = d->max_depth;
     sc.integrator = d->integrator;
+    ctx->aov_target = ctx->next_aov_target;
+    ctx->aov_scale = ctx->next_aov_scale;
     sc.direct_strategy = d->direct_strategy;
     sc.ao_samples = d->ao_samples > 0 ? d->ao_samples : 64;
     sc.ao_cos_sample = d->ao_cos_sample != 0;
@@ -1744,6 +1760,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
     if (const char* e = std::getenv("PBRTGPU_POOL_PATHS")) pool_target = std::max<size_t>(65536, std::strtoull(e, nullptr, 10));
     pool_target = std::min<size_t>(pool_target, (size_t)1 << 30);      // 32-bit path ids and queue counters with room to spare
     const bool ao = sc.integrator == PT_INTEGRATOR_AO;
+    const bool aov = sc.integrator == PT_INTEGRATOR_AOV;
     const bool rec = sc.integrator == PT_INTEGRATOR_DIRECTLIGHTING || sc.integrator == PT_INTEGRATOR_WHITTED;
     // next-event entries per path: Whitted one per light, DirectLighting "one" a single one, "all" one per light sample
     const uint32_t rec_epp = !rec ? 0u : (sc.integrator == PT_INTEGRATOR_DIRECTLIGHTING && sc.direct_strategy == PT_DIRECT_ONE) ? 1u
@@ -1908,6 +1925,19 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 }
                 PT_HIP(hipEventRecord(b, ctx->stream));
                 PT_HIP(ptk_ao_resolve(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_w, ao_occ));
+                PT_HIP(hipEventRecord(c, ctx->stream));
+            } else if (aov) {
+                // camera rays -> closest hits -> one field of the interaction per hit
+                const uint32_t n_paths = n_pix * ns;
+                hipEvent_t a = get_event(ctx, ev_i), b = get_event(ctx, ev_i + 1), c = get_event(ctx, ev_i + 2);
+                if (!a || !b || !c) return ctx->fail(PT_ERR_DEVICE, "hipEventCreate failed");
+                spans.push_back({ev_i, 0});
+                ev_i += 3;
+                PT_HIP(hipEventRecord(a, ctx->stream));
+                PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                ctx->trace_launches++;
+                PT_HIP(hipEventRecord(b, ctx->stream));
+                PT_HIP(ptk_aov(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ctx->aov_target, ctx->aov_scale, cnt));
                 PT_HIP(hipEventRecord(c, ctx->stream));
             } else if (rec) {
                 // DirectLighting / Whitted: depth-first walk over the specular trees, two traversal launches per tree level

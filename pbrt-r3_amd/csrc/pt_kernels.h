@@ -41,6 +41,7 @@ hipError_t ptk_ao_rays(hipStream_t st, int grid, const PtScene& sc, const PtPath
 hipError_t ptk_ao_queue(hipStream_t st, const PtQueues& Q, const uint32_t* counter, uint32_t n_s);
 hipError_t ptk_iota(hipStream_t st, int grid, uint32_t* out, uint32_t n);
 hipError_t ptk_ao_resolve(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n_paths, const float* ao_w, const uint8_t* occ);
+hipError_t ptk_aov(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt);
 hipError_t ptk_expand_tiles(hipStream_t st, const int4* tiles, const uint32_t* tile_off, uint32_t n_tiles, int32_t sb_x0, int32_t sb_y0, uint32_t sb_w,
                             uint32_t* pixels, uint32_t* bitmap, uint32_t* err);
 hipError_t ptk_wavefront_results(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n, const uint8_t* kind, pt_hit* out, uint8_t* occ);

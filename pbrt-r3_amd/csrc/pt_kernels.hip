@@ -4205,6 +4205,107 @@ hipError_t ptk_rec_next(hipStream_t st, int grid, const PtScene& sc, const PtPat
     return hipGetLastError();
 }
 
+// ============================================================ AOVIntegrator (integrators/aov.rs:100-182)
+// After the camera rays have been traced: the interaction at the hit from the pieces rec_build puts together for the recursive integrators'
+// root frame (make_surf_any / make_surf_inst, the camera's scaled offset rays, compute_differentials), the material's bump map, then one
+// field as a colour.  A ray that escaped keeps the zero k_gen wrote.  `target` is uniform over the launch: the switch is a scalar branch.
+PT_DEV V3 aov_clamp(V3 v, float scale) { return mk3(clampf(v.x, 0.0f, 1.0f), clampf(v.y, 0.0f, 1.0f), clampf(v.z, 0.0f, 1.0f)) * scale; }      // spectrum_from_rgb(..) * scale
+PT_DEV V3 aov_v2c(V3 v, float scale) { return aov_clamp(0.5f * v + mk3(0.5f, 0.5f, 0.5f), scale); }                                              // v2c(..) * scale
+// material_bump (core/material.rs:31-72) for the whole shading frame.  textured_lobes hands back the bumped normal and dpdu only (all a
+// BSDF needs) and evaluates every other parameter on the way; this integrator reports shading.dpdv as well and needs no parameter.
+PT_DEV void aov_bump(const PtScene& sc, uint32_t prog, const TexHit& th, Surf& s) {
+    float du = 0.5f * (fabsf(th.dudx) + fabsf(th.dudy));
+    if (du == 0.0f) du = 0.0005f;
+    float dv = 0.5f * (fabsf(th.dvdx) + fabsf(th.dvdy));
+    if (dv == 0.0f) dv = 0.0005f;
+    TexHit ev = th;
+    ev.p = th.p + du * s.sh_dpdu; ev.uv = mk2(s.uv.x + du, s.uv.y + 0.0f);
+    const float u_displace = tex_eval(sc.textures, sc.tex_prog + prog, ev, sc.images).x;
+    ev.p = th.p + dv * s.sh_dpdv; ev.uv = mk2(s.uv.x + 0.0f, s.uv.y + dv);
+    const float v_displace = tex_eval(sc.textures, sc.tex_prog + prog, ev, sc.images).x;
+    const float displace = tex_eval(sc.textures, sc.tex_prog + prog, th, sc.images).x;
+    const V3 dpdu = s.sh_dpdu + (u_displace - displace) / du * s.sh_n + displace * s.sh_dndu;
+    const V3 dpdv = s.sh_dpdv + (v_displace - displace) / dv * s.sh_n + displace * s.sh_dndv;
+    s.sh_n = face_forward(normalize(cross(dpdu, dpdv)), s.n);          // set_shading_geometry(.., false) (surface_interaction.rs:140-161)
+    s.sh_dpdu = dpdu; s.sh_dpdv = dpdv;
+}
+template <bool FULL>
+PT_DEV void aov_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t base = (blockIdx.x * blockDim.x + threadIdx.x) - lane; base < n_paths; base += gridDim.x * blockDim.x) {
+        const uint32_t p = base + lane;
+        bool found = false;
+        if (p < n_paths) {
+            const int32_t rec = P.hit_rec[p];
+            if (rec >= 0) {
+                const V3 ro = f4_3(P.ray_o[p]), rd = f4_3(P.ray_d[p]);
+                Sampler sl;
+                sl.index = P.sobol_index[p];
+                sl.dim = 2;
+                const uint32_t pk = P.pixel[p];
+                sl.px = (int32_t)(pk & 0xffffu) + sc.film.sample_bounds[0];
+                sl.py = (int32_t)(pk >> 16) + sc.film.sample_bounds[1];
+                V2 u_lens = mk2(0.0f, 0.0f);
+                if (sc.cam.lens_radius > 0.0f) u_lens = sl.get_2d(sc);
+                const float2 pf = P.p_film[p];
+                RayDiffs rdf;
+                camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf);
+                uint32_t inst = 0;
+                if constexpr (FULL) inst = sc.n_instances ? P.hit_inst[p] : 0u;
+                Surf sf;
+                float thit;
+                if constexpr (FULL) found = make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, sf, &thit);
+                else found = make_surf_any<false>(sc, ro, rd, (uint32_t)rec, sf, &thit);
+                if (found) {
+                    TexHit th;
+                    th.p = sf.p; th.uv = sf.uv;
+                    compute_differentials(th, sf.p, sf.n, sf.dpdu, sf.dpdv, true, rdf);
+                    if constexpr (FULL) {          // GeometricPrimitive::compute_scattering_functions: a surface without a material stops here
+                        if (sf.material >= 0 && sc.materials[sf.material].textured) {
+                            const uint32_t prog = sc.mat_params[sf.material].prog[8];
+                            if (prog) aov_bump(sc, prog, th, sf);
+                        }
+                    }
+                    V3 l = mk3(0.0f, 0.0f, 0.0f);
+                    switch (target) {
+                        case PT_AOV_DISTANCE: { const float dist = P.hit_t[p] / length(rd); l = aov_clamp(mk3(dist, dist, dist), scale); break; }      // r.ray.t_max / |d|
+                        case PT_AOV_DEPTH: { const float dist = length(sf.p - ro); l = aov_clamp(mk3(dist, dist, dist), scale); break; }
+                        case PT_AOV_N: l = aov_v2c(sf.n, scale); break;
+                        case PT_AOV_NS: l = aov_v2c(sf.sh_n, scale); break;
+                        case PT_AOV_UV: l = aov_clamp(mk3(sf.uv.x, sf.uv.y, 0.0f), scale); break;
+                        case PT_AOV_RDXC: case PT_AOV_DRODX: l = aov_v2c(rdf.rx_o, scale); break;
+                        case PT_AOV_DRDDX: l = aov_v2c(rdf.rx_d, scale); break;
+                        case PT_AOV_DPDX: l = aov_v2c(th.dpdx, scale); break;
+                        case PT_AOV_DPDY: l = aov_v2c(th.dpdy, scale); break;
+                        case PT_AOV_DPDU: l = aov_v2c(sf.dpdu, scale); break;
+                        case PT_AOV_DPDV: l = aov_v2c(sf.dpdv, scale); break;
+                        case PT_AOV_DUVDX: l = aov_v2c(mk3(fabsf(th.dudx), fabsf(th.dvdx), 0.0f), scale); break;
+                        case PT_AOV_DUVDY: l = aov_v2c(mk3(fabsf(th.dudy), fabsf(th.dvdy), 0.0f), scale); break;
+                        case PT_AOV_DPDUS: l = aov_v2c(sf.sh_dpdu, scale); break;
+                        case PT_AOV_DPDVS: l = aov_v2c(sf.sh_dpdv, scale); break;
+                        default: break;                                       // PT_AOV_RDYC: no match arm (aov.rs:178), black
+                    }
+                    P.L[p] = make_float4(l.x, l.y, l.z, 0.0f);
+                }
+            }
+        }
+        const uint64_t hits = __ballot(found);
+        if (lane == 0 && hits) atomicAdd(&cnt->vertices, (unsigned long long)__popcll(hits));
+    }
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    aov_body<true>(sc, P, n_paths, target, scale, cnt);
+}
+// scenes without spheres, instances and textured materials (no bump map either: it makes a material textured)
+extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_aov_plain(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    aov_body<false>(sc, P, n_paths, target, scale, cnt);
+}
+hipError_t ptk_aov(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_aov, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, n_paths, target, scale, cnt);
+    else hipLaunchKernelGGL(k_aov_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, n_paths, target, scale, cnt);
+    return hipGetLastError();
+}
+
 // ============================================================ launch wrappers (host side of this TU)
 #define PT_LAUNCH_CHECK() hipGetLastError()
 

@@ -221,6 +221,7 @@ class SceneDesc:
         self.desc = capi.pt_scene_desc()
         self.buffers = {}
         self.alpha_masks = []       # capi.pt_alpha_mask, one per masked mesh (uploaded beside the descriptor, like infinite_lights)
+        self.aov = (capi.PT_AOV_UV, 1.0)      # Integrator "aov": (pt_aov_target, scale), uploaded beside the descriptor too
 
     def _set(self, name, arr, ctype):
         self.buffers[name] = arr
@@ -262,6 +263,7 @@ class SceneBuilder:
         self.spp, self.max_depth, self.rr_threshold = 16, 5, 1.0
         self.integrator, self.ao_samples, self.ao_cos_sample = capi.PT_INTEGRATOR_PATH, 64, True
         self.direct_strategy = capi.PT_DIRECT_ALL
+        self.aov = (capi.PT_AOV_UV, 1.0)
         self.light_strategy = capi.PT_LIGHTS_SPATIAL
         self.split_method, self.max_node_prims = capi.PT_SPLIT_SAH, 4
 
@@ -361,6 +363,12 @@ class SceneBuilder:
     def integrator_whitted(self, maxdepth=5):
         """Integrator "whitted" (integrators/whitted.rs:112-135)."""
         self.integrator, self.max_depth = capi.PT_INTEGRATOR_WHITTED, int(maxdepth)
+
+    def integrator_aov(self, target="uv", scale=1.0):
+        """Integrator "aov" (integrators/aov.rs:195-214): `target` by the reference's names (capi.AOV_TARGETS)."""
+        if target not in capi.AOV_TARGETS:
+            raise ValueError('AOV target "%s" unknown.' % target)
+        self.integrator, self.aov = capi.PT_INTEGRATOR_AOV, (capi.AOV_TARGETS[target], float(scale))
 
     def accelerator_bvh(self, splitmethod="sah", maxnodeprims=4):
         self.split_method = {"sah": 0, "hlbvh": 1, "middle": 2, "equal": 3}.get(splitmethod, 0)
@@ -794,6 +802,7 @@ class SceneBuilder:
             d.n_spheres, d.spheres = len(self.spheres), sph
         sd.infinite_lights = list(self.infinite_lights)
         sd.alpha_masks = list(self.alpha_masks)
+        sd.aov = tuple(self.aov)
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
         d.camera_to_world[:] = [float(v) for v in self.camera_to_world]
         d.fov = self.fov
