@@ -186,6 +186,26 @@ typedef struct {
     uint32_t reserved;
 } pt_infinite_light;
 
+/* The delta lights: PointLight, SpotLight and DistantLight (src/lights/point.rs, spot.rs, distant.rs).  The record carries what the
+ * reference's constructors are given -- the transform pair, the spectrum and the two cone angles -- and nothing derived from them: the
+ * upload computes p_light = light_to_world.transform_point(0) (point, spot), w_light = normalize(light_to_world.transform_vector(direction))
+ * (distant), the cone cosines cos(angle * (PI / 180)) in f32 (spot) and the world radius (distant) as those constructors do.  Passed with
+ * pt_scene_set_delta_lights, not in pt_scene_desc.  Transforms must be affine (last row 0 0 0 1). */
+#define PT_DELTA_POINT   0
+#define PT_DELTA_SPOT    1
+#define PT_DELTA_DISTANT 2
+typedef struct {
+    int32_t kind;               /* PT_DELTA_* */
+    uint32_t light_index;       /* position in the scene's light list, as pt_infinite_light.light_index (the two kinds count together) */
+    float light_to_world[16];   /* row-major Transform.m.  point: Translate(from) * CTM (point.rs:121); spot: CTM * Translate(from) *
+                                 * Inverse(dir_to_z) (spot.rs:148-154); distant: the CTM (distant.rs:136-146) */
+    float world_to_light[16];   /* its stored inverse (Transform.m_inv); spot: `falloff` reads its first three rows */
+    float spectrum[3];          /* "I" * "scale" (point, spot), "L" * "scale" (distant) */
+    float cone_total_width;     /* spot: "coneangle", degrees */
+    float cone_falloff_start;   /* spot: "coneangle" - "conedelta", degrees */
+    float direction[3];         /* distant: "from" - "to" as given (light space; not normalised): the w_light argument of DistantLight::new */
+} pt_delta_light;
+
 /* AlphaMaskShape (src/shapes/alphamask.rs) around every triangle of a mesh: "alpha" / "shadowalpha" of a trianglemesh or plymesh
  * (shapes/triangle.rs:654-694).  A candidate hit is rejected when the mask evaluated at its intersection-time interaction is <= 0;
  * the rejected hit does not shorten the ray.  Closest-hit rays test "alpha", shadow (any-hit) rays "alpha" and then "shadowalpha".
@@ -403,6 +423,10 @@ pt_status pt_set_data_dir(pt_context* ctx, const char* dir);
  * scene with infinite lights is preceded by this call.  A scene with one runs the *_env kernels of the path, directlighting and whitted
  * integrators (escaped rays add Le, next-event estimation samples the map). */
 pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_infinite_light* lights);
+/* The delta lights (point, spot, distant) of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the infinite
+ * lights.  Their next-event estimate has no MIS weight and no probe ray (estimate_direct_surface, sample_lights.rs:380-397); a scene
+ * with one runs the *_env kernels, as a scene with an infinite light does.  An unknown kind or a projective transform fails the upload. */
+pt_status pt_scene_set_delta_lights(pt_context* ctx, uint32_t n, const pt_delta_light* lights);
 /* The alpha masks of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the infinite lights.  At most one record
  * per mesh.  A bad mesh or texture index, or a texture that is not a float texture, fails the upload with PT_ERR_INVALID_ARGUMENT.  A
  * scene with a mask traces every ray with k_trace_alpha (k_trace_batch_alpha for the trace hooks). */
@@ -479,12 +503,14 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
 pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const float* wo, const float* u,
                          uint32_t flags, float* f_out, float* wi_out, float* pdf_out, uint32_t* type_out);
 /* Light `light` (index into the uploaded scene's light list) at n reference points ref_p (3 floats each), Light::sample_li for u (2 floats
- * each): li_out 3 floats, wi_out 3 floats, pdf_out 1 float (0 when sample_li returns None).  Infinite and area lights. */
+ * each): li_out 3 floats, wi_out 3 floats, pdf_out 1 float (0 when sample_li returns None).  Infinite, area and delta lights. */
 pt_status pt_light_sample_li(pt_context* ctx, uint32_t light, uint32_t n, const float* ref_p, const float* u, float* li_out, float* wi_out,
                              float* pdf_out);
-/* InfiniteAreaLight::pdf_li (infinite.rs:161-180) for n world directions wi (3 floats each).  Infinite lights only. */
+/* InfiniteAreaLight::pdf_li (infinite.rs:161-180) for n world directions wi (3 floats each).  Infinite lights; a delta light's is 0
+ * for every direction (point.rs:65-67, spot.rs:86-88, distant.rs:83-85). */
 pt_status pt_light_pdf_li(pt_context* ctx, uint32_t light, uint32_t n, const float* wi, float* pdf_out);
-/* InfiniteAreaLight::le (infinite.rs:111-122) for n world ray directions d (3 floats each): rgb_out 3 floats.  Infinite lights only. */
+/* InfiniteAreaLight::le (infinite.rs:111-122) for n world ray directions d (3 floats each): rgb_out 3 floats.  Infinite lights only (a delta
+ * light has no le: refused). */
 pt_status pt_light_le(pt_context* ctx, uint32_t light, uint32_t n, const float* d, float* rgb_out);
 /* Per-sample radiance (PathIntegrator::li after validate_radiance_result) for the
  * pixels of one tile: out is 3 floats per (pixel, sample), pixel-major. */

@@ -49,15 +49,23 @@ typedef struct {
     int32_t quick;
     int32_t quick_full_resolution;
     int32_t pixelsamples;
-    int32_t reserved;
+    int32_t delta_lights;            /* non-zero: LightSource "spot" and "distant" become pt_delta_light records; the pbrt_gpu command-line front
+                                      * end sets it.  0, and every entry point without options, goes on refusing them (PT_ERR_UNSUPPORTED).  A
+                                      * stop-gap: a test pins that refusal of the plain entry points; when it changes, taking the two directives
+                                      * becomes the default and this field goes back to reserved. */
 } pth_options;
 pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
 pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** out, char* err, size_t err_cap);
+/* The same with options (NULL: pth_parse_string). */
+pt_status pth_parse_string_opts(const char* text, const char* work_dir, const pth_options* opts, pth_scene** out, char* err, size_t err_cap);
 /* The flattened scene; pointers stay valid until pth_scene_free. */
 const pt_scene_desc* pth_scene_get_desc(const pth_scene* s);
 /* The scene's LightSource "infinite" lights (for pt_scene_set_infinite_lights); *n receives their count.  Valid until pth_scene_free. */
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n);
+/* The scene's LightSource "spot" / "distant" lights, parsed with pth_options.delta_lights (for pt_scene_set_delta_lights); *n receives their count.
+ * Valid until pth_scene_free. */
+const pt_delta_light* pth_scene_get_delta_lights(const pth_scene* s, uint32_t* n);
 /* The scene's alpha-masked meshes (for pt_scene_set_alpha_masks); *n receives their count.  Valid until pth_scene_free. */
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
 /* Integrator "aov": its "target" (a pt_aov_target, default uv) and "scale" (default 1), for pt_scene_set_aov.  Other integrators: the defaults. */

@@ -72,6 +72,14 @@ class pt_infinite_light(C.Structure):
                 ("light_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PT_DELTA_POINT, PT_DELTA_SPOT, PT_DELTA_DISTANT = range(3)
+
+
+class pt_delta_light(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("light_index", C.c_uint32), ("light_to_world", C.c_float * 16), ("world_to_light", C.c_float * 16),
+                ("spectrum", C.c_float * 3), ("cone_total_width", C.c_float), ("cone_falloff_start", C.c_float), ("direction", C.c_float * 3)]
+
+
 PT_ALPHA_NONE, PT_ALPHA_CONSTANT, PT_ALPHA_TEXTURE = range(3)
 
 
@@ -171,7 +179,7 @@ SYMBOLS = [
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le", "pt_scene_set_alpha_masks",
-    "pt_scene_set_aov",
+    "pt_scene_set_aov", "pt_scene_set_delta_lights",
 ]
 
 _lib = None
@@ -234,18 +242,23 @@ def tiles_array(tiles):
     return arr
 
 
-HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_scene_get_desc", "pth_scene_output_filename",
+HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_parse_string_opts", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
+
+
+class pth_options(C.Structure):
+    _fields_ = [("quick", C.c_int32), ("quick_full_resolution", C.c_int32), ("pixelsamples", C.c_int32), ("delta_lights", C.c_int32)]
 
 
 class ParsedScene:
     """A scene parsed from .pbrt text by the C++ front end (include/pbrtgpu_host.h).  Quacks like
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
-    def __init__(self, text=None, filename=None, work_dir=None, lib=None):
+    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False):
+        """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -262,8 +275,15 @@ class ParsedScene:
         L.pth_scene_free.restype = None
         self.h = C.c_void_p()
         err = C.create_string_buffer(2048)
-        if filename is not None:
+        opts = pth_options(0, 0, 0, 1)
+        if filename is not None and delta_lights:
+            L.pth_parse_file_opts.argtypes = [C.c_char_p, C.POINTER(pth_options), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+            st = L.pth_parse_file_opts(filename.encode(), C.byref(opts), C.byref(self.h), err, 2048)
+        elif filename is not None:
             st = L.pth_parse_file(filename.encode(), C.byref(self.h), err, 2048)
+        elif delta_lights:
+            L.pth_parse_string_opts.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(pth_options), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+            st = L.pth_parse_string_opts(text.encode(), (work_dir or ".").encode(), C.byref(opts), C.byref(self.h), err, 2048)
         else:
             st = L.pth_parse_string(text.encode(), (work_dir or ".").encode(), C.byref(self.h), err, 2048)
         if st != 0:
@@ -275,6 +295,11 @@ class ParsedScene:
         n_inf = C.c_uint32()
         arr = L.pth_scene_get_infinite_lights(self.h, C.byref(n_inf))
         self.infinite_lights = [arr[i] for i in range(n_inf.value)]       # LightSource "infinite" (copies)
+        L.pth_scene_get_delta_lights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.pth_scene_get_delta_lights.restype = C.POINTER(pt_delta_light)
+        n_dl = C.c_uint32()
+        dl = L.pth_scene_get_delta_lights(self.h, C.byref(n_dl))
+        self.delta_lights = [pt_delta_light.from_buffer_copy(dl[i]) for i in range(n_dl.value)]    # LightSource "spot" / "distant" (copies)
         L.pth_scene_get_alpha_masks.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.pth_scene_get_alpha_masks.restype = C.POINTER(pt_alpha_mask)
         n_am = C.c_uint32()
@@ -456,6 +481,9 @@ class Context:
         inf = list(getattr(scene, "infinite_lights", None) or [])
         arr = (pt_infinite_light * max(1, len(inf)))(*inf)
         self._check(self.lib.pt_scene_set_infinite_lights(self.h, C.c_uint32(len(inf)), arr if inf else None))
+        dls = list(getattr(scene, "delta_lights", None) or [])
+        dl_arr = (pt_delta_light * max(1, len(dls)))(*dls)
+        self._check(self.lib.pt_scene_set_delta_lights(self.h, C.c_uint32(len(dls)), dl_arr if dls else None))
         am = list(getattr(scene, "alpha_masks", None) or [])
         am_arr = (pt_alpha_mask * max(1, len(am)))(*am)
         self._check(self.lib.pt_scene_set_alpha_masks(self.h, C.c_uint32(len(am)), am_arr if am else None))
@@ -592,7 +620,7 @@ class Context:
         return li, wi, pdf
 
     def light_pdf_li(self, light, wi):
-        """InfiniteAreaLight::pdf_li for world directions wi."""
+        """InfiniteAreaLight::pdf_li for world directions wi; 0 for a delta light."""
         wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
         pdf = np.empty(len(wi), np.float32)
         self._check(self.lib.pt_light_pdf_li(self.h, C.c_uint32(light), C.c_uint32(len(wi)), _ptr(wi), _ptr(pdf)))

@@ -73,7 +73,7 @@ struct Rendezvous {
 
 static int32_t g_aov_target = PT_AOV_UV;      // Integrator "aov" of the parsed scene (pth_scene_get_aov), handed to every upload
 static float g_aov_scale = 1.0f;
-static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const pt_alpha_mask* am, uint32_t n_am, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
+static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const pt_delta_light* dl, uint32_t n_dl, const pt_alpha_mask* am, uint32_t n_am, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
                             double* secs_out, std::vector<RankReport>* reports, std::vector<float>* xyzw_out) {
     const int n_gpus = (int)devs.size();
     bool shared_device = false;
@@ -107,6 +107,7 @@ static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* i
     bool ok = each([&](int r) {
         if (!check(r, pt_context_create(devs[(size_t)r], &ctxs[(size_t)r]), "no usable HIP device")) return;
         if (!check(r, pt_scene_set_infinite_lights(ctxs[(size_t)r], n_inf, inf), "infinite lights")) return;
+        if (!check(r, pt_scene_set_delta_lights(ctxs[(size_t)r], n_dl, dl), "delta lights")) return;
         if (!check(r, pt_scene_set_alpha_masks(ctxs[(size_t)r], n_am, am), "alpha masks")) return;
         if (!check(r, pt_scene_set_aov(ctxs[(size_t)r], g_aov_target, g_aov_scale), "aov target")) return;
         check(r, pt_scene_upload(ctxs[(size_t)r], dsc), "scene upload");
@@ -212,6 +213,7 @@ int main(int argc, char** argv) {
         return cs == PT_OK ? 0 : 1;
     }
     opts.pixelsamples = spp;
+    opts.delta_lights = 1;           // LightSource "spot" / "distant" render here (pt_scene_set_delta_lights below)
     char err[1024] = {0};
     pth_scene* scene = nullptr;
     pt_status st = pth_parse_file_opts(input.c_str(), &opts, &scene, err, sizeof(err));
@@ -219,6 +221,8 @@ int main(int argc, char** argv) {
     if (!quiet && pth_scene_warnings(scene)[0]) std::fprintf(stderr, "%s", pth_scene_warnings(scene));
     uint32_t n_inf_lights = 0;
     const pt_infinite_light* inf_lights = pth_scene_get_infinite_lights(scene, &n_inf_lights);
+    uint32_t n_delta_lights = 0;
+    const pt_delta_light* delta_lights = pth_scene_get_delta_lights(scene, &n_delta_lights);
     uint32_t n_alpha_masks = 0;
     const pt_alpha_mask* alpha_masks = pth_scene_get_alpha_masks(scene, &n_alpha_masks);
     pth_scene_get_aov(scene, &g_aov_target, &g_aov_scale);
@@ -238,7 +242,7 @@ int main(int argc, char** argv) {
         double secs = 0;
         std::vector<RankReport> reports;
         std::vector<float> xyzw;
-        if (render_multi_gpu(pth_scene_get_desc(scene), inf_lights, n_inf_lights, alpha_masks, n_alpha_masks, devices, rgb, &info, &c, &secs, &reports, xyzw_file.empty() ? nullptr : &xyzw) != 0) { pth_scene_free(scene); return 1; }
+        if (render_multi_gpu(pth_scene_get_desc(scene), inf_lights, n_inf_lights, delta_lights, n_delta_lights, alpha_masks, n_alpha_masks, devices, rgb, &info, &c, &secs, &reports, xyzw_file.empty() ? nullptr : &xyzw) != 0) { pth_scene_free(scene); return 1; }
         if (!xyzw_file.empty() && !write_floats(xyzw_file, xyzw)) return 1;
         int w = info.cropped_bounds[2] - info.cropped_bounds[0], h = info.cropped_bounds[3] - info.cropped_bounds[1];
         const pt_scene_desc* dsc = pth_scene_get_desc(scene);
@@ -261,6 +265,7 @@ int main(int argc, char** argv) {
     if (st != PT_OK) { std::fprintf(stderr, "pbrt_gpu: no usable HIP device %d (there is no CPU fallback)\n", device); return 1; }
     auto fail = [&](const char* what) { std::fprintf(stderr, "pbrt_gpu: %s: %s\n", what, pt_last_error(ctx)); pt_context_destroy(ctx); pth_scene_free(scene); return 1; };
     if (pt_scene_set_infinite_lights(ctx, n_inf_lights, inf_lights) != PT_OK) return fail("infinite lights");
+    if (pt_scene_set_delta_lights(ctx, n_delta_lights, delta_lights) != PT_OK) return fail("delta lights");
     if (pt_scene_set_alpha_masks(ctx, n_alpha_masks, alpha_masks) != PT_OK) return fail("alpha masks");
     if (pt_scene_set_aov(ctx, g_aov_target, g_aov_scale) != PT_OK) return fail("aov target");
     if (pt_scene_upload(ctx, pth_scene_get_desc(scene)) != PT_OK) return fail("scene upload");

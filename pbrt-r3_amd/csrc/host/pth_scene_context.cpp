@@ -140,6 +140,8 @@ public:
     std::map<std::string, uint32_t> node_float_textures, node_spectrum_textures;   // name -> index into textures
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
+    std::vector<pt_delta_light> delta_lights;
+    bool accept_delta_lights = false;            // pth_options.delta_lights: LightSource "spot" / "distant" are taken (off: refused, as before)
     int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
     float aov_scale = 1.0f;
     std::vector<pt_alpha_mask> alpha_masks;                             // "alpha" / "shadowalpha" of trianglemesh / plymesh shapes, one per mesh
@@ -414,9 +416,68 @@ public:
         if (it == gstates.back().named_materials.end()) { warn("NamedMaterial \"" + name + "\" unknown."); return; }
         gstates.back().material = it->second;
     }
+    // create_spot_light (lights/spot.rs:136-162) and create_distant_light (lights/distant.rs:136-146): one pt_delta_light
+    void delta_light_source(const std::string& name, const ParamSet& p) {
+        const bool spot = name == "spot";
+        float I[3] = {1.0f, 1.0f, 1.0f}, sc[3] = {1.0f, 1.0f, 1.0f};
+        spectrum_from(p, spot ? "I" : "L", I);
+        spectrum_from(p, "scale", sc);
+        if (!error.empty()) return;
+        auto point_of = [&](const char* n, V3f d) { const std::vector<float>* v = p.get_points(n); return (v && v->size() == 3) ? V3f{(*v)[0], (*v)[1], (*v)[2]} : d; };
+        const V3f from = point_of("from", {0.0f, 0.0f, 0.0f}), to = point_of("to", {0.0f, 0.0f, 1.0f});
+        pt_delta_light dl;
+        std::memset(&dl, 0, sizeof(dl));
+        for (int k = 0; k < 3; k++) dl.spectrum[k] = I[k] * sc[k];
+        Xf l2w = transforms.back().t[0];                            // the CTM at the directive
+        if (spot) {
+            const float coneangle = p.find_one_float("coneangle", 30.0f);
+            const float conedelta = p.find_one_float("conedeltaangle", p.find_one_float("conedelta", 5.0f));
+            // Vector3f::coordinate_system, the normalising variant (vector3.rs:72-83), of the normalised direction
+            const V3f dir = normf(normf(sub(to, from)));
+            const V3f du = std::fabs(dir.x) > std::fabs(dir.y) ? normf({-dir.z, 0.0f, dir.x}) : normf({0.0f, dir.z, -dir.y});
+            const V3f dv = normf(crossf(dir, du));
+            Xf dir_to_z;
+            dir_to_z.m = pth::m_identity();
+            const float rows[3][3] = {{du.x, du.y, du.z}, {dv.x, dv.y, dv.z}, {dir.x, dir.y, dir.z}};
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) dir_to_z.m.a[4 * r + c] = rows[r][c];
+            if (!pth::m_inverse(dir_to_z.m, &dir_to_z.inv)) { fail("LightSource \"spot\": \"from\" and \"to\" give no direction"); return; }
+            l2w = pth::xf_mul(pth::xf_mul(l2w, pth::xf_translate(from.x, from.y, from.z)), pth::xf_inverse(dir_to_z));
+            dl.kind = PT_DELTA_SPOT;
+            dl.cone_total_width = coneangle;
+            dl.cone_falloff_start = coneangle - conedelta;
+        } else {
+            dl.kind = PT_DELTA_DISTANT;
+            const V3f d = sub(from, to);
+            dl.direction[0] = d.x; dl.direction[1] = d.y; dl.direction[2] = d.z;
+        }
+        for (int k = 0; k < 2; k++) {
+            const float* m = k ? l2w.inv.a : l2w.m.a;
+            if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f) { fail("LightSource \"" + name + "\" under a projective transform is not on the accelerated path"); return; }
+        }
+        std::memcpy(dl.light_to_world, l2w.m.a, 64);
+        std::memcpy(dl.world_to_light, l2w.inv.a, 64);
+        dl.light_index = n_world_lights++;                          // appended to scene.lights as the directive is read
+        delta_lights.push_back(dl);
+    }
     void pbrt_light_source(const std::string& name, const ParamSet& p) override {
+        if ((name == "spot" || name == "distant") && accept_delta_lights) { delta_light_source(name, p); return; }
+        if (name == "spot" || name == "distant") {
+            fail("LightSource \"" + name + "\": taken only when the caller asks for delta lights (pth_options.delta_lights; pbrt_gpu does); "
+                 "without the option only infinite lights and diffuse area lights are on the accelerated path");
+            return;
+        }
+        if (name == "goniometric" || name == "projection") {
+            fail("LightSource \"" + name + "\": goniometric and projection lights (image lookups per sample) are not on the accelerated path");
+            return;
+        }
+        if (name == "point") {       // complete below the front end (pt_delta_light kind PT_DELTA_POINT, SceneBuilder.light_point); the directive is still refused
+            fail("LightSource \"point\": not enabled in the .pbrt front end yet (the C ABI and SceneBuilder.light_point take point lights); "
+                 "spot, distant and infinite lights and diffuse area lights are on the accelerated path");
+            return;
+        }
         if (name != "infinite" && name != "exinfinite") {          // create_light.rs:29: "exinfinite" is the same light
-            fail("LightSource \"" + name + "\": only infinite lights and diffuse area lights are on the accelerated path");
+            fail("LightSource \"" + name + "\": only infinite, spot and distant lights and diffuse area lights are on the accelerated path");
             return;
         }
         // create_infinite_light (lights/infinite.rs:273-293): L * scale, "mapname", "samples" falling back to "nsamples"
@@ -1085,6 +1146,19 @@ static pt_status finish(pth_scene* s, bool parsed, const std::string& perr, pth_
     return PT_OK;
 }
 
+// pth_options before the parse (what acts while the scene is assembled) and after it (--pixelsamples), for both parse entry points
+static void apply_options(pth_scene* s, const pth_options* opts) {
+    if (!opts) return;
+    s->ctx.quick_render = opts->quick != 0 || opts->quick_full_resolution != 0;     // bin/pbrt.rs:360-366
+    s->ctx.quick_full_resolution = opts->quick_full_resolution != 0;
+    s->ctx.accept_delta_lights = opts->delta_lights != 0;
+}
+static pt_status finish_with_options(pth_scene* s, bool ok, const std::string& perr, const pth_options* opts, pth_scene** out, char* err, size_t err_cap) {
+    pt_status st = finish(s, ok, perr, out, err, err_cap);
+    if (st == PT_OK && opts && opts->pixelsamples > 0) (*out)->ctx.desc.spp = opts->pixelsamples;   // bin/pbrt.rs:234-238
+    return st;
+}
+
 extern "C" {
 
 pt_status pth_parse_file(const char* filename, pth_scene** out, char* err, size_t err_cap) {
@@ -1093,24 +1167,27 @@ pt_status pth_parse_file(const char* filename, pth_scene** out, char* err, size_
 pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth_scene** out, char* err, size_t err_cap) {
     if (!filename || !out) return PT_ERR_INVALID_ARGUMENT;
     pth_scene* s = new pth_scene;
-    if (opts) {
-        s->ctx.quick_render = opts->quick != 0 || opts->quick_full_resolution != 0;     // bin/pbrt.rs:360-366
-        s->ctx.quick_full_resolution = opts->quick_full_resolution != 0;
-    }
+    apply_options(s, opts);
     std::string perr;
     bool ok = pth::pbrt_parse_file(filename, s->ctx, &perr);
-    pt_status st = finish(s, ok, perr, out, err, err_cap);
-    if (st == PT_OK && opts && opts->pixelsamples > 0) (*out)->ctx.desc.spp = opts->pixelsamples;   // bin/pbrt.rs:234-238
-    return st;
+    return finish_with_options(s, ok, perr, opts, out, err, err_cap);
 }
 pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** out, char* err, size_t err_cap) {
+    return pth_parse_string_opts(text, work_dir, nullptr, out, err, err_cap);
+}
+pt_status pth_parse_string_opts(const char* text, const char* work_dir, const pth_options* opts, pth_scene** out, char* err, size_t err_cap) {
     if (!text || !out) return PT_ERR_INVALID_ARGUMENT;
     pth_scene* s = new pth_scene;
+    apply_options(s, opts);
     std::string perr;
     bool ok = pth::pbrt_parse_string(text, work_dir ? work_dir : ".", s->ctx, &perr);
-    return finish(s, ok, perr, out, err, err_cap);
+    return finish_with_options(s, ok, perr, opts, out, err, err_cap);
 }
 const pt_scene_desc* pth_scene_get_desc(const pth_scene* s) { return s ? &s->ctx.desc : nullptr; }
+const pt_delta_light* pth_scene_get_delta_lights(const pth_scene* s, uint32_t* n) {
+    if (n) *n = s ? (uint32_t)s->ctx.delta_lights.size() : 0u;
+    return (s && !s->ctx.delta_lights.empty()) ? s->ctx.delta_lights.data() : nullptr;
+}
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.infinite_lights.size() : 0u;
     return (s && !s->ctx.infinite_lights.empty()) ? s->ctx.infinite_lights.data() : nullptr;

@@ -66,6 +66,7 @@ struct pt_context {
     PtScene sc;
     pt_scene_info info;
     std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
+    std::vector<pt_delta_light> delta_lights;       // pt_scene_set_delta_lights: the next upload's point / spot / distant lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
     int32_t next_aov_target = PT_AOV_UV;            // pt_scene_set_aov: the next upload's AOV target and scale (create_aov_integrator's defaults)
     float next_aov_scale = 1.0f;
@@ -543,6 +544,12 @@ pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_inf
     return PT_OK;
 }
 
+pt_status pt_scene_set_delta_lights(pt_context* ctx, uint32_t n, const pt_delta_light* lights) {
+    if (!ctx || (n && !lights)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->delta_lights.assign(lights, lights + n);
+    return PT_OK;
+}
+
 pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_mask* masks) {
     if (!ctx || (n && !masks)) return PT_ERR_INVALID_ARGUMENT;
     ctx->alpha_masks.assign(masks, masks + n);
@@ -564,6 +571,7 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (!ctx || !d) return PT_ERR_INVALID_ARGUMENT;
     const pt_status st = scene_upload(ctx, d);
     ctx->inf_lights.clear();
+    ctx->delta_lights.clear();
     ctx->alpha_masks.clear();
     ctx->next_aov_target = PT_AOV_UV;
     ctx->next_aov_scale = 1.0f;
@@ -661,6 +669,14 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             im.n_levels == 0 || im.n_levels > PT_MAX_MIP_LEVELS || im.width > (1u << 14) || im.height > (1u << 14))
             return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: its image is not a power-of-two pyramid of 1 or 3 channels (at most 16384 wide)");
         if (il.n_samples < 0 || il.n_samples > 4096) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "infinite light: n_samples outside [0, 4096]");
+    }
+    for (const pt_delta_light& dl : ctx->delta_lights) {
+        if (dl.kind < PT_DELTA_POINT || dl.kind > PT_DELTA_DISTANT) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "delta light: unknown kind");
+        for (int k = 0; k < 2; k++) {
+            const float* m = k ? dl.world_to_light : dl.light_to_world;
+            if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f)
+                return ctx->fail(PT_ERR_UNSUPPORTED, "delta light under a projective transform (last matrix row must be 0 0 0 1)");
+        }
     }
     // alpha masks: one record per mesh, float textures only (a texture whose channels are equal wherever it is evaluated)
     std::vector<uint8_t> mesh_alpha(d->n_meshes, 0);    // 1: the mesh's triangles carry PT_TRI_ALPHA
@@ -1313,19 +1329,22 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     if (up_n_nodes >= (1u << 25)) return ctx->fail(PT_ERR_UNSUPPORTED, "more than 2^25 BVH nodes (32-bit node offsets)");
     ctx->n_nodes_up = up_n_nodes; ctx->n_tris_up = up_n_tris;
     if ((st = upload(ctx, ctx->d_materials, mats.data(), mats.size())) != PT_OK) return st;
-    {   // infinite lights: their records at their places in the light list (scene_context.rs:1178-1188), in directive order
-        std::vector<uint32_t> order(ctx->inf_lights.size());
-        for (uint32_t k = 0; k < order.size(); k++) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ctx->inf_lights[a].light_index < ctx->inf_lights[b].light_index; });
+    {   // infinite and delta lights: their records at their places in the light list (scene_context.rs:1178-1188), in directive order
+        const uint32_t n_inf = (uint32_t)ctx->inf_lights.size(), n_all = n_inf + (uint32_t)ctx->delta_lights.size();
+        auto index_of = [&](uint32_t k) { return k < n_inf ? ctx->inf_lights[k].light_index : ctx->delta_lights[k - n_inf].light_index; };
+        std::vector<uint32_t> order(n_all);
+        for (uint32_t k = 0; k < n_all; k++) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return index_of(a) < index_of(b); });
         for (uint32_t k : order) {
             PtLight L;
             std::memset(&L, 0, sizeof(L));
-            std::memcpy(&L.p0[0], &k, 4);
-            L.mesh_flags = PT_LIGHT_INFINITE;
+            const uint32_t side = k < n_inf ? k : k - n_inf;          // index of its PtEnvLight / PtDeltaLight record
+            std::memcpy(&L.p0[0], &side, 4);
+            L.mesh_flags = k < n_inf ? PT_LIGHT_INFINITE : PT_LIGHT_DELTA;
             L.tri_rec = 0xffffffffu;
             L.prim = 0xffffffffu;
-            L.n_samples = (uint32_t)std::max(1, ctx->inf_lights[k].n_samples);
-            const size_t at = std::min<size_t>(ctx->inf_lights[k].light_index, lights.size());
+            L.n_samples = k < n_inf ? (uint32_t)std::max(1, ctx->inf_lights[k].n_samples) : 1u;        // BaseLight::new(.., 1) for the three delta lights
+            const size_t at = std::min<size_t>(index_of(k), lights.size());
             lights.insert(lights.begin() + (ptrdiff_t)at, L);
         }
     }
@@ -1408,11 +1427,50 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     for (int a = 0; a < 3; a++) { const float ext = up_root_hi[a] - up_root_lo[a]; sc.cell_scale[a] = ext > 0.0f ? (float)(1u << PT_SORT_CELL_BITS) / ext : 0.0f; }
     std::memcpy(sc.wb_min, up_root_lo, 12);
     std::memcpy(sc.wb_max, up_root_hi, 12);
-    std::vector<float> env_power(ctx->inf_lights.size(), 0.0f);
+    std::vector<float> env_power(ctx->inf_lights.size(), 0.0f), delta_power(ctx->delta_lights.size(), 0.0f);
     sc.n_envs = 0;
+    sc.n_deltas = 0;
+    std::vector<PtEnvLight> envs(ctx->inf_lights.size());
+    std::vector<PtDeltaLight> deltas(ctx->delta_lights.size());
+    if (!ctx->delta_lights.empty()) {    // PtDeltaLight records: what PointLight::new / SpotLight::new / DistantLight::new + preprocess compute
+        const float kPiF = 3.14159265358979323846f;
+        const float dx = sc.wb_max[0] - sc.wb_min[0], dy = sc.wb_max[1] - sc.wb_min[1], dz = sc.wb_max[2] - sc.wb_min[2];
+        const float radius = std::sqrt(dx * dx + dy * dy + dz * dz) * 0.5f;          // Bounds3::bounding_sphere (bounds3.rs:173-177)
+        auto lum = [](float r, float g, float b) { return 0.212671f * r + 0.715160f * g + 0.072169f * b; };
+        for (size_t k = 0; k < deltas.size(); k++) {
+            const pt_delta_light& dl = ctx->delta_lights[k];
+            PtDeltaLight& o = deltas[k];
+            std::memset(&o, 0, sizeof(o));
+            o.kind = (uint32_t)dl.kind;
+            std::memcpy(o.spectrum, dl.spectrum, 12);
+            const float* m = dl.light_to_world;
+            float s = 0.0f;
+            if (dl.kind == PT_DELTA_DISTANT) {
+                // w_light = normalize(light_to_world.transform_vector(from - to)) (distant.rs:28); power = L * (pi r^2) (:77-81)
+                const float x = dl.direction[0], y = dl.direction[1], z = dl.direction[2];
+                const float vx = m[0] * x + m[1] * y + m[2] * z, vy = m[4] * x + m[5] * y + m[6] * z, vz = m[8] * x + m[9] * y + m[10] * z;
+                const float len = std::sqrt(vx * vx + vy * vy + vz * vz);
+                o.v[0] = vx / len; o.v[1] = vy / len; o.v[2] = vz / len;
+                o.radius = radius;
+                s = kPiF * radius * radius;
+            } else {
+                // p_light = light_to_world.transform_point(0) (point.rs:33, spot.rs:32; matrix4x4.rs:284-297 with w = 1 for an affine matrix)
+                for (int a = 0; a < 3; a++) o.v[a] = m[4 * a] * 0.0f + m[4 * a + 1] * 0.0f + m[4 * a + 2] * 0.0f + m[4 * a + 3];
+                if (dl.kind == PT_DELTA_SPOT) {
+                    o.cos_total_width = std::cos(dl.cone_total_width * (kPiF / 180.0f));        // spot.rs:13-16, :34-35
+                    o.cos_falloff_start = std::cos(dl.cone_falloff_start * (kPiF / 180.0f));
+                    for (int a = 0; a < 3; a++)
+                        for (int b = 0; b < 3; b++) o.w2l[3 * a + b] = dl.world_to_light[4 * a + b];
+                    s = 2.0f * kPiF * (1.0f - 0.5f * (o.cos_falloff_start - o.cos_total_width));      // spot.rs:81-84
+                } else {
+                    s = 4.0f * kPiF;                                                                   // point.rs:61-63
+                }
+            }
+            delta_power[k] = lum(o.spectrum[0] * s, o.spectrum[1] * s, o.spectrum[2] * s);
+        }
+    }
     if (!ctx->inf_lights.empty()) {      // PtEnvLight records + their Distribution2D tables (one buffer; its bytes are gone from what the path pool may take)
         const size_t ne = ctx->inf_lights.size();
-        std::vector<PtEnvLight> envs(ne);
         std::vector<std::vector<float>> tabs(ne);
         std::vector<size_t> tab_off(ne);
         size_t total = 0;
@@ -1449,16 +1507,21 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             e.mfunc = e.cdf + (size_t)e.nv * (e.nu + 1);
             e.mcdf = e.mfunc + e.nv;
         }
-        std::vector<uint8_t> lbuf(lights.size() * sizeof(PtLight) + ne * sizeof(PtEnvLight));       // the records behind the lights (scene_envs)
-        std::memcpy(lbuf.data(), lights.data(), lights.size() * sizeof(PtLight));
-        std::memcpy(lbuf.data() + lights.size() * sizeof(PtLight), envs.data(), ne * sizeof(PtEnvLight));
+    } else { ctx->d_env_tabs.release(); }
+    if (!envs.empty() || !deltas.empty()) {
+        const size_t ne = envs.size(), nd = deltas.size(), lb = lights.size() * sizeof(PtLight);
+        std::vector<uint8_t> lbuf(lb + ne * sizeof(PtEnvLight) + nd * sizeof(PtDeltaLight));       // the records behind the lights (scene_envs, scene_deltas)
+        std::memcpy(lbuf.data(), lights.data(), lb);
+        if (ne) std::memcpy(lbuf.data() + lb, envs.data(), ne * sizeof(PtEnvLight));
+        if (nd) std::memcpy(lbuf.data() + lb + ne * sizeof(PtEnvLight), deltas.data(), nd * sizeof(PtDeltaLight));
         if ((st = upload(ctx, ctx->d_lights, lbuf.data(), lbuf.size())) != PT_OK) return st;
         sc.lights = ctx->d_lights.as<PtLight>();
         sc.n_envs = (uint32_t)ne;
+        sc.n_deltas = (uint32_t)nd;
         // the hit records were numbered over the area lights alone: give every emitter its index in the merged list
         PT_HIP(ptk_light_renumber(ctx->stream, ctx->d_tris.as<PtTri>(), ctx->d_tri_info.p ? ctx->d_tri_info.as<PtTriInfo>() : nullptr, sc.lights, (uint32_t)lights.size()));
         PT_HIP(hipStreamSynchronize(ctx->stream));
-    } else { ctx->d_env_tabs.release(); }
+    }
     sc.max_depth = d->max_depth;
     sc.integrator = d->integrator;
     ctx->aov_target = ctx->next_aov_target;
@@ -1605,6 +1668,10 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
                     uint32_t k;
                     std::memcpy(&k, &lights[i].p0[0], 4);
                     tab[i] = env_power[k];
+                } else if (lights[i].mesh_flags & PT_LIGHT_DELTA) {
+                    uint32_t k;
+                    std::memcpy(&k, &lights[i].p0[0], 4);
+                    tab[i] = delta_power[k];
                 } else {
                     float n = lights[i].two_sided ? 2.0f : 1.0f;
                     float s = n * lights[i].area * 3.14159265358979323846f;
@@ -2480,6 +2547,10 @@ static pt_status light_hook(pt_context* ctx, uint32_t light, uint32_t mode, uint
     if (mode != 0) {
         PtLight L;
         PT_HIP(hipMemcpy(&L, ctx->d_lights.as<PtLight>() + light, sizeof(L), hipMemcpyDeviceToHost));
+        if (mode == 1 && (L.mesh_flags & PT_LIGHT_DELTA)) {         // pdf_li of a delta light is 0 for every direction
+            if (n) std::memset(o1, 0, (size_t)n * 4);
+            return PT_OK;
+        }
         if (!(L.mesh_flags & PT_LIGHT_INFINITE)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_light_pdf_li / pt_light_le: not an infinite light");
     }
     if (n == 0) return PT_OK;

@@ -203,6 +203,19 @@ struct PtEnvLight {
     float m_int;                 // the marginal's func_int
     uint32_t pad[3];
 };
+#define PT_LIGHT_DELTA 0x20000000u    // PtLight::mesh_flags: a PointLight / SpotLight / DistantLight, side record scene_deltas(sc)[bits(p0[0])]; tri_rec = ~0u
+// The delta lights (lights/point.rs, spot.rs, distant.rs) as their constructors leave them: every field is computed at upload from a
+// pt_delta_light.  Their estimate has no MIS weight and no probe ray (sample_lights.rs:380-397).
+struct PtDeltaLight {            // 80 bytes
+    uint32_t kind;               // PT_DELTA_POINT / PT_DELTA_SPOT / PT_DELTA_DISTANT
+    float v[3];                  // p_light (point, spot) or w_light (distant)
+    float spectrum[3];           // I (point, spot) or L (distant), scale included
+    float cos_total_width;       // spot: cos(radians(coneangle)), f32 on the host
+    float cos_falloff_start;     // spot: cos(radians(coneangle - conedelta))
+    float radius;                // distant: the world bound's bounding-sphere radius (PtEnvLight::radius)
+    float w2l[9];                // spot: rows 0..2 of world_to_light.m, the 3 x 3 part transform_vector reads (SpotLight::falloff)
+    uint32_t pad;
+};
 
 struct PtCamera {
     float raster_to_camera[16];
@@ -270,6 +283,8 @@ struct PtScene {
     uint32_t dist_leaves;        // 1: no leaf holds more than 8 triangles, k_trace spreads leaf tests over the wave
     uint32_t any_one_sided;      // 1: some triangle is one-sided ("twosided" false): leaf rounds also need the ray direction
     uint32_t general_materials;  // 1 when any material is not Matte: k_shade_general runs instead of k_shade
+    uint32_t n_deltas;           // delta lights (PtLight records with PT_LIGHT_DELTA; side records: scene_deltas); > 0: the *_env kernels run.  (It sits in
+                                 // what was the alignment hole before `nodes`: PtScene keeps its size and every other field its offset.)
     const PtNode* nodes;
     const PtTri* tris;
     const PtTriInfo* tri_info;
@@ -303,6 +318,10 @@ struct PtScene {
 };
 // The infinite lights' PtEnvLight records follow the n_lights PtLight records in the same buffer (PtScene keeps its size and layout).
 PT_HOSTDEV_ENVS inline const PtEnvLight* scene_envs(const PtScene& sc) { return reinterpret_cast<const PtEnvLight*>(sc.lights + sc.n_lights); }
+// ... and the delta lights' PtDeltaLight records follow those.
+PT_HOSTDEV_ENVS inline const PtDeltaLight* scene_deltas(const PtScene& sc) { return reinterpret_cast<const PtDeltaLight*>(scene_envs(sc) + sc.n_envs); }
+static_assert(sizeof(PtDeltaLight) == 80 && sizeof(PtEnvLight) % 8 == 0 && sizeof(PtLight) % 16 == 0, "side records of the light buffer");
+static_assert(__builtin_offsetof(PtScene, nodes) == 16, "n_deltas fills the hole in front of PtScene::nodes");
 
 // ---- wavefront path pool (SoA, one slot per in-flight camera sample)
 struct PtPaths {

@@ -2194,8 +2194,39 @@ PT_DEV V3 env_le_all(const PtScene& sc, V3 d) {
     for (uint32_t k = 0; k < sc.n_envs; k++) r = r + env_le(sc, scene_envs(sc)[k], d);
     return r;
 }
-// Light::sample_li of any light kind; an infinite light's visibility target is p + wi * 2r, an interaction without error or normal
-template <bool SPH, bool ENV>
+// ---- the delta lights (lights/point.rs:44-59, spot.rs:45-79, distant.rs:55-75).  sample_li always returns Some with pdf 1; the visibility
+// target is a bare interaction (no error, no normal) at p_light, or at p + w_light * 2r for the distant light -- the infinite light's target.
+PT_DEV float spot_falloff(const PtDeltaLight& dl, V3 w) {
+    const V3 wl = normalize(mk3(dl.w2l[0] * w.x + dl.w2l[1] * w.y + dl.w2l[2] * w.z, dl.w2l[3] * w.x + dl.w2l[4] * w.y + dl.w2l[5] * w.z,
+                                dl.w2l[6] * w.x + dl.w2l[7] * w.y + dl.w2l[8] * w.z));
+    const float cos_theta = wl.z;
+    if (cos_theta < dl.cos_total_width) return 0.0f;
+    if (cos_theta >= dl.cos_falloff_start) return 1.0f;
+    const float delta = (cos_theta - dl.cos_total_width) / (dl.cos_falloff_start - dl.cos_total_width);
+    return (delta * delta) * (delta * delta);
+}
+PT_DEV void delta_sample_li(const PtDeltaLight& dl, V3 ref_p, V3* li, V3* wi, float* pdf, V3* lp) {
+    const V3 v = ld3(dl.v), sp = ld3(dl.spectrum);
+    *pdf = 1.0f;
+    if (dl.kind == PT_DELTA_DISTANT) {
+        *wi = v;
+        *li = sp;
+        *lp = ref_p + v * (2.0f * dl.radius);
+        return;
+    }
+    *wi = normalize(v - ref_p);
+    const float d2 = distance_squared(v, ref_p);
+    if (dl.kind == PT_DELTA_SPOT) *li = sp * (spot_falloff(dl, -*wi) / d2);        // the scalar quotient first (spot.rs:72-73)
+    else *li = sp / d2;
+    *lp = v;
+}
+// whether light l is a delta light (Light::is_delta): only the DELTA instantiations can meet one
+template <bool DELTA>
+PT_DEV bool light_is_delta(const PtLight& l) { if constexpr (DELTA) return (l.mesh_flags & PT_LIGHT_DELTA) != 0; else return false; }
+// Light::sample_li of any light kind; an infinite light's visibility target is p + wi * 2r, an interaction without error or normal.
+// DELTA: the scene may hold delta lights.  The whole-vertex shading kernels of scenes with infinite lights alone (k_shade_env, k_shade_env_inst)
+// are built without it: the branch costs them 50 more spilled registers, and they stay at what they took before.
+template <bool SPH, bool ENV, bool DELTA = ENV>
 PT_DEV bool light_sample_kind(const PtScene& sc, const PtLight& l, V3 ref_p, V3 ref_pe, V3 ref_n, V2 u, V3* li, V3* wi, float* pdf, V3* lp, V3* lperr,
                               V3* ln) {
     if constexpr (ENV) {
@@ -2205,6 +2236,13 @@ PT_DEV bool light_sample_kind(const PtScene& sc, const PtLight& l, V3 ref_p, V3 
             *lp = ref_p + *wi * (2.0f * e.radius);
             *lperr = mk3(0.0f, 0.0f, 0.0f); *ln = mk3(0.0f, 0.0f, 0.0f);
             return true;
+        }
+        if constexpr (DELTA) {
+            if (l.mesh_flags & PT_LIGHT_DELTA) {
+                delta_sample_li(scene_deltas(sc)[__float_as_uint(l.p0[0])], ref_p, li, wi, pdf, lp);
+                *lperr = mk3(0.0f, 0.0f, 0.0f); *ln = mk3(0.0f, 0.0f, 0.0f);
+                return true;
+            }
         }
     }
     return light_sample_any<SPH>(sc, l, ref_p, ref_pe, ref_n, u, li, wi, pdf, lp, lperr, ln);
@@ -2592,7 +2630,8 @@ PT_DEV float opaque_zero() { float z = 0.0f; asm volatile("" : "+v"(z)); return 
 // sample dimensions were drawn); 2 = everything else (emission, pass-through, continuation, Russian roulette), run AFTER part 1 on the same
 // list because it overwrites the ray.  Both halves rebuild the interaction from (ray, record): the split trades that for register room.
 // ENV: the scene has an infinite light (the *_env kernels): escaped rays add its Le, next-event estimation samples it.
-template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false>
+// DELTA (with ENV): the scene has a delta light (k_shade_delta, k_shade_delta_inst): its estimate is f Li / pdf with no power heuristic, no BSDF half, no probe ray.
+template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false, bool DELTA = false>
 PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, const uint32_t* list, uint32_t begin, uint32_t end,
                        uint32_t* ticket) {
     __shared__ unsigned long long s_vert;
@@ -2925,7 +2964,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             V3 li, wi, lp, lperr, ln;
                             float lpdf;
                             bool sampled;
-                            if constexpr (ENV) sampled = light_sample_kind<SPH, true>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
+                            if constexpr (ENV) sampled = light_sample_kind<SPH, true, DELTA>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
                             else sampled = light_sample_any<SPH>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
                             if (sampled) {
                                 if (lpdf > 0.0f && !is_black(li)) {
@@ -2940,8 +2979,11 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                         s_stage[1][threadIdx.x] = make_float4(sd.x, sd.y, sd.z, 0.0f);
                                         if (Q.shadow_key) s_pkey[n_batch][threadIdx.x] = ray_sort_key(sc, origin, sd);
                                         wr |= 4u; PT_COMMIT_NOW(1);
-                                        float weight = power_heuristic(lpdf, spdf);
-                                        A = f * li * (weight / lpdf);
+                                        if (light_is_delta<DELTA>(lt)) A = f * li / lpdf;          // no power heuristic (sample_lights.rs:380-381)
+                                        else {
+                                            float weight = power_heuristic(lpdf, spdf);
+                                            A = f * li * (weight / lpdf);
+                                        }
                                         nee |= PT_NEE_SHADOW;
                                     }
                                 }
@@ -2951,7 +2993,8 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             V3 f2, wi2;
                             float spdf2;
                             uint32_t type2;      // never specular: the flags exclude BSDF_SPECULAR (sample_lights.rs:343-347)
-                            if (sample_bsdf(s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
+                            // (a delta light: the whole branch is skipped, no probe ray -- sample_lights.rs:397)
+                            if (!light_is_delta<DELTA>(lt) && sample_bsdf(s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
                                 V3 f = f2 * abs_dot(wi2, s.sh_n);
                                 if (!is_black(f) && spdf2 > 0.0f) {
                                     // light.pdf_li -> Shape::pdf_from (shape.rs:40-54): one test against the light's own triangle
@@ -3261,6 +3304,13 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_sha
 }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_env_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
+// Scenes with a delta light (with or without infinite lights): the same two kernels with the delta branch of next-event estimation
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_delta(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, false, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_delta_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, true, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 
 // ============================================================ film
@@ -3695,8 +3745,11 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
                 V3 sd = target - origin;
                 R.sh_o[e] = make_float4(origin.x, origin.y, origin.z, 1.0f - PT_SHADOW_EPS);
                 R.sh_d[e] = make_float4(sd.x, sd.y, sd.z, 0.0f);
-                float weight = power_heuristic(lpdf, spdf);
-                A = f * li * (weight / lpdf);
+                if (light_is_delta<ENV>(lt)) A = f * li / lpdf;
+                else {
+                    float weight = power_heuristic(lpdf, spdf);
+                    A = f * li * (weight / lpdf);
+                }
                 nee |= PT_NEE_SHADOW;
             }
         }
@@ -3704,7 +3757,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
     V3 f2, wi2;
     float spdf2;
     uint32_t type2;
-    if (gbsdf_sample_f(nd.gb, s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
+    if (!light_is_delta<ENV>(lt) && gbsdf_sample_f(nd.gb, s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
         V3 f = f2 * abs_dot(wi2, s.sh_n);
         if (!is_black(f) && spdf2 > 0.0f) {
             V3 po = offset_ray_origin(s.p, s.p_error, s.n, wi2);
@@ -4193,13 +4246,13 @@ hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPat
 hipError_t ptk_rec_enter(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtQueues& Qn, const PtRec& R, PtCounters* cnt,
                          uint32_t lights_per_node) {
     (void)lights_per_node;
-    if (sc.n_envs) hipLaunchKernelGGL(k_rec_enter_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
+    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_enter_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_enter, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     else hipLaunchKernelGGL(k_rec_enter_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     return hipGetLastError();
 }
 hipError_t ptk_rec_next(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtRec& R) {
-    if (sc.n_envs) hipLaunchKernelGGL(k_rec_next_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
+    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_next_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_next, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     else hipLaunchKernelGGL(k_rec_next_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     return hipGetLastError();
@@ -4340,7 +4393,7 @@ hipError_t ptk_trace(hipStream_t st, int grid, int grid_dist, const PtScene& sc,
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_nee_resolve(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q) {
-    if (sc.n_envs) hipLaunchKernelGGL(k_nee_resolve_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
+    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_nee_resolve_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
     else hipLaunchKernelGGL(k_nee_resolve, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
     return PT_LAUNCH_CHECK();
 }
@@ -4348,7 +4401,7 @@ hipError_t ptk_nee_resolve(hipStream_t st, int grid, const PtScene& sc, const Pt
 // (light1, tri_info.light) were numbered without them
 extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_renumber(PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || (lights[i].mesh_flags & PT_LIGHT_INFINITE)) return;
+    if (i >= n || (lights[i].mesh_flags & (PT_LIGHT_INFINITE | PT_LIGHT_DELTA))) return;
     const uint32_t r = lights[i].tri_rec;
     tris[r].light1 = i + 1u;
     if (tinfo) tinfo[r].light = (int32_t)i;
@@ -4507,10 +4560,12 @@ hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode) {
 }
 int ptk_nee_split_default() { return PT_NEE_SPLIT_DEFAULT; }
 hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nsplit, int local_sort) {
-    if (sc.n_envs) {
-        // an infinite light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort, the split next-event kernels
+    if (sc.n_envs || sc.n_deltas) {
+        // an infinite or a delta light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort, the split next-event kernels
         // (PBRTGPU_NEE_SPLIT), the local sort (PBRTGPU_SHADE_LOCAL), the textured split (PBRTGPU_TEX_SPLIT) and PBRTGPU_SHADE_UNSORTED are routed around
-        if (sc.n_instances) hipLaunchKernelGGL(k_shade_env_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        if (sc.n_deltas && sc.n_instances) hipLaunchKernelGGL(k_shade_delta_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        else if (sc.n_deltas) hipLaunchKernelGGL(k_shade_delta, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        else if (sc.n_instances) hipLaunchKernelGGL(k_shade_env_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         else hipLaunchKernelGGL(k_shade_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         return PT_LAUNCH_CHECK();
     }
@@ -4611,7 +4666,7 @@ hipError_t ptk_light_grid(hipStream_t st, const PtScene& sc, float* data, uint32
     if (jobs == 0) return hipSuccess;
     const uint64_t batches = (jobs + 63) / 64;          // kGridBatch pairs each
     const uint32_t grid = (uint32_t)(batches < 2048u ? batches : 2048u);
-    if (sc.n_envs) hipLaunchKernelGGL(k_light_grid_env, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
+    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_light_grid_env, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
     else if (sc.n_spheres) hipLaunchKernelGGL(k_light_grid_sph, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
     else hipLaunchKernelGGL(k_light_grid, dim3(grid), dim3(128), 0, st, sc, data, n_vox, vox_list);
     hipLaunchKernelGGL(k_light_grid_cdf, dim3((n_vox + 63) / 64), dim3(64), 0, st, sc, data, n_vox);

@@ -186,6 +186,55 @@ def transform_mul(t1, t2):
     return _mul4(t1[0], t2[0]), _mul4(t2[1], t1[1])
 
 
+def matrix_inverse(m):
+    """Matrix4x4::inverse (matrix4x4.rs:231-282): Gauss-Jordan elimination with full pivoting in f32, the reference's pivot and operation
+    order (what Transform::from(Matrix4x4) stores as m_inv).  None for a singular matrix."""
+    w = np.array(m, np.float32).reshape(4, 4).copy()
+    used, row_of, col_of = [0, 0, 0, 0], [0] * 4, [0] * 4
+    for step in range(4):
+        prow = pcol = 0
+        best = f32(0.0)
+        for r in range(4):
+            if used[r] == 1:
+                continue
+            for c in range(4):
+                if used[c] == 0:
+                    v = np.abs(w[r, c])
+                    if v >= best:
+                        best, prow, pcol = v, r, c
+                elif used[c] > 1:
+                    return None
+        used[pcol] += 1
+        if prow != pcol:
+            w[[prow, pcol]] = w[[pcol, prow]]
+        row_of[step], col_of[step] = prow, pcol
+        if w[pcol, pcol] == 0:
+            return None
+        inv = f32(1.0) / w[pcol, pcol]
+        w[pcol, pcol] = f32(1.0)
+        w[pcol] = w[pcol] * inv
+        for r in range(4):
+            if r == pcol:
+                continue
+            f = w[r, pcol]
+            w[r, pcol] = f32(0.0)
+            w[r] = w[r] - w[pcol] * f
+    for step in range(3, -1, -1):
+        if row_of[step] != col_of[step]:
+            w[:, [row_of[step], col_of[step]]] = w[:, [col_of[step], row_of[step]]]
+    return w.reshape(-1)
+
+
+def coordinate_system(d):
+    """Vector3f::coordinate_system, the normalising variant (vector3.rs:72-83): (v1, v2, v3)."""
+    v1 = _normalize(_v(*d))
+    if np.abs(v1[0]) > np.abs(v1[1]):
+        v2 = _normalize(_v(-v1[2], 0.0, v1[0]))
+    else:
+        v2 = _normalize(_v(0.0, v1[2], -v1[1]))
+    return v1, v2, _normalize(_cross(v1, v2))
+
+
 def _swaps_handedness(m):
     m = np.asarray(m, np.float32)
     det = (m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8])) + m[2] * (m[4] * m[9] - m[5] * m[8])
@@ -243,6 +292,7 @@ class SceneBuilder:
         self.textures = []
         self.images = []            # (pt_image, texel buffer)
         self.infinite_lights = []   # capi.pt_infinite_light, in directive order
+        self.delta_lights = []      # capi.pt_delta_light (point, spot, distant), in directive order
         self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
         self.instances = []
         self.objects = {}           # name -> object index
@@ -577,16 +627,59 @@ class SceneBuilder:
         il.world_to_light[:] = [float(v) for v in minv.astype(np.float32).reshape(-1)]
         il.image = self.image_pyramid(base)
         il.n_samples = int(nsamples)
+        n = self._next_light_index()
+        il.light_index = n
+        self.infinite_lights.append(il)
+        return n
+
+    def _next_light_index(self):
+        """The number of lights created so far: where a LightSource directive read now lands in scene.lights."""
         n = 0
         for tm in self.tri_mesh:
             for mid in np.asarray(tm).reshape(-1):
                 mm = self.meshes[int(mid)]
                 n += 1 if (mm.area_light >= 0 and mm.object == 0) else 0
         n += sum(1 for sp in self.spheres if sp.area_light >= 0 and sp.object == 0)
-        n += len(self.infinite_lights)
-        il.light_index = n
-        self.infinite_lights.append(il)
-        return n
+        return n + len(self.infinite_lights) + len(self.delta_lights)
+
+    def _delta_light(self, kind, spectrum, scale, l2w, direction=(0.0, 0.0, 0.0), total_width=0.0, falloff_start=0.0):
+        dl = capi.pt_delta_light()
+        dl.kind = kind
+        dl.light_to_world[:] = [float(v) for v in np.asarray(l2w[0], np.float32).reshape(-1)]
+        dl.world_to_light[:] = [float(v) for v in np.asarray(l2w[1], np.float32).reshape(-1)]
+        dl.spectrum[:] = [float(f32(a) * f32(b)) for a, b in zip(spectrum, scale)]
+        dl.cone_total_width = float(f32(total_width))
+        dl.cone_falloff_start = float(f32(falloff_start))
+        dl.direction[:] = [float(f32(v)) for v in direction]
+        dl.light_index = self._next_light_index()
+        self.delta_lights.append(dl)
+        return dl.light_index
+
+    @staticmethod
+    def _ctm(ctm):
+        return (np.eye(4, dtype=np.float32).reshape(-1),) * 2 if ctm is None else (np.asarray(ctm[0], np.float32).reshape(-1), np.asarray(ctm[1], np.float32).reshape(-1))
+
+    def light_spot(self, I=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), coneangle=30.0, conedelta=5.0, frm=(0.0, 0.0, 0.0), to=(0.0, 0.0, 1.0), ctm=None):
+        """LightSource "spot" (create_spot_light, lights/spot.rs:136-162) read at this point of the scene.  ctm: the (m, m_inv) pair of the
+        current transformation matrix (None: identity); light_to_world = ctm * Translate(from) * Inverse(dir_to_z).  Returns the light's index."""
+        frm, to = _v(*frm), _v(*to)
+        d, du, dv = coordinate_system(_normalize(to - frm))
+        dir_to_z = np.eye(4, dtype=np.float32)
+        dir_to_z[0, :3], dir_to_z[1, :3], dir_to_z[2, :3] = du, dv, d
+        inv = matrix_inverse(dir_to_z)
+        assert inv is not None, "spot light: from and to give no direction"
+        l2w = transform_mul(transform_mul(self._ctm(ctm), transform_translate(frm[0], frm[1], frm[2])), (inv, dir_to_z.reshape(-1)))
+        return self._delta_light(capi.PT_DELTA_SPOT, I, scale, l2w, total_width=f32(coneangle), falloff_start=f32(coneangle) - f32(conedelta))
+
+    def light_distant(self, L=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), frm=(0.0, 0.0, 0.0), to=(0.0, 0.0, 1.0), ctm=None):
+        """LightSource "distant" (create_distant_light, lights/distant.rs:136-146): light_to_world is the CTM, the direction from - to."""
+        return self._delta_light(capi.PT_DELTA_DISTANT, L, scale, self._ctm(ctm), direction=_v(*frm) - _v(*to))
+
+    def light_point(self, I=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), frm=(0.0, 0.0, 0.0), ctm=None):
+        """LightSource "point" (create_point_light, lights/point.rs:113-124): light_to_world = Translate(from) * ctm -- the reference's order,
+        the opposite of pbrt-v3's."""
+        frm = _v(*frm)
+        return self._delta_light(capi.PT_DELTA_POINT, I, scale, transform_mul(transform_translate(frm[0], frm[1], frm[2]), self._ctm(ctm)))
 
     def no_area_light(self):
         self.cur_area_light = -1
@@ -801,6 +894,7 @@ class SceneBuilder:
             sd.buffers["spheres"] = sph
             d.n_spheres, d.spheres = len(self.spheres), sph
         sd.infinite_lights = list(self.infinite_lights)
+        sd.delta_lights = list(self.delta_lights)
         sd.alpha_masks = list(self.alpha_masks)
         sd.aov = tuple(self.aov)
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
@@ -952,6 +1046,11 @@ def rt1m(n_triangles=1000000, res=1024, spp=256, max_depth=8, s=0.005, seed_sequ
                         b.object_instance("fill", transform_mul(transform_translate(c[0], c[1], c[2]), transform_scale(1.0 / g, 1.0 / g, 1.0 / g)))
                         k += 1
         b.material_matte((0.5, 0.5, 0.5))
+    if light == "distant":      # secondary workload (tools/delta_light_bench.py): no emitter, a sun shining in through the open front
+        b.light_distant(L=(3.0, 2.5, 2.0), frm=(0.3, 0.6, -1.0), to=(0.0, 0.0, 0.0))
+        if finish is not None:
+            finish(b)
+        return b.build()
     b.area_light_source_diffuse(L=(17, 12, 4))
     if light == "sphere":       # secondary workload: an analytic sphere light (the sphere-capable kernel instantiations run)
         t = transform_translate(0.0, 0.85, 0.0)
