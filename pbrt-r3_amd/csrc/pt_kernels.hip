@@ -1222,19 +1222,30 @@ static_assert(PT_LEAF_LANES_MIN > 0, "the leaf round is triggered by the number 
 #define PT_SPH_LANES_MIN 8           // scenes with spheres: a sphere round once this many lanes are parked on a leaf that holds a sphere (2 / 4 / 6 / 8 / 10 / 16 / 24 / 32:
                                      // 46.9 / 45.2 / 44.6 / 44.4 / 44.5 / 44.9 / 48.6 / 54.2 ms per launch, RT1M lit by a sphere, 64 spp)
 #endif
+// inclusive maximum over the lanes at and below this one, as six v_max_u32_dpp: within each row of 16 lanes (row_shr:1/2/4/8; a lane with no source
+// takes 0, the identity), then lane 15 of rows 0 and 2 to rows 1 and 3 (row_bcast:15, row_mask 0xa), then lane 31 to rows 2 and 3 (row_bcast:31, row_mask 0xc)
+// All 64 lanes must be active: a lane whose source lane is disabled keeps `old`, here 0, and the maximum would skip that lane's word.
+PT_DEV uint32_t wave_max_scan(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false));
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false));
+    return x;
+}
 // DIST: every leaf holds at most 8 triangles and its reference carries the count, so a leaf phase can pool the
 // triangles of all parked lanes and hand one (ray, triangle) test to each lane of the wave.
 // FAR: k_trace_far, the pooled-leaf kernel that fetches nodes pairwise (node_step_coop).
 template <bool DIST, bool SPH, bool INST = false, bool FAR = false, bool ALPHA = false>
 PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     // LDS per block.  Pooled-leaf kernels (PT_TRACE_WIDE: one 1024-thread block per CU): PT_FS_SLOTS = 24 stack slots x 4 KB = 96 KB (deeper
-    // lanes spill to HBM), a leaf round's 64 test results and owner map per wave (17 KB) and the top of the tree (341 nodes x 112 bytes = 38 KB):
-    // 153.9 of the CU's 160 KB.
+    // lanes spill to HBM), a leaf round's 64 test results per wave (16 KB; the owner map borrows their first words) and the top of the tree
+    // (341 nodes x 112 bytes = 38 KB): 152.9 of the CU's 160 KB.
     constexpr uint32_t TB = DIST ? PT_TBLOCK : PT_BLOCK;          // threads per block (PT_TRACE_WIDE: the pooled-leaf kernels run 1024)
     __shared__ uint32_t s_stack[(DIST ? PT_FS_SLOTS : PT_LDS_STACK) * TB];
     __shared__ unsigned long long s_cnt[4];
     __shared__ float4 s_res[DIST ? TB : 1];          // per wave: 64 test results (ok, t_scaled, det, t)
-    __shared__ unsigned char s_map[DIST ? TB : 1];   // per wave: work item -> owner lane
 #if PT_TOP_NODES > 0
     __shared__ float4 s_top[DIST ? PT_TOP_NODES * 7 : 1];      // rows 0..6 (six plane rows, child references) of the first nodes of the tree
 #endif
@@ -1444,14 +1455,22 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 const unsigned long long m_served = __ballot(lf_served);
                 const int last = 63 - __clzll(m_served);                      // m_served != 0: the first parked lane always fits
                 lf_items = (uint32_t)__shfl((int)(lf_pre + tcnt_r), last, 64);
-                if (lf_served)
-                    for (uint32_t k = 0; k < tcnt_r; k++) s_map[wbase + lf_pre + k] = (unsigned char)lane;
+                // The owner map.  A served owner marks the slot of its FIRST item with a word that grows with the owner's position (served owners' lf_pre and lane
+                // numbers both rise in lane order), every other slot holds 0, and an inclusive maximum over the lanes below spreads the word to the leaf's other
+                // items: item i's owner is the last owner that starts at or below i (tests/test_leaf_item_map.py).  Three LDS instructions per round; every owner
+                // used to store its lane number once per triangle of its leaf, and item i took the owner's lf_pre by one more shuffle.
+                // The slots are the first 64 words of the wave's results, which nobody reads until leaf_finish has written them.
+                typedef uint32_t __attribute__((may_alias)) map_word;
+                map_word* const s_own = reinterpret_cast<map_word*>(&s_res[wbase]);
+                s_own[lane] = 0u;
+                if (lf_served) s_own[lf_pre] = ((lf_pre << 6) | lane) + 1u;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 lf_valid = lane < lf_items;
-                const int o = lf_valid ? (int)s_map[wbase + lane] : 0;
-                const uint32_t k = lane - (uint32_t)__shfl((int)lf_pre, o, 64);
+                const uint32_t own_w = wave_max_scan(s_own[lane]) - 1u;        // (slot 0 is always a first item: no lane sees 0.  A lane past lf_items decodes the last owner and tests nothing.)
+                const int o = (int)(own_w & 63u);
+                const uint32_t k = lane - (own_w >> 6);
                 const uint32_t first = (uint32_t)__shfl((int)(r.top & PT_LEAF_FIRST_MASK), o, 64);
                 lf_rp.o = mk3(__shfl(r.rp.o.x, o, 64), __shfl(r.rp.o.y, o, 64), __shfl(r.rp.o.z, o, 64));
                 lf_rp.d = mk3(0.0f, 0.0f, 0.0f);        // only the one-sided test (and a sphere) reads the direction
@@ -1475,6 +1494,12 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 if constexpr (SPH && !SR) { m_sitems = __ballot(sphere_rec); }
                 bool cand = false;          // HACC: this item passes everything, the t_max comparison against the round's t_max included
                 if (lf_valid) {
+                    // The record as the THREE 16-byte loads load_tri asked for.  tri_core's packed subtractions want (p0.x, p0.y) and (p0.y, p0.z) as register
+                    // pairs, and the compiler fetched each pair by a load of its own: four lane requests per record instead of three (at 0, 4, 16 and 32 bytes),
+                    // in a kernel that runs at 0.9 of the vector L1's request rate.  Through the empty asm the components are opaque and the pairs are built
+                    // from registers.  (All nine: with p0 alone the other two vertices were cut up instead.  Here and not at the load: the asm waits for the
+                    // values, and this is where they are needed first.)
+                    asm("" : "+v"(lf_tv.p0.x), "+v"(lf_tv.p0.y), "+v"(lf_tv.p0.z), "+v"(lf_tv.p1.x), "+v"(lf_tv.p1.y), "+v"(lf_tv.p1.z), "+v"(lf_tv.p2.x), "+v"(lf_tv.p2.y), "+v"(lf_tv.p2.z));
                     // The triangle test runs for EVERY item, a sphere's record included (its fields are not vertices: the result is thrown
                     // away).  With the test behind `if (!sphere)` the compiler moved the record's loads into the two branches, behind the
                     // load of the flags they depend on: a second memory round trip in every leaf round of the sphere-capable kernel
