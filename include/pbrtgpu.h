@@ -128,10 +128,19 @@ typedef enum {
     PT_MATERIAL_METAL = 5,     /* materials/metal.rs:51-85      eta (spectrum -> RGB), k, roughness | uroughness/vroughness */
     PT_MATERIAL_UBER = 6,      /* materials/uber.rs:63-127      Kd, Ks, Kr, Kt, opacity, eta, roughness | u/v roughness */
     PT_MATERIAL_SUBSTRATE = 7, /* materials/substrate.rs:34-68  Kd, Ks, uroughness, vroughness */
-    PT_MATERIAL_TRANSLUCENT = 8 /* materials/translucent.rs:38-107  Kd, Ks, reflect (in kr / tex_kr), transmit (in kt / tex_kt), roughness,
+    PT_MATERIAL_TRANSLUCENT = 8,/* materials/translucent.rs:38-107  Kd, Ks, reflect (in kr / tex_kr), transmit (in kt / tex_kt), roughness,
                                  * remaproughness; eta is the constant 1.5 ("eta" / "index" are not read, translucent.rs:48) */
+    PT_MATERIAL_MIX = 9         /* materials/mix.rs:53-96: every BxDF of "namedmaterial1" scaled by s1 = clamp_zero(amount), then every BxDF of
+                                 * "namedmaterial2" scaled by s2 = clamp_zero(1 - s1) (core/reflection/scaled.rs).  "amount" rides in kd / tex_kd
+                                 * (default 0.5); the children ride as material index + 1 in tex_kr (namedmaterial1) and tex_kt (namedmaterial2),
+                                 * which a mix does not otherwise read.  A child's index must be smaller than the mix's own (definition order: no
+                                 * cycles, and a child may itself be a mix); anything else is PT_ERR_INVALID_ARGUMENT.  Every other field is
+                                 * ignored: a mix has no bump map of its own, its shading frame and BSDF::eta are child 1's.  At most
+                                 * PT_MIX_MAX_LEAVES leaves and PT_MIX_MAX_LOBES BxDFs per tree (PT_ERR_UNSUPPORTED beyond). */
 } pt_material_type;
 
+#define PT_MIX_MAX_LEAVES 4          /* leaf materials under one mix tree */
+#define PT_MIX_MAX_LOBES 16          /* BxDFs of one mix tree's BSDF (the reference's list has no limit) */
 #define PT_ROUGHNESS_UNSET (-1.0f)   /* "uroughness"/"vroughness" not given: Metal and Uber fall back to "roughness" */
 
 /* Field defaults are the reference's create_*_material defaults; a field a material type does not

@@ -55,6 +55,16 @@ typedef struct {
                                       * becomes the default and this field goes back to reserved. */
 } pth_options;
 pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth_scene** out, char* err, size_t err_cap);
+/* The same two parses with a feature mask beside the options (opts may be NULL).  pth_options is passed by pointer and carries no size
+ * field, so it cannot grow: directives that are taken only when the caller asks ride here.  PTH_FEATURE_MIX_MATERIAL: Material "mix" and the
+ * MakeNamedMaterial type "mix" become PT_MATERIAL_MIX records (children before the mix in the material table); without the bit, and through
+ * every other entry point, they are refused as before (PT_ERR_UNSUPPORTED, the same message).  The same stop-gap as
+ * pth_options.delta_lights, for the same reason (a test pins the refusal of the plain entry points), and it goes away with it.
+ * PTH_FEATURE_DELTA_LIGHTS: what pth_options.delta_lights != 0 does; the old field keeps working.  pbrt_gpu sets both. */
+#define PTH_FEATURE_MIX_MATERIAL 1u
+#define PTH_FEATURE_DELTA_LIGHTS 2u
+pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
+pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
 pt_status pth_parse_string(const char* text, const char* work_dir, pth_scene** out, char* err, size_t err_cap);
 /* The same with options (NULL: pth_parse_string). */

@@ -14,6 +14,9 @@ DATA_DIR = os.path.join(HERE, "data")
 PT_MATERIAL_NONE, PT_MATERIAL_MATTE, PT_MATERIAL_PLASTIC, PT_MATERIAL_MIRROR = 0, 1, 2, 3
 PT_MATERIAL_GLASS, PT_MATERIAL_METAL, PT_MATERIAL_UBER, PT_MATERIAL_SUBSTRATE = 4, 5, 6, 7
 PT_MATERIAL_TRANSLUCENT = 8
+PT_MATERIAL_MIX = 9
+PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
+PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS = 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
 PT_MESH_HAS_N, PT_MESH_HAS_S, PT_MESH_HAS_UV = 8, 16, 32
@@ -245,7 +248,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_parse_string_opts", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_parse_file_features", "pth_parse_string_features",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
@@ -257,8 +260,9 @@ class ParsedScene:
     """A scene parsed from .pbrt text by the C++ front end (include/pbrtgpu_host.h).  Quacks like
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
-    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False):
-        """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before."""
+    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False):
+        """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
+        mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -276,7 +280,15 @@ class ParsedScene:
         self.h = C.c_void_p()
         err = C.create_string_buffer(2048)
         opts = pth_options(0, 0, 0, 1)
-        if filename is not None and delta_lights:
+        feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        features = PTH_FEATURE_MIX_MATERIAL | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0)
+        if mix_materials and filename is not None:
+            L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
+            st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
+        elif mix_materials:
+            L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
+            st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
+        elif filename is not None and delta_lights:
             L.pth_parse_file_opts.argtypes = [C.c_char_p, C.POINTER(pth_options), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
             st = L.pth_parse_file_opts(filename.encode(), C.byref(opts), C.byref(self.h), err, 2048)
         elif filename is not None:

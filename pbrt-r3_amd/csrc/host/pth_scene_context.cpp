@@ -106,7 +106,13 @@ inline bool swaps_handedness(const M44& m) {
 struct TransformSet { Xf t[2]; };
 const unsigned kAllBits = 3, kStartBit = 1, kEndBit = 2;
 
-struct MaterialInstance { std::string name; ParamSet params; bool none = false; };
+struct MaterialInstance {
+    std::string name; ParamSet params; bool none = false;
+    // Material "mix" (taken with PTH_FEATURE_MIX_MATERIAL): the children as they were when the instance was created -- indices into the
+    // material table, -1 = a "none" material.  make_material (scene_context.rs:446-452) looks "namedmaterial1" / "namedmaterial2" up
+    // among the named materials current at the directive and keeps the materials it found.
+    int mix_child[2] = {-1, -1};
+};
 struct GraphicsState {
     MaterialInstance material;                                   // default: matte, no params (graphics_state.rs:61-91)
     std::map<std::string, MaterialInstance> named_materials;
@@ -141,6 +147,7 @@ public:
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
     std::vector<pt_delta_light> delta_lights;
+    bool accept_mix = false;                     // PTH_FEATURE_MIX_MATERIAL: Material "mix" is taken (off: refused, as before)
     bool accept_delta_lights = false;            // pth_options.delta_lights: LightSource "spot" / "distant" are taken (off: refused, as before)
     int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
     float aov_scale = 1.0f;
@@ -401,6 +408,7 @@ public:
         MaterialInstance mi;
         mi.name = name; mi.params = p;
         mi.none = name.empty() || name == "none";
+        if (name == "mix" && accept_mix) resolve_mix_children(mi, mi.params, ParamSet());
         gstates.back().material = mi;
     }
     void pbrt_make_named_material(const std::string& name, const ParamSet& p) override {
@@ -409,6 +417,7 @@ public:
         if (mi.name.empty()) warn("No parameter string \"type\" found in MakeNamedMaterial");
         mi.params = p;
         mi.none = mi.name == "none";
+        if (mi.name == "mix" && accept_mix) resolve_mix_children(mi, mi.params, ParamSet());
         gstates.back().named_materials[name] = mi;
     }
     void pbrt_named_material(const std::string& name) override {
@@ -622,8 +631,48 @@ public:
         if (geom.floats.count(n)) { *out = geom.find_one_float(n, *out); return true; }
         return false;
     }
+    // shape_may_set_material_parameters (scene_context.rs:224-267), as its text has it: ANY string or texture parameter other than "alpha" /
+    // "shadowalpha" (so a plymesh's "filename" counts: the first loop has no length test), a single float other than "radius", a single
+    // bool / int / spectrum, a single point.
+    static bool shape_may_set_material_parameters(const ParamSet& g) {
+        for (auto& kv : g.strings) if (kv.first != "alpha" && kv.first != "shadowalpha") return true;
+        for (auto& kv : g.textures) if (kv.first != "alpha" && kv.first != "shadowalpha") return true;
+        for (auto& kv : g.floats) if (kv.second.size() == 1 && kv.first != "radius") return true;
+        for (auto& kv : g.bools) if (kv.second.size() == 1) return true;
+        for (auto& kv : g.ints) if (kv.second.size() == 1) return true;
+        for (auto& kv : g.rgbs) if (kv.second.size() == 3) return true;
+        if (!g.spectrum_files.empty() || !g.blackbodies.empty()) return true;
+        for (auto& kv : g.points) if (kv.second.size() == 3) return true;
+        return false;
+    }
+    // get_named_material_matte (scene_context.rs:423-430): the named material as it was created at its own directive (no shape parameters), or,
+    // for a name that is not found, a matte built from the mix's own parameters -- no error.
+    int mix_child_material(const std::string& child, const ParamSet& mix_params, const ParamSet& geom) {
+        auto it = gstates.back().named_materials.find(child);
+        if (it != gstates.back().named_materials.end()) {
+            if (it->second.none) return -1;
+            const MaterialInstance ci = it->second;          // (a copy: make_material may grow the tables)
+            return make_material(ci, ParamSet(), false);
+        }
+        MaterialInstance matte;
+        matte.name = "matte"; matte.params = mix_params;
+        return make_material(matte, geom, false);
+    }
+    void resolve_mix_children(MaterialInstance& mi, const ParamSet& mix_params, const ParamSet& geom) {
+        const char* keys[2] = {"namedmaterial1", "namedmaterial2"};
+        for (int k = 0; k < 2; k++) {
+            const std::string child = geom.find_one_string(keys[k], mix_params.find_one_string(keys[k], ""));
+            mi.mix_child[k] = mix_child_material(child, mix_params, geom);
+            if (!error.empty()) return;
+            if (mi.mix_child[k] < 0) { fail("Material \"mix\": \"" + std::string(keys[k]) + "\" \"" + child + "\" is a \"none\" material: it leaves no BSDF to scale (the reference asserts, mix.rs:78-79)"); return; }
+        }
+    }
     int material_for_shape(const ParamSet& geom) {
-        const MaterialInstance& mi = gstates.back().material;
+        const MaterialInstance mi = gstates.back().material;
+        return make_material(mi, geom, true);
+    }
+    // at_shape: the material of a shape (get_material_for_shape, scene_context.rs:269-296); otherwise a mix's child, as its directive created it
+    int make_material(const MaterialInstance& mi, const ParamSet& geom, bool at_shape) {
         if (mi.none) return -1;
         const ParamSet& mp = mi.params;
         pt_material m;
@@ -689,6 +738,24 @@ public:
             lookup_rgb(geom, mp, "Kd", m.kd, &m.tex_kd); lookup_rgb(geom, mp, "Ks", m.ks, &m.tex_ks);
             lookup_rgb(geom, mp, "reflect", m.kr, &m.tex_kr); lookup_rgb(geom, mp, "transmit", m.kt, &m.tex_kt);
             lookup_float(geom, mp, "roughness", &m.roughness, &m.tex_roughness);
+        } else if (mi.name == "mix" && accept_mix) {                // mix.rs:98-104, scene_context.rs:446-452
+            // The children: the ones the directive found; a shape that may set material parameters creates the material again, with its
+            // parameters in front, among the named materials current at the shape (scene_context.rs:269-287).
+            MaterialInstance now = mi;
+            if (at_shape && shape_may_set_material_parameters(geom)) { resolve_mix_children(now, mp, geom); if (!error.empty()) return -1; }
+            if (now.mix_child[0] < 0 || now.mix_child[1] < 0) { fail("Material \"mix\": a child is a \"none\" material"); return -1; }
+            m.type = PT_MATERIAL_MIX;
+            set3(m.kd, 0.5f);
+            if (at_shape) lookup_rgb(geom, mp, "amount", m.kd, &m.tex_kd);      // get_spectrum_texture("amount", 0.5): a "float amount" is not found
+            else lookup_rgb(ParamSet(), mp, "amount", m.kd, &m.tex_kd);
+            m.tex_kr = (uint32_t)now.mix_child[0] + 1u;
+            m.tex_kt = (uint32_t)now.mix_child[1] + 1u;
+            m.remap_roughness = 1;                                  // (not read; as SceneBuilder.material_mix leaves it)
+            if (!error.empty()) return -1;
+            for (size_t i = 0; i < materials.size(); i++)
+                if (std::memcmp(&materials[i], &m, sizeof(m)) == 0) return (int)i;
+            materials.push_back(m);
+            return (int)materials.size() - 1;
         } else {
             fail("Material \"" + mi.name + "\": outside the accelerated path (matte, plastic, mirror, glass, metal, uber, substrate, translucent are supported)");
             return -1;
@@ -1161,6 +1228,26 @@ static pt_status finish_with_options(pth_scene* s, bool ok, const std::string& p
 
 extern "C" {
 
+pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap) {
+    if (!filename || !out) return PT_ERR_INVALID_ARGUMENT;
+    pth_scene* s = new pth_scene;
+    apply_options(s, opts);
+    s->ctx.accept_mix = (features & PTH_FEATURE_MIX_MATERIAL) != 0;
+    if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
+    std::string perr;
+    bool ok = pth::pbrt_parse_file(filename, s->ctx, &perr);
+    return finish_with_options(s, ok, perr, opts, out, err, err_cap);
+}
+pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap) {
+    if (!text || !out) return PT_ERR_INVALID_ARGUMENT;
+    pth_scene* s = new pth_scene;
+    apply_options(s, opts);
+    s->ctx.accept_mix = (features & PTH_FEATURE_MIX_MATERIAL) != 0;
+    if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
+    std::string perr;
+    bool ok = pth::pbrt_parse_string(text, work_dir ? work_dir : ".", s->ctx, &perr);
+    return finish_with_options(s, ok, perr, opts, out, err, err_cap);
+}
 pt_status pth_parse_file(const char* filename, pth_scene** out, char* err, size_t err_cap) {
     return pth_parse_file_opts(filename, nullptr, out, err, err_cap);
 }

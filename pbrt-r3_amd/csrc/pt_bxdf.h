@@ -484,3 +484,89 @@ PT_DEV bool gbsdf_sample_f(const GBsdf& b, V3 wo_w, V2 u, uint32_t flags, V3* f_
     *f_out = f; *wi_out = wi_world; *pdf_out = pdf; *type_out = sampled_type;
     return true;
 }
+
+// ---- BSDF over scaled lobes: Material "mix" (materials/mix.rs:53-96).  Every BxDF of the tree's leaves sits in one list, each wrapped in a
+// ScaledBxDF (core/reflection/scaled.rs) per mix node above its leaf: f and the spectrum of sample_f are scale * inner, one f32 multiply per
+// channel and node, innermost first; pdf, type and the sampled wi are the inner lobe's.  A lobe scaled by 0 is in the list like any other: it
+// counts in num_components, in the component choice and in the averaged pdf.  scales == nullptr: an unscaled list, the arithmetic of gbsdf_*.
+struct MBsdf : GBsdf {
+    const PtMixScales* scales;
+};
+PT_DEV V3 mlobe_scale(const MBsdf& b, uint32_t i, V3 f) {
+    if (b.scales) {
+        const uint32_t leaf = b.scales->lobe_leaf[i];          // (ranges: the upload's caps, pt_context.cpp)
+        const uint32_t nc = b.scales->n_chain[leaf];
+        for (uint32_t k = 0; k < nc; k++) {
+            const float* s = b.scales->s[leaf][k];
+            f = mk3(s[0] * f.x, s[1] * f.y, s[2] * f.z);
+        }
+    }
+    return f;
+}
+PT_DEV uint32_t mbsdf_num_components(const MBsdf& b, uint32_t flags) {
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < b.n_lobes; i++) n += lobe_matches(b.lobes[i], flags) ? 1u : 0u;
+    return n;
+}
+PT_DEV V3 mbsdf_f_local(const MBsdf& b, V3 wo, V3 wi, bool reflect, uint32_t flags) {
+    V3 r = mk3(0.0f, 0.0f, 0.0f);
+    for (uint32_t i = 0; i < b.n_lobes; i++) {
+        const PtLobe& l = b.lobes[i];
+        if (lobe_matches(l, flags) && ((reflect && (l.type & PT_BSDF_REFLECTION)) || (!reflect && (l.type & PT_BSDF_TRANSMISSION))))
+            r = r + mlobe_scale(b, i, globe_f(l, wo, wi));
+    }
+    return r;
+}
+PT_DEV V3 mbsdf_f(const MBsdf& b, V3 wo_w, V3 wi_w, uint32_t flags) {
+    V3 wi = gw2l(b, wi_w), wo = gw2l(b, wo_w);
+    if (wo.z == 0.0f || !gfinite3(wo)) return mk3(0.0f, 0.0f, 0.0f);
+    bool reflect = (dot(wi_w, b.ng) * dot(wo_w, b.ng)) > 0.0f;
+    return mbsdf_f_local(b, wo, wi, reflect, flags);
+}
+PT_DEV float mbsdf_pdf(const MBsdf& b, V3 wo_w, V3 wi_w, uint32_t flags) { return gbsdf_pdf(b, wo_w, wi_w, flags); }      // ScaledBxDF::pdf is the inner lobe's
+PT_DEV bool mbsdf_sample_f(const MBsdf& b, V3 wo_w, V2 u, uint32_t flags, V3* f_out, V3* wi_out, float* pdf_out, uint32_t* type_out) {
+    int matching = (int)mbsdf_num_components(b, flags);
+    if (matching == 0) return false;
+    int comp = (int)floorf(u.x * (float)matching);
+    if (comp > matching - 1) comp = matching - 1;
+    uint32_t index = 0;
+    int count = comp;
+    for (uint32_t i = 0; i < b.n_lobes; i++) {
+        if (lobe_matches(b.lobes[i], flags)) {
+            if (count == 0) { index = i; break; }
+            count--;
+        }
+    }
+    const PtLobe& lb = b.lobes[index];
+    V2 remapped = mk2(fminf((u.x * (float)matching) - (float)comp, PT_ONE_MINUS_EPS), u.y);
+    V3 wo = gw2l(b, wo_w);
+    if (wo.z == 0.0f || !gfinite3(wo)) return false;
+    V3 f, wi;
+    float pdf;
+    uint32_t t;
+    if (!globe_sample_f(lb, wo, remapped, &f, &wi, &pdf, &t)) return false;
+    f = mlobe_scale(b, index, f);
+    if (pdf <= 0.0f) return false;
+    uint32_t sampled_type = t != 0 ? t : lb.type;
+    V3 wi_world = gl2w(b, wi);
+    if ((lb.type & PT_BSDF_SPECULAR) == 0 && matching > 1)
+        for (uint32_t i = 0; i < b.n_lobes; i++)
+            if (i != index && lobe_matches(b.lobes[i], flags)) pdf += globe_pdf(b.lobes[i], wo, wi);
+    if (matching > 1) pdf /= (float)matching;
+    if ((lb.type & PT_BSDF_SPECULAR) == 0) {
+        bool reflect = (dot(wi_world, b.ng) * dot(wo_w, b.ng)) > 0.0f;
+        f = mbsdf_f_local(b, wo, wi, reflect, flags);
+    }
+    *f_out = f; *wi_out = wi_world; *pdf_out = pdf; *type_out = sampled_type;
+    return true;
+}
+// one spelling for code instantiated over either list (the recursive integrators' node)
+PT_DEV V3 xbsdf_f(const GBsdf& b, V3 wo_w, V3 wi_w, uint32_t flags) { return gbsdf_f(b, wo_w, wi_w, flags); }
+PT_DEV V3 xbsdf_f(const MBsdf& b, V3 wo_w, V3 wi_w, uint32_t flags) { return mbsdf_f(b, wo_w, wi_w, flags); }
+PT_DEV float xbsdf_pdf(const GBsdf& b, V3 wo_w, V3 wi_w, uint32_t flags) { return gbsdf_pdf(b, wo_w, wi_w, flags); }
+PT_DEV bool xbsdf_sample_f(const GBsdf& b, V3 wo_w, V2 u, uint32_t flags, V3* f_out, V3* wi_out, float* pdf_out, uint32_t* type_out) {
+    return gbsdf_sample_f(b, wo_w, u, flags, f_out, wi_out, pdf_out, type_out);
+}
+PT_DEV bool xbsdf_sample_f(const MBsdf& b, V3 wo_w, V2 u, uint32_t flags, V3* f_out, V3* wi_out, float* pdf_out, uint32_t* type_out) {
+    return mbsdf_sample_f(b, wo_w, u, flags, f_out, wi_out, pdf_out, type_out);
+}

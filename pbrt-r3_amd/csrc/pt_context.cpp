@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <array>
 #include <memory>
@@ -79,6 +80,7 @@ struct pt_context {
     std::vector<uint64_t> sobol_vdc, sobol_inv;
     uint32_t sobol_n_vdc = 0, sobol_n_inv = 0, sobol_msize = 52;
     uint32_t n_materials = 0;
+    std::vector<uint8_t> mix_per_hit;               // per material: 1 for a "mix" whose lobes are built at every hit (the BSDF hooks refuse it)
     uint32_t max_stack = 1;
     uint32_t film_w = 0, film_h = 0;
     int bvh_build_where = PT_BVH_BUILD_AUTO;
@@ -619,11 +621,17 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         if (d->meshes[m].area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "area light index out of range");
 
         int32_t mi = d->meshes[m].material;
-        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_TRANSLUCENT))
+        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_MIX))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
     }
     for (uint32_t i = 0; i < d->n_materials; i++) {
         const pt_material& m = d->materials[i];
+        if (m.type == PT_MATERIAL_MIX) {       // "amount" in kd / tex_kd, the children as material index + 1 in tex_kr / tex_kt; nothing else is read
+            if (m.tex_kd > d->n_textures || (m.tex_kd && !d->textures)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material texture index out of range");
+            if (m.tex_kr == 0 || m.tex_kr > i || m.tex_kt == 0 || m.tex_kt > i)
+                return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material " + std::to_string(i) + " (mix): a child's material index must be smaller than the mix's own (definition order)");
+            continue;
+        }
         const uint32_t refs[13] = {m.tex_kd, m.tex_ks, m.tex_kr, m.tex_kt, m.tex_opacity, m.tex_sigma, m.tex_metal_eta, m.tex_metal_k, m.tex_bump,
                                    m.tex_roughness, m.tex_uroughness, m.tex_vroughness, m.tex_eta};
         for (uint32_t r : refs)
@@ -652,7 +660,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         const pt_sphere& sp = d->spheres[i];
         if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere material index out of range");
         if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere area light index out of range");
-        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_TRANSLUCENT))
+        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_MIX))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
         if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere before_triangle exceeds n_triangles");
         if (!(sp.radius > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere radius must be positive");
@@ -1214,8 +1222,100 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         }
         return off;
     };
+    std::vector<PtMix> mixes;
+    ctx->mix_per_hit.assign(mats.size(), 0);
     for (uint32_t i = 0; i < d->n_materials; i++) {
         build_lobes(d->materials[i], mats[i]);
+        if (d->materials[i].type == PT_MATERIAL_MIX) {
+            // Flatten the tree under the mix (children precede it, so their PtMaterial records exist): leaves in lobe order, per leaf the
+            // mix nodes above it innermost first.  Constant trees get their lobe list and scales here, once; a tree with a textured
+            // "amount" or a textured leaf gets them at every hit (mix_hit_lobes, pt_kernels.hip).
+            PtMix mx;
+            std::memset(&mx, 0, sizeof(mx));
+            uint32_t n_leaves = 0, n_lobes = 0;
+            std::string refusal;
+            std::vector<std::pair<uint32_t, uint32_t>> above;          // (node, side) from the root down
+            std::function<void(uint32_t)> walk = [&](uint32_t mi) {
+                const pt_material& in = d->materials[mi];
+                if (n_leaves > 4u * PT_MIX_MAX_LEAVES) { n_leaves++; return; }      // far past the cap: refused below; the count in the message stops growing here
+                if (in.type == PT_MATERIAL_MIX) {
+                    if (above.size() >= 4u * PT_MIX_MAX_NODES) { mx.n_nodes++; n_leaves += 2; return; }      // that deep a tree has more leaves than the cap: no need to go down (bounds the recursion)
+                    const uint32_t k = mx.n_nodes++;
+                    if (k < PT_MIX_MAX_NODES) {
+                        std::memcpy(mx.amount[k], in.kd, 12);
+                        if (in.tex_kd) {
+                            mx.amount_prog[k] = add_program(in.tex_kd - 1);
+                            if (!mx.amount_prog[k] && refusal.empty()) refusal = "a material parameter's texture graph needs more than 12 nodes";
+                            mx.per_hit = 1;
+                        }
+                    }
+                    above.push_back({k, 0u});
+                    walk(in.tex_kr - 1);
+                    above.back().second = 1u;
+                    walk(in.tex_kt - 1);
+                    above.pop_back();
+                    return;
+                }
+                const uint32_t j = n_leaves++;
+                if (in.type < PT_MATERIAL_NONE || in.type > PT_MATERIAL_TRANSLUCENT) {
+                    if (refusal.empty()) refusal = "child material " + std::to_string(mi) + " has a material type that is not on the accelerated path";
+                    return;
+                }
+                n_lobes += mats[mi].textured ? pt_lobes_most(in.type) : mats[mi].n_lobes;          // a texture-driven leaf: the most its type can add
+                if (in.type == PT_MATERIAL_NONE && refusal.empty())
+                    refusal = "child material " + std::to_string(mi) + " is \"none\": it leaves no BSDF to scale (the reference asserts, mix.rs:78-79)";
+                else if (!mats[mi].textured && !mats[mi].has_bsdf && refusal.empty())
+                    refusal = "child material " + std::to_string(mi) + " never has a BSDF (black Kr and Kt / reflect and transmit): nothing to scale (the reference asserts, mix.rs:78-79)";
+                if (j >= PT_MIX_MAX_LEAVES) return;
+                if (mats[mi].textured) mx.per_hit = 1;
+                mx.leaf_material[j] = (int32_t)mi;
+                mx.scales.n_chain[j] = (uint32_t)above.size();
+                for (size_t c = 0; c < above.size() && c < PT_MIX_MAX_NODES; c++) {
+                    const auto& a = above[above.size() - 1 - c];
+                    mx.chain[j][c] = a.first | (a.second << 8);
+                }
+            };
+            walk(i);
+            if (!refusal.empty()) return ctx->fail(PT_ERR_UNSUPPORTED, "material " + std::to_string(i) + " (mix): " + refusal);
+            if (n_leaves > PT_MIX_MAX_LEAVES || n_lobes > PT_MIX_MAX_LOBES)
+                return ctx->fail(PT_ERR_UNSUPPORTED, "material " + std::to_string(i) + " (mix): its tree has " + std::to_string(n_leaves) + " leaves and " + std::to_string(n_lobes) +
+                                                     " lobes; the accelerated path takes at most " + std::to_string(PT_MIX_MAX_LEAVES) + " leaves and " +
+                                                     std::to_string(PT_MIX_MAX_LOBES) + " lobes per mix tree");
+            mx.n_leaves = n_leaves;
+            PtMaterial& mm = mats[i];
+            mm.n_lobes = 0; mm.has_bsdf = 1;                            // a mix always allocates its BSDF (mix.rs:81-88)
+            mm.bsdf_eta = mats[mx.leaf_material[0]].bsdf_eta;           // child 1's, recursively (mix.rs:83)
+            if (!mx.per_hit) {
+                float ns[PT_MIX_MAX_NODES][2][3];
+                for (uint32_t k = 0; k < mx.n_nodes; k++)
+                    for (int c = 0; c < 3; c++) {
+                        ns[k][0][c] = clamp_zero(mx.amount[k][c]);               // s1 = amount.clamp_zero()
+                        ns[k][1][c] = clamp_zero(1.0f - ns[k][0][c]);            // s2 = (1 - s1).clamp_zero()
+                    }
+                for (uint32_t j = 0; j < mx.n_leaves; j++) {
+                    const PtMaterial& lm = mats[mx.leaf_material[j]];
+                    for (uint32_t l = 0; l < lm.n_lobes; l++) { mx.scales.lobe_leaf[mx.n_lobes] = j; mx.lobes[mx.n_lobes++] = lm.lobes[l]; }
+                    for (uint32_t c = 0; c < mx.scales.n_chain[j]; c++)
+                        std::memcpy(mx.scales.s[j][c], ns[mx.chain[j][c] & 0xffu][mx.chain[j][c] >> 8], 12);
+                }
+                mm.nonspecular = 0; mm.spec_mask = 0;
+                for (uint32_t l = 0; l < mx.n_lobes; l++) {
+                    if (!(mx.lobes[l].type & kSpecular)) mm.nonspecular++;
+                    if ((mx.lobes[l].type & (kRefl | kSpecular)) == mx.lobes[l].type) mm.spec_mask |= 1u;
+                    if ((mx.lobes[l].type & (kTrans | kSpecular)) == mx.lobes[l].type) mm.spec_mask |= 2u;
+                }
+            } else {
+                mm.textured = 1;                   // the per-hit route of the *_mix kernels
+                any_textured = true;
+                ctx->mix_per_hit[i] = 1;
+                mparams[i].m = d->materials[i];
+            }
+            mixes.push_back(mx);
+            mm.mix1 = (uint32_t)mixes.size();
+            general_materials = true;
+            mm.sort_bin = PT_SORT_GENERAL0 + std::min(n_general_bins++, PT_SORT_TEX0 - PT_SORT_GENERAL0 - 1u);
+            continue;
+        }
         {
             const pt_material& in = d->materials[i];
             const uint32_t refs[13] = {in.tex_kd, in.tex_ks, in.tex_kr, in.tex_kt, in.tex_opacity, in.tex_sigma, in.tex_metal_eta, in.tex_metal_k, in.tex_bump,
@@ -1328,7 +1428,15 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     }          // host path
     if (up_n_nodes >= (1u << 25)) return ctx->fail(PT_ERR_UNSUPPORTED, "more than 2^25 BVH nodes (32-bit node offsets)");
     ctx->n_nodes_up = up_n_nodes; ctx->n_tris_up = up_n_tris;
-    if ((st = upload(ctx, ctx->d_materials, mats.data(), mats.size())) != PT_OK) return st;
+    if (mixes.empty()) { if ((st = upload(ctx, ctx->d_materials, mats.data(), mats.size())) != PT_OK) return st; }
+    else {          // the PtMix records ride behind the PtMaterial records (material_mix, pt_device.h)
+        std::vector<unsigned char> both(mats.size() * sizeof(PtMaterial) + mixes.size() * sizeof(PtMix));
+        for (PtMaterial& m : mats) m.mix_base = (uint32_t)mats.size();
+        std::memcpy(both.data(), mats.data(), mats.size() * sizeof(PtMaterial));
+        std::memcpy(both.data() + mats.size() * sizeof(PtMaterial), mixes.data(), mixes.size() * sizeof(PtMix));
+        if ((st = upload(ctx, ctx->d_materials, both.data(), both.size())) != PT_OK) return st;
+    }
+    const uint32_t n_mix = (uint32_t)mixes.size();
     {   // infinite and delta lights: their records at their places in the light list (scene_context.rs:1178-1188), in directive order
         const uint32_t n_inf = (uint32_t)ctx->inf_lights.size(), n_all = n_inf + (uint32_t)ctx->delta_lights.size();
         auto index_of = [&](uint32_t k) { return k < n_inf ? ctx->inf_lights[k].light_index : ctx->delta_lights[k - n_inf].light_index; };
@@ -1422,6 +1530,9 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     sc.n_spheres = d->n_spheres;
     if (d->n_spheres) sc.general_materials = 1;     // sphere scenes run the sphere-capable kernel instantiations (sorted shade queue)
     if (d->n_instances) { sc.general_materials = 1; sc.dist_leaves = 0; }      // k_trace_inst walks leaves per lane; one shade kernel handles everything
+    // The mix materials' count rides above bit 0 (scene_n_mix).  This is the LAST write to the field: the assignments above set bit 0 and would
+    // erase the count, and every reader takes the field as a truth value or through scene_n_mix, never by comparing it with 1.
+    sc.general_materials = (sc.general_materials & 1u) | (n_mix << 1);
     sc.root_ref = up_root_ref;
     sc.n_top = n_top;
     for (int a = 0; a < 3; a++) { const float ext = up_root_hi[a] - up_root_lo[a]; sc.cell_scale[a] = ext > 0.0f ? (float)(1u << PT_SORT_CELL_BITS) / ext : 0.0f; }
@@ -2526,6 +2637,8 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
     if (!ctx || !wo || !wi || !f_out || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (material >= ctx->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material index out of range");
+    if (material < ctx->mix_per_hit.size() && ctx->mix_per_hit[material])
+        return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this mix material's lobes are built at every hit (a textured amount or leaf); the hooks take constant trees");
     if (n == 0) return PT_OK;
     (void)hipSetDevice(ctx->device);
     DevBuf d_wo, d_wi, d_f, d_pdf;
@@ -2583,6 +2696,8 @@ pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const f
     if (!ctx || !wo || !u || !f_out || !wi_out || !pdf_out || !type_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (material >= ctx->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material index out of range");
+    if (material < ctx->mix_per_hit.size() && ctx->mix_per_hit[material])
+        return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this mix material's lobes are built at every hit (a textured amount or leaf); the hooks take constant trees");
     if (n == 0) return PT_OK;
     (void)hipSetDevice(ctx->device);
     DevBuf d_wo, d_u, d_f, d_wi, d_pdf, d_t;

@@ -125,8 +125,31 @@ struct PtMaterial {
     uint32_t textured;           // 1: parameters come from textures at each hit (PtMatParams), the lobes below are unused
     uint32_t spec_mask;          // bit 0: some lobe matches BSDF_REFLECTION | BSDF_SPECULAR, bit 1: ... BSDF_TRANSMISSION | BSDF_SPECULAR (what specular_reflect /
                                  // specular_transmit ask BSDF::sample_f for: with the bit clear the call returns None before it looks at anything)
-    uint32_t pad[2];
+    uint32_t mix1;               // PT_MATERIAL_MIX: index + 1 of the material's PtMix record (0: not a mix); read by the *_mix kernels only
+    uint32_t mix_base;           // ... and where the PtMix table starts: that many PtMaterial records into the materials buffer (material_mix below)
     PtLobe lobes[PT_MAX_LOBES];
+};
+// Material "mix" (materials/mix.rs:53-96): the tree under one mix material, flattened at upload.  Its BSDF is the leaves' BxDFs in order
+// (child 1's, then child 2's, recursively), each wrapped in one ScaledBxDF (core/reflection/scaled.rs) per mix node above its leaf: the
+// scale multiplies what the inner lobe returns, innermost node first, and never enters PtLobe::r.  PT_MAX_LOBES stays what it is for
+// every other kernel: these lists live here, beside the materials.
+#define PT_MIX_MAX_NODES (PT_MIX_MAX_LEAVES - 1)     // a binary tree of PT_MIX_MAX_LEAVES leaves has that many inner nodes, and no leaf more above it
+struct PtMixScales {
+    uint32_t lobe_leaf[PT_MIX_MAX_LOBES];                       // per lobe: the leaf it came from
+    uint32_t n_chain[PT_MIX_MAX_LEAVES];                        // per leaf: mix nodes above it
+    float s[PT_MIX_MAX_LEAVES][PT_MIX_MAX_NODES][3];            // per leaf: the scale (s1 or s2) of each of them, innermost first
+};
+struct PtMix {
+    uint32_t n_leaves, n_nodes;
+    uint32_t n_lobes;            // constant trees: entries of lobes[]
+    uint32_t per_hit;            // 1: some "amount" or some leaf is texture-driven -- lobes and scales are built at every hit (mix_hit_lobes)
+    int32_t leaf_material[PT_MIX_MAX_LEAVES];                   // in lobe order; [0] is the leftmost leaf: its bump map gives the frame, its BSDF the eta
+    uint32_t chain[PT_MIX_MAX_LEAVES][PT_MIX_MAX_NODES];        // per leaf, innermost first: node index | side << 8 (0: the node's s1, 1: its s2)
+    float amount[PT_MIX_MAX_NODES][3];                          // per node: "amount" where it is constant
+    uint32_t amount_prog[PT_MIX_MAX_NODES];                     // ... or the offset of its texture program in PtScene::tex_prog (0 = constant)
+    uint32_t pad;
+    PtMixScales scales;          // constant trees: complete.  Per-hit trees: n_chain only
+    PtLobe lobes[PT_MIX_MAX_LOBES];
 };
 // One MIP pyramid (core/texture/mipmap.rs) in HBM: all levels back to back, level l at texels + level_off[l] floats.
 #define PT_MAX_MIP_LEVELS 16
@@ -282,7 +305,9 @@ struct PtCounters {
 struct PtScene {
     uint32_t dist_leaves;        // 1: no leaf holds more than 8 triangles, k_trace spreads leaf tests over the wave
     uint32_t any_one_sided;      // 1: some triangle is one-sided ("twosided" false): leaf rounds also need the ray direction
-    uint32_t general_materials;  // 1 when any material is not Matte: k_shade_general runs instead of k_shade
+    uint32_t general_materials;  // bit 0: some material is not Matte, k_shade_general runs instead of k_shade (read as a truth value).  Bits 1..: the
+                                 // number of Material "mix" materials (scene_n_mix); > 0: the *_mix kernels run.  PtScene keeps its size and layout:
+                                 // it is a kernel argument that the shading kernels also hold in scratch, so a new field would move their figures
     uint32_t n_deltas;           // delta lights (PtLight records with PT_LIGHT_DELTA; side records: scene_deltas); > 0: the *_env kernels run.  (It sits in
                                  // what was the alignment hole before `nodes`: PtScene keeps its size and every other field its offset.)
     const PtNode* nodes;
@@ -320,6 +345,12 @@ struct PtScene {
 PT_HOSTDEV_ENVS inline const PtEnvLight* scene_envs(const PtScene& sc) { return reinterpret_cast<const PtEnvLight*>(sc.lights + sc.n_lights); }
 // ... and the delta lights' PtDeltaLight records follow those.
 PT_HOSTDEV_ENVS inline const PtDeltaLight* scene_deltas(const PtScene& sc) { return reinterpret_cast<const PtDeltaLight*>(scene_envs(sc) + sc.n_envs); }
+// The mix materials' count rides above bit 0 of general_materials; their PtMix records follow the PtMaterial records in the materials buffer.
+PT_HOSTDEV_ENVS inline uint32_t scene_n_mix(const PtScene& sc) { return sc.general_materials >> 1; }
+PT_HOSTDEV_ENVS inline const PtMix& material_mix(const PtScene& sc, const PtMaterial& m) {
+    return reinterpret_cast<const PtMix*>(sc.materials + m.mix_base)[m.mix1 - 1u];
+}
+static_assert(sizeof(PtMaterial) % 16 == 0 && sizeof(PtMix) % 4 == 0, "the PtMix table behind the materials");
 static_assert(sizeof(PtDeltaLight) == 80 && sizeof(PtEnvLight) % 8 == 0 && sizeof(PtLight) % 16 == 0, "side records of the light buffer");
 static_assert(__builtin_offsetof(PtScene, nodes) == 16, "n_deltas fills the hole in front of PtScene::nodes");
 

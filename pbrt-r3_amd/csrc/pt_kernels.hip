@@ -2629,6 +2629,79 @@ __device__ __noinline__ void textured_lobes(const PtScene& sc, int32_t material,
     textured_params(sc, material, th, mp, a3, n, uv, sh_n, sh_dpdu, sh_dpdv, sh_dndu, sh_dndv);
     build_lobes_call(mp.m, a3[0], a3[1], a3[2], *out);
 }
+// Material "mix" with a textured "amount" or a textured leaf: the tree's lobe list and scale chains at this hit (constant trees: built once at
+// upload, PtMix).  "amount" is evaluated on the interaction as it arrives (mix.rs:62-63); the leftmost leaf's bump map bends the caller's frame
+// (the mix's BSDF is allocated from the interaction as child 1 left it, mix.rs:83); every other leaf works on a copy, as the reference's
+// clone `si2` (mix.rs:65): its bump map never reaches the BSDF.  A leaf that has no BSDF at this hit adds no lobes.
+struct PtMixHit {
+    PtMixScales scales;
+    PtLobe lobes[PT_MIX_MAX_LOBES];
+};
+struct PtNoMix {};
+// leaf0_done: the caller has run the leftmost leaf through textured_lobes on its own interaction (mix_hit below) and *out holds that leaf's lobes;
+// n0 / dpdu0: the shading frame as the interaction arrived, which every later leaf's clone starts from.
+__device__ __noinline__ void mix_hit_lobes(const PtScene& sc, int32_t material, const TexHit& th_in, PtMaterial* out, uint32_t leaf0_done, PtMixHit* mh, V3 n, V2 uv, V3 n0,
+                                           V3 dpdu0, V3 sh_dpdv, V3 sh_dndu, V3 sh_dndv) {
+    // (the texture code is handed objects of this frame, as every other caller hands it its own: with a pointer of unknown origin among
+    // tex_eval's callers the compiler stops treating its TexHit as private memory, and every kernel that evaluates a texture changes)
+    const TexHit th = th_in;
+    const PtMix& mx = material_mix(sc, sc.materials[material]);
+    float ns[PT_MIX_MAX_NODES][2][3];
+    const uint32_t n_nodes = mx.n_nodes, n_leaves = mx.n_leaves;          // within PT_MIX_MAX_NODES / PT_MIX_MAX_LEAVES: the upload refuses anything else
+    for (uint32_t k = 0; k < n_nodes; k++) {
+        V3 a = ld3(mx.amount[k]);
+        if (mx.amount_prog[k]) { TexHit ev = th; a = tex_eval(sc.textures, sc.tex_prog + mx.amount_prog[k], ev, sc.images); }
+        const float s1[3] = {clamp_zero(a.x), clamp_zero(a.y), clamp_zero(a.z)};
+        for (int c = 0; c < 3; c++) { ns[k][0][c] = s1[c]; ns[k][1][c] = clamp_zero(1.0f - s1[c]); }
+    }
+    float eta0 = 1.0f;
+    uint32_t nl = 0;
+    for (uint32_t j = 0; j < n_leaves; j++) {
+        const int32_t mj = mx.leaf_material[j];
+        const PtMaterial* lm = &sc.materials[mj];
+        PtMaterial tm;
+        if (j == 0 && leaf0_done) lm = out;
+        else if (lm->textured) {
+            V3 c_n = n0, c_dpdu = dpdu0;          // the clone a later leaf works on is taken before any bump map (mix.rs:65) and thrown away
+            textured_lobes(sc, mj, th, &tm, n, uv, &c_n, &c_dpdu, sh_dpdv, sh_dndu, sh_dndv);
+            lm = &tm;
+        }
+        if (j == 0) eta0 = lm->bsdf_eta;
+        if (lm->has_bsdf)
+            for (uint32_t i = 0; i < lm->n_lobes && nl < PT_MIX_MAX_LOBES; i++) {          // (nl: a bound on a store; the upload counts a textured leaf at pt_lobes_most)
+                mh->lobes[nl] = lm->lobes[i];
+                mh->scales.lobe_leaf[nl] = j;
+                nl++;
+            }
+        const uint32_t nc = mx.scales.n_chain[j];
+        mh->scales.n_chain[j] = nc;
+        for (uint32_t c = 0; c < nc; c++) {
+            const uint32_t e = mx.chain[j][c], node = e & 0xffu, side = (e >> 8) & 1u;
+            for (int q = 0; q < 3; q++) mh->scales.s[j][c][q] = ns[node][side][q];
+        }
+    }
+    out->type = PT_MATERIAL_MIX;
+    out->has_bsdf = 1; out->nonspecular = 0; out->spec_mask = 0; out->bsdf_eta = eta0;
+    out->n_lobes = nl;
+    for (uint32_t i = 0; i < nl; i++) {
+        const uint32_t t = mh->lobes[i].type;
+        if (!(t & kSpecular)) out->nonspecular++;
+        if ((t & (kRefl | kSpecular)) == t) out->spec_mask |= 1u;
+        if ((t & (kTrans | kSpecular)) == t) out->spec_mask |= 2u;
+    }
+}
+// The leftmost leaf goes through textured_lobes from the kernel, on the kernel's own interaction, exactly as a textured material that is no
+// mix does: its bump map bends the frame the BSDF is built on.  The rest of the tree follows in mix_hit_lobes.
+PT_DEV void mix_hit(const PtScene& sc, int32_t material, const TexHit& th, PtMaterial* out, PtMixHit* mh, Surf& s) {
+    const int32_t m0 = material_mix(sc, sc.materials[material]).leaf_material[0];
+    const V3 n0 = s.sh_n, dpdu0 = s.sh_dpdu;
+    uint32_t leaf0_done = 0;
+    if (sc.materials[m0].textured) {
+        textured_lobes(sc, m0, th, out, s.n, s.uv, &s.sh_n, &s.sh_dpdu, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
+        leaf0_done = 1;
+    }
+    mix_hit_lobes(sc, material, th, out, leaf0_done, mh, s.n, s.uv, n0, dpdu0, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
+}
 // Sort key of a ray for pt_raysort.hip: Morton code of the cell of its origin inside the world bound (2^PT_SORT_CELL_BITS cells per axis), direction octant on top
 PT_DEV uint32_t ray_sort_key(const PtScene& sc, V3 o, V3 d) {
     const float fx = (o.x - sc.wb_min[0]) * sc.cell_scale[0], fy = (o.y - sc.wb_min[1]) * sc.cell_scale[1], fz = (o.z - sc.wb_min[2]) * sc.cell_scale[2];
@@ -2656,7 +2729,8 @@ PT_DEV float opaque_zero() { float z = 0.0f; asm volatile("" : "+v"(z)); return 
 // list because it overwrites the ray.  Both halves rebuild the interaction from (ray, record): the split trades that for register room.
 // ENV: the scene has an infinite light (the *_env kernels): escaped rays add its Le, next-event estimation samples it.
 // DELTA (with ENV): the scene has a delta light (k_shade_delta, k_shade_delta_inst): its estimate is f Li / pdf with no power heuristic, no BSDF half, no probe ray.
-template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false, bool DELTA = false>
+// MIX (with TEX, ENV and DELTA): the scene holds a Material "mix" (k_shade_mix, k_shade_mix_inst): the BSDF is the scaled lobe list (MBsdf, pt_bxdf.h).
+template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false, bool DELTA = false, bool MIX = false>
 PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, const uint32_t* list, uint32_t begin, uint32_t end,
                        uint32_t* ticket) {
     __shared__ unsigned long long s_vert;
@@ -2860,6 +2934,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             if (found && (int32_t)bounces < sc.max_depth) {
                 bool no_bsdf = s.material < 0;
                 PtMaterial tm;                     // TEX / RES: this hit's lobes
+                std::conditional_t<MIX, PtMixHit, PtNoMix> mh;      // MIX: the lobes and scale chains of a mix tree built at this hit
                 bool use_tm = false;
                 if constexpr (TEX) {
                     if (!no_bsdf && sc.materials[s.material].textured) {
@@ -2880,6 +2955,10 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf);
                         }
                         compute_differentials(th, s.p, s.n, s.dpdu, s.dpdv, has_diff, rdf);
+                        if constexpr (MIX) {
+                            if (sc.materials[s.material].mix1) mix_hit(sc, s.material, th, &tm, &mh, s);
+                            else textured_lobes(sc, s.material, th, &tm, s.n, s.uv, &s.sh_n, &s.sh_dpdu, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
+                        } else
                         textured_lobes(sc, s.material, th, &tm, s.n, s.uv, &s.sh_n, &s.sh_dpdu, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
                         use_tm = true;
                         no_bsdf = tm.has_bsdf == 0;
@@ -2912,7 +2991,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 } else {
                     if constexpr (PART != 1) n_vert++;
                     Bsdf b;
-                    GBsdf gb;
+                    std::conditional_t<MIX, MBsdf, GBsdf> gb;
                     bool nonspecular;
                     float bsdf_eta = 1.0f;
                     if constexpr (GENERAL) {
@@ -2921,6 +3000,13 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         gb.ss = normalize(s.sh_dpdu);
                         gb.ts = normalize(cross(gb.ns, gb.ss));
                         gb.lobes = m.lobes; gb.n_lobes = m.n_lobes;
+                        if constexpr (MIX) {
+                            gb.scales = nullptr;
+                            if (sc.materials[s.material].mix1) {
+                                if (use_tm) { gb.lobes = mh.lobes; gb.scales = &mh.scales; }             // built at this hit
+                                else { const PtMix& mx = material_mix(sc, sc.materials[s.material]); gb.lobes = mx.lobes; gb.n_lobes = mx.n_lobes; gb.scales = &mx.scales; }
+                            }
+                        }
 #if PT_LOBES_IN_LDS
                         if constexpr (!INST && !TEX) {          // (the one-kernel textured form spills as it is: 109 registers, 171 with this)
                             // The lobe evaluators walk the material's lobe list four times per vertex (f, pdf, two sample_f), a dependent chain of
@@ -2956,13 +3042,16 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                     }
                     const uint32_t kNoSpec = PT_BSDF_ALL & ~PT_BSDF_SPECULAR;
                     auto eval_f = [&](V3 wo_w, V3 wi_w) -> V3 {
-                        if constexpr (GENERAL) return gbsdf_f(gb, wo_w, wi_w, kNoSpec); else return bsdf_f(b, wo_w, wi_w);
+                        if constexpr (MIX) return mbsdf_f(gb, wo_w, wi_w, kNoSpec);
+                        else if constexpr (GENERAL) return gbsdf_f(gb, wo_w, wi_w, kNoSpec); else return bsdf_f(b, wo_w, wi_w);
                     };
                     auto eval_pdf = [&](V3 wo_w, V3 wi_w) -> float {
-                        if constexpr (GENERAL) return gbsdf_pdf(gb, wo_w, wi_w, kNoSpec); else return bsdf_pdf(b, wo_w, wi_w);
+                        if constexpr (MIX) return mbsdf_pdf(gb, wo_w, wi_w, kNoSpec);
+                        else if constexpr (GENERAL) return gbsdf_pdf(gb, wo_w, wi_w, kNoSpec); else return bsdf_pdf(b, wo_w, wi_w);
                     };
                     auto sample_bsdf = [&](V3 wo_w, V2 uu, uint32_t fl, V3* f_o, V3* wi_o, float* pdf_o, uint32_t* type_o) -> bool {
-                        if constexpr (GENERAL) return gbsdf_sample_f(gb, wo_w, uu, fl, f_o, wi_o, pdf_o, type_o);
+                        if constexpr (MIX) return mbsdf_sample_f(gb, wo_w, uu, fl, f_o, wi_o, pdf_o, type_o);
+                        else if constexpr (GENERAL) return gbsdf_sample_f(gb, wo_w, uu, fl, f_o, wi_o, pdf_o, type_o);
                         else { *type_o = PT_BSDF_REFLECTION | PT_BSDF_DIFFUSE; return bsdf_sample_f(b, wo_w, uu, f_o, wi_o, pdf_o); }
                     };
                     PT_SHP(1);
@@ -3337,6 +3426,14 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_sha
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_delta_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
+// Scenes that hold a Material "mix": the same two kernels once more, with the scaled lobe list as their BSDF (MBsdf) -- spheres, per-hit textures,
+// environment and delta lights compiled in, so a mix works beside every light and shape the path has.  Scenes without a mix never launch them.
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_mix(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, false, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_mix_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+    shade_body<true, true, true, true, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+}
 
 // ============================================================ film
 PT_DEV V3 validate_radiance(V3 l) {    // sampler.rs:151-176
@@ -3688,6 +3785,42 @@ extern "C" __global__ void k_bsdf_sample(PtScene sc, uint32_t material, uint32_t
         type[i] = t;
     }
 }
+// ... of a scene that holds a Material "mix": the scaled lobe list (a constant tree's PtMix record; any other material rides unscaled)
+PT_DEV MBsdf canonical_mbsdf(const PtScene& sc, uint32_t material) {
+    MBsdf mb;
+    mb.ns = mk3(0.0f, 0.0f, 1.0f); mb.ng = mb.ns;
+    mb.ss = normalize(mk3(1.0f, 0.0f, 0.0f));
+    mb.ts = normalize(cross(mb.ns, mb.ss));
+    mb.lobes = sc.materials[material].lobes;
+    mb.n_lobes = sc.materials[material].n_lobes;
+    mb.scales = nullptr;
+    const uint32_t mix1 = sc.materials[material].mix1;
+    if (mix1 && mix1 <= scene_n_mix(sc)) { const PtMix& mx = material_mix(sc, sc.materials[material]); mb.lobes = mx.lobes; mb.n_lobes = mx.n_lobes; mb.scales = &mx.scales; }
+    return mb;
+}
+extern "C" __global__ void k_bsdf_eval_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        MBsdf mb = canonical_mbsdf(sc, material);
+        V3 o = ld3(wo + 3 * i), w = ld3(wi + 3 * i);
+        V3 r = mbsdf_f(mb, o, w, flags);
+        f[3 * i] = r.x; f[3 * i + 1] = r.y; f[3 * i + 2] = r.z;
+        pdf[i] = mbsdf_pdf(mb, o, w, flags);
+    }
+}
+extern "C" __global__ void k_bsdf_sample_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f, float* wi,
+                                             float* pdf, uint32_t* type) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        MBsdf mb = canonical_mbsdf(sc, material);
+        V3 r = mk3(0.0f, 0.0f, 0.0f), w = r;
+        float p = 0.0f;
+        uint32_t t = 0;
+        if (!mbsdf_sample_f(mb, ld3(wo + 3 * i), mk2(u[2 * i], u[2 * i + 1]), flags, &r, &w, &p, &t)) { r = mk3(0.0f, 0.0f, 0.0f); w = r; p = 0.0f; t = 0; }
+        f[3 * i] = r.x; f[3 * i + 1] = r.y; f[3 * i + 2] = r.z;
+        wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z;
+        pdf[i] = p;
+        type[i] = t;
+    }
+}
 
 // ============================================================ recursive integrators (directlighting, whitted)
 // DirectLightingIntegrator::li (integrators/directlighting.rs:66-135) and WhittedIntegrator::li (integrators/whitted.rs:38-110) with
@@ -3703,9 +3836,13 @@ extern "C" __global__ void k_bsdf_sample(PtScene sc, uint32_t material, uint32_t
 //                  the root has returned
 // The interaction of a frame is rebuilt from its ray and hit record whenever it is needed again (after the reflect subtree, for the
 // transmit sample): the same arithmetic, so the same values.  One kernel variant (spheres, textures, instances all compiled in).
-struct RecNode {
+// MIX: the scene holds a Material "mix" (k_rec_enter_mix / k_rec_next_mix): the node's BSDF is the scaled lobe list, a per-hit tree's lobes sit in `mh`
+template <bool MIX> struct RecMixPart {};
+template <> struct RecMixPart<true> { PtMixHit mh; };
+template <bool MIX>
+struct RecNodeT : RecMixPart<MIX> {
     Surf s;
-    GBsdf gb;
+    std::conditional_t<MIX, MBsdf, GBsdf> gb;
     PtMaterial tm;
     TexHit th;
     V3 n_before;
@@ -3713,10 +3850,11 @@ struct RecNode {
     uint32_t spec_mask;          // PtMaterial::spec_mask of the node's BSDF
     bool found, has_bsdf;
 };
+using RecNode = RecNodeT<false>;
 // FULL = false: the instantiation for scenes without spheres, instances and textured materials (the triangle-only test, no texture programs, no
 // per-hit lobe list in scratch): what `directlighting` / `whitted` run on BASELINE's scenes.  FULL = true: everything compiled in.
-template <bool FULL>
-PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t inst, bool has_diff, const RayDiffs& rdf, RecNode& nd) {
+template <bool FULL, bool MIX = false>
+PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t inst, bool has_diff, const RayDiffs& rdf, RecNodeT<MIX>& nd) {
     float thit;
     if constexpr (FULL) nd.found = rec >= 0 && make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, nd.s, &thit);
     else nd.found = rec >= 0 && make_surf_any<false>(sc, ro, rd, (uint32_t)rec, nd.s, &thit);
@@ -3731,6 +3869,10 @@ PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t ins
     const PtMaterial* m = &sc.materials[nd.s.material];
     if constexpr (FULL) {
         if (m->textured) {
+            if constexpr (MIX) {
+                if (m->mix1) mix_hit(sc, nd.s.material, nd.th, &nd.tm, &nd.mh, nd.s);
+                else textured_lobes(sc, nd.s.material, nd.th, &nd.tm, nd.s.n, nd.s.uv, &nd.s.sh_n, &nd.s.sh_dpdu, nd.s.sh_dpdv, nd.s.sh_dndu, nd.s.sh_dndv);
+            } else
             textured_lobes(sc, nd.s.material, nd.th, &nd.tm, nd.s.n, nd.s.uv, &nd.s.sh_n, &nd.s.sh_dpdu, nd.s.sh_dpdv, nd.s.sh_dndu, nd.s.sh_dndv);
             m = &nd.tm;
         }
@@ -3741,6 +3883,14 @@ PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t ins
     nd.gb.ss = normalize(nd.s.sh_dpdu);
     nd.gb.ts = normalize(cross(nd.gb.ns, nd.gb.ss));
     nd.gb.lobes = m->lobes; nd.gb.n_lobes = m->n_lobes;
+    if constexpr (MIX) {
+        nd.gb.scales = nullptr;
+        const PtMaterial& m0 = sc.materials[nd.s.material];
+        if (m0.mix1) {
+            if (m0.textured) { nd.gb.lobes = nd.mh.lobes; nd.gb.scales = &nd.mh.scales; }          // built at this hit
+            else { const PtMix& mx = material_mix(sc, m0); nd.gb.lobes = mx.lobes; nd.gb.n_lobes = mx.n_lobes; nd.gb.scales = &mx.scales; }
+        }
+    }
     nd.bsdf_eta = m->bsdf_eta;
     nd.spec_mask = m->spec_mask;
 }
@@ -3748,8 +3898,8 @@ PT_DEV float4* rec_frame(const PtRec& R, uint32_t depth, uint32_t k, uint32_t p)
 // estimate_direct (sample_lights.rs:178-328) for light `light_num`: the two MIS terms and their rays go to entry e, the rays' results
 // are combined by k_rec_next.  Returns the PT_NEE_* flags of the entry.
 // ENV: the scene has an infinite light (k_rec_enter_env): its map is sampled, B counts when the probe escapes (k_rec_next_env)
-template <bool FULL, bool ENV = false>
-PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const RecNode& nd, uint32_t light_num, V2 u_light, V2 u_scat, uint32_t e, float divisor = 1.0f) {
+template <bool FULL, bool ENV = false, bool MIX = false>
+PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const RecNodeT<MIX>& nd, uint32_t light_num, V2 u_light, V2 u_scat, uint32_t e, float divisor = 1.0f) {
     const Surf& s = nd.s;
     const PtLight& lt = sc.lights[light_num];
     const uint32_t kNoSpec = PT_BSDF_ALL & ~PT_BSDF_SPECULAR;
@@ -3762,8 +3912,8 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
     else sampled = light_sample_any<FULL>(sc, lt, s.p, s.p_error, s.n, u_light, &li, &wi, &lpdf, &lp, &lperr, &ln);
     if (sampled) {
         if (lpdf > 0.0f && !is_black(li)) {
-            V3 f = gbsdf_f(nd.gb, s.wo, wi, kNoSpec) * abs_dot(wi, s.sh_n);
-            float spdf = gbsdf_pdf(nd.gb, s.wo, wi, kNoSpec);
+            V3 f = xbsdf_f(nd.gb, s.wo, wi, kNoSpec) * abs_dot(wi, s.sh_n);
+            float spdf = xbsdf_pdf(nd.gb, s.wo, wi, kNoSpec);
             if (!is_black(f)) {
                 V3 origin = offset_ray_origin(s.p, s.p_error, s.n, lp - s.p);
                 V3 target = offset_ray_origin(lp, lperr, ln, origin - lp);
@@ -3782,7 +3932,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
     V3 f2, wi2;
     float spdf2;
     uint32_t type2;
-    if (!light_is_delta<ENV>(lt) && gbsdf_sample_f(nd.gb, s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
+    if (!light_is_delta<ENV>(lt) && xbsdf_sample_f(nd.gb, s.wo, u_scat, kNoSpec, &f2, &wi2, &spdf2, &type2)) {
         V3 f = f2 * abs_dot(wi2, s.sh_n);
         if (!is_black(f) && spdf2 > 0.0f) {
             V3 po = offset_ray_origin(s.p, s.p_error, s.n, wi2);
@@ -3852,7 +4002,7 @@ PT_DEV RayDiffs rec_load_diff(const PtRec& R, uint32_t p) {
     d.rx_d = f4_3(R.diff[2 * (size_t)R.n_paths + p]); d.ry_d = f4_3(R.diff[3 * (size_t)R.n_paths + p]);
     return d;
 }
-template <bool FULL, bool ENV = false>
+template <bool FULL, bool ENV = false, bool MIX = false>
 PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtQueues& Qn, const PtRec& R, PtCounters* cnt) {
     const uint32_t n = Q.counts[PT_Q_CUR];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3875,8 +4025,8 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
         RayDiffs rdf;
         rdf.rx_o = rdf.ry_o = rdf.rx_d = rdf.ry_d = mk3(0.0f, 0.0f, 0.0f);
         if (has_diff) rdf = rec_load_diff(R, p);
-        RecNode nd;
-        rec_build<FULL>(sc, ro, rd, rec, inst, has_diff, rdf, nd);
+        RecNodeT<MIX> nd;
+        rec_build<FULL, MIX>(sc, ro, rd, rec, inst, has_diff, rdf, nd);
         uint32_t outcome = PT_REC_OUT_FRAME;
         if (!nd.found) outcome = PT_REC_OUT_RETURN0;              // the lights' le(ray) sum: zero for area lights
         else if (!nd.has_bsdf) {
@@ -3911,7 +4061,7 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                     if constexpr (ENV) sampled = light_sample_kind<FULL, true>(sc, lt, nd.s.p, nd.s.p_error, nd.s.n, u, &li, &wi, &lpdf, &lp, &lperr, &ln);
                     else sampled = light_sample_any<FULL>(sc, lt, nd.s.p, nd.s.p_error, nd.s.n, u, &li, &wi, &lpdf, &lp, &lperr, &ln);
                     if (sampled && !(lpdf <= 0.0f || is_black(li))) {
-                        V3 f = gbsdf_f(nd.gb, nd.s.wo, wi, PT_BSDF_ALL);
+                        V3 f = xbsdf_f(nd.gb, nd.s.wo, wi, PT_BSDF_ALL);
                         if (!is_black(f)) {
                             V3 origin = offset_ray_origin(nd.s.p, nd.s.p_error, nd.s.n, lp - nd.s.p);
                             V3 target = offset_ray_origin(lp, lperr, ln, origin - lp);
@@ -3942,13 +4092,13 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                                 for (uint32_t k = 0; k < n; k++) {
                                     const uint64_t idx = n == 1u ? sm.index : sampler_index(sc, sample_num * n + k, sm.px, sm.py);
                                     const V2 u = mk2(sample_dimension(sc, idx, 5u, sm.px, sm.py), sample_dimension(sc, idx, 6u, sm.px, sm.py));
-                                    rec_estimate_direct<FULL, ENV>(sc, R, nd, j, u, u, e0 + off + k, (float)n);
+                                    rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u, u, e0 + off + k, (float)n);
                                 }
                             } else {
                                 arr = R.n_arrays;
                                 const V2 u_light = sm.get_2d(sc);
                                 const V2 u_scat = sm.get_2d(sc);
-                                rec_estimate_direct<FULL, ENV>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f);
+                                rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f);
                                 for (uint32_t k = 1; k < n; k++) R.flags[e0 + off + k] = 0u;
                             }
                             off += n;
@@ -3961,7 +4111,7 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                         const float light_pdf = 1.0f / (float)sc.n_lights;
                         const V2 u_light = sm.get_2d(sc);
                         const V2 u_scat = sm.get_2d(sc);
-                        rec_estimate_direct<FULL, ENV>(sc, R, nd, light_num, u_light, u_scat, e0);
+                        rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, light_num, u_light, u_scat, e0);
                         float4 a = R.A[e0];
                         a.w = light_pdf;
                         R.A[e0] = a;
@@ -4039,7 +4189,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_r
     rec_enter_body<true, true>(sc, P, Q, Qn, R, cnt);
 }
 // specular_reflect / specular_transmit at the frame `depth` (sampler.rs:37-143): true = a child ray was set up (cur ray, differentials, pending f / scale)
-template <bool FULL>
+template <bool FULL, bool MIX = false>
 PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R, uint32_t p, uint32_t depth, bool transmit, Sampler& sm, V3* pend_f, float* pend_scale, uint32_t* child_flags) {
     // A BSDF without a lobe that matches (REFLECTION | SPECULAR) / (TRANSMISSION | SPECULAR): the reference draws its 2-D sample
     // (sampler.rs:45, :92) and BSDF::sample_f returns None at `matching_comps == 0` (bsdf.rs:104-107) -- every Matte, Plastic, Metal or Substrate
@@ -4053,13 +4203,13 @@ PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R
     RayDiffs rdf;
     rdf.rx_o = f4_3(*rec_frame(R, depth, 2, p)); rdf.ry_o = f4_3(*rec_frame(R, depth, 3, p));
     rdf.rx_d = f4_3(*rec_frame(R, depth, 4, p)); rdf.ry_d = f4_3(*rec_frame(R, depth, 5, p));
-    RecNode nd;
-    rec_build<FULL>(sc, ro, rd, rec, iw & 0x7fffffffu, has_diff, rdf, nd);
+    RecNodeT<MIX> nd;
+    rec_build<FULL, MIX>(sc, ro, rd, rec, iw & 0x7fffffffu, has_diff, rdf, nd);
     const V2 u = sm.get_2d(sc);
     V3 f, wi;
     float pdf;
     uint32_t ty;
-    if (!gbsdf_sample_f(nd.gb, nd.s.wo, u, (transmit ? PT_BSDF_TRANSMISSION : PT_BSDF_REFLECTION) | PT_BSDF_SPECULAR, &f, &wi, &pdf, &ty)) return false;
+    if (!xbsdf_sample_f(nd.gb, nd.s.wo, u, (transmit ? PT_BSDF_TRANSMISSION : PT_BSDF_REFLECTION) | PT_BSDF_SPECULAR, &f, &wi, &pdf, &ty)) return false;
     const Surf& s = nd.s;
     const V3 wo = s.wo;
     V3 ns = s.sh_n;
@@ -4108,7 +4258,7 @@ PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R
     *pend_scale = wi_ns / pdf;
     return true;
 }
-template <bool FULL, bool ENV = false>
+template <bool FULL, bool ENV = false, bool MIX = false>
 PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtRec& R) {
     const uint32_t n = Q.counts[PT_Q_CUR];
     const uint32_t lane = threadIdx.x & 63;
@@ -4223,11 +4373,11 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
                         uint32_t cflags;
                         bool child = false;
                         if (phase == 0) {
-                            child = rec_sample_child<FULL>(sc, P, R, p, (uint32_t)d, false, sm, &pend_f, &pend_scale, &cflags);
+                            child = rec_sample_child<FULL, MIX>(sc, P, R, p, (uint32_t)d, false, sm, &pend_f, &pend_scale, &cflags);
                             if (!child) { l = l + mk3(0.0f, 0.0f, 0.0f); phase = 1; }
                         }
                         if (!child && phase == 1) {
-                            child = rec_sample_child<FULL>(sc, P, R, p, (uint32_t)d, true, sm, &pend_f, &pend_scale, &cflags);
+                            child = rec_sample_child<FULL, MIX>(sc, P, R, p, (uint32_t)d, true, sm, &pend_f, &pend_scale, &cflags);
                             if (child) phase = 2;
                             else l = l + mk3(0.0f, 0.0f, 0.0f);
                         } else if (child) phase = 1;
@@ -4264,6 +4414,11 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true>(sc, P, Q, R); }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_plain(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<false>(sc, P, Q, R); }
 extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_env(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true>(sc, P, Q, R); }
+// Scenes that hold a Material "mix": everything compiled in as in the _env pair, with the scaled lobe list as the node's BSDF
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_mix(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+    rec_enter_body<true, true, true>(sc, P, Q, Qn, R, cnt);
+}
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_mix(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true, true>(sc, P, Q, R); }
 hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtRec& R, uint32_t n) {
     hipLaunchKernelGGL(k_rec_init, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, R, n);
     return hipGetLastError();
@@ -4271,13 +4426,15 @@ hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPat
 hipError_t ptk_rec_enter(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtQueues& Qn, const PtRec& R, PtCounters* cnt,
                          uint32_t lights_per_node) {
     (void)lights_per_node;
-    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_enter_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
+    if (scene_n_mix(sc)) hipLaunchKernelGGL(k_rec_enter_mix, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
+    else if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_enter_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_enter, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     else hipLaunchKernelGGL(k_rec_enter_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, Qn, R, cnt);
     return hipGetLastError();
 }
 hipError_t ptk_rec_next(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, const PtRec& R) {
-    if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_next_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
+    if (scene_n_mix(sc)) hipLaunchKernelGGL(k_rec_next_mix, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
+    else if (sc.n_envs || sc.n_deltas) hipLaunchKernelGGL(k_rec_next_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     else if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_rec_next, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     else hipLaunchKernelGGL(k_rec_next_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, R);
     return hipGetLastError();
@@ -4307,7 +4464,9 @@ PT_DEV void aov_bump(const PtScene& sc, uint32_t prog, const TexHit& th, Surf& s
     s.sh_n = face_forward(normalize(cross(dpdu, dpdv)), s.n);          // set_shading_geometry(.., false) (surface_interaction.rs:140-161)
     s.sh_dpdu = dpdu; s.sh_dpdv = dpdv;
 }
-template <bool FULL>
+// MIX (k_aov_mix): ns and the shading dpdu / dpdv of a Material "mix" are its leftmost leaf's after that leaf's bump map (mix.rs:83: the BSDF is
+// allocated from the interaction as child 1 left it); no other leaf's bump map reaches the interaction
+template <bool FULL, bool MIX = false>
 PT_DEV void aov_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t base = (blockIdx.x * blockDim.x + threadIdx.x) - lane; base < n_paths; base += gridDim.x * blockDim.x) {
@@ -4339,6 +4498,14 @@ PT_DEV void aov_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, int3
                     th.p = sf.p; th.uv = sf.uv;
                     compute_differentials(th, sf.p, sf.n, sf.dpdu, sf.dpdv, true, rdf);
                     if constexpr (FULL) {          // GeometricPrimitive::compute_scattering_functions: a surface without a material stops here
+                        if constexpr (MIX) {
+                            int32_t bm = sf.material;
+                            if (bm >= 0 && sc.materials[bm].mix1) bm = material_mix(sc, sc.materials[bm]).leaf_material[0];
+                            if (bm >= 0 && sc.materials[bm].textured) {
+                                const uint32_t prog = sc.mat_params[bm].prog[8];
+                                if (prog) aov_bump(sc, prog, th, sf);
+                            }
+                        } else
                         if (sf.material >= 0 && sc.materials[sf.material].textured) {
                             const uint32_t prog = sc.mat_params[sf.material].prog[8];
                             if (prog) aov_bump(sc, prog, th, sf);
@@ -4378,7 +4545,11 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_a
 extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_aov_plain(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
     aov_body<false>(sc, P, n_paths, target, scale, cnt);
 }
+extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov_mix(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    aov_body<true, true>(sc, P, n_paths, target, scale, cnt);
+}
 hipError_t ptk_aov(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+    if (scene_n_mix(sc)) { hipLaunchKernelGGL(k_aov_mix, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, n_paths, target, scale, cnt); return hipGetLastError(); }
     if (sc.n_spheres || sc.n_instances || sc.textured) hipLaunchKernelGGL(k_aov, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, n_paths, target, scale, cnt);
     else hipLaunchKernelGGL(k_aov_plain, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, n_paths, target, scale, cnt);
     return hipGetLastError();
@@ -4585,6 +4756,11 @@ hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode) {
 }
 int ptk_nee_split_default() { return PT_NEE_SPLIT_DEFAULT; }
 hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nsplit, int local_sort) {
+    if (scene_n_mix(sc)) {          // a Material "mix": one kernel over the unsorted queue as well, every light and shape compiled in
+        if (sc.n_instances) hipLaunchKernelGGL(k_shade_mix_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        else hipLaunchKernelGGL(k_shade_mix, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
+        return PT_LAUNCH_CHECK();
+    }
     if (sc.n_envs || sc.n_deltas) {
         // an infinite or a delta light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort, the split next-event kernels
         // (PBRTGPU_NEE_SPLIT), the local sort (PBRTGPU_SHADE_LOCAL), the textured split (PBRTGPU_TEX_SPLIT) and PBRTGPU_SHADE_UNSORTED are routed around
@@ -4714,12 +4890,14 @@ hipError_t ptk_camera_rays(hipStream_t st, const PtScene& sc, uint32_t n, const 
 }
 hipError_t ptk_bsdf_eval(hipStream_t st, const PtScene& sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f,
                          float* pdf) {
-    hipLaunchKernelGGL(k_bsdf_eval, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, wi, flags, f, pdf);
+    if (scene_n_mix(sc)) hipLaunchKernelGGL(k_bsdf_eval_mix, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, wi, flags, f, pdf);
+    else hipLaunchKernelGGL(k_bsdf_eval, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, wi, flags, f, pdf);
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_bsdf_sample(hipStream_t st, const PtScene& sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f,
                            float* wi, float* pdf, uint32_t* type) {
-    hipLaunchKernelGGL(k_bsdf_sample, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, u, flags, f, wi, pdf, type);
+    if (scene_n_mix(sc)) hipLaunchKernelGGL(k_bsdf_sample_mix, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, u, flags, f, wi, pdf, type);
+    else hipLaunchKernelGGL(k_bsdf_sample, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, u, flags, f, wi, pdf, type);
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_sobol_samples(hipStream_t st, const PtScene& sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, const uint32_t* dim,

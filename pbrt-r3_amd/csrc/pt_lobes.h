@@ -26,6 +26,17 @@ PT_HD inline PtLobe* push_lobe(PtMaterial& m, uint32_t kind, uint32_t type, cons
     l->ax = l->ay = 0.001f;
     return l;
 }
+// The most BxDFs build_lobes below can add for a material type (a mix tree counts a texture-driven leaf at this: pt_context.cpp).  Kept beside
+// the switch it summarises: a type that gains a lobe there changes its entry here.
+PT_HD inline uint32_t pt_lobes_most(int32_t type) {
+    switch (type) {
+        case PT_MATERIAL_MATTE: case PT_MATERIAL_MIRROR: case PT_MATERIAL_METAL: case PT_MATERIAL_SUBSTRATE: return 1;
+        case PT_MATERIAL_PLASTIC: case PT_MATERIAL_GLASS: return 2;
+        case PT_MATERIAL_TRANSLUCENT: return 4;
+        case PT_MATERIAL_UBER: return 5;
+        default: return 0;
+    }
+}
 PT_HD inline void set_distribution(PtLobe* l, float ax, float ay) {                               // TrowbridgeReitzDistribution::new
     l->ax = 0.001f > ax ? 0.001f : ax;     // f32::max: a NaN roughness becomes 0.001
     l->ay = 0.001f > ay ? 0.001f : ay;

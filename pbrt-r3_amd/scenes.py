@@ -603,6 +603,21 @@ class SceneBuilder:
             if isinstance(v, Tex):
                 setattr(self.materials[self.cur_material], "tex_" + k, v.index + 1)
 
+    def material_mix(self, m1, m2, amount=(0.5, 0.5, 0.5)):
+        """materials/mix.rs:98-104: m1 / m2 are material indices (cur_material after a material_* call; a child may itself be a mix),
+        "amount" a colour or a Tex.  amount weights m1 and 1 - amount weights m2.  The children travel as index + 1 in tex_kr / tex_kt,
+        "amount" in kd / tex_kd; a textured amount keeps the reference's default 0.5 as its (unused) constant."""
+        for c in (m1, m2):
+            if not 0 <= int(c) < len(self.materials):
+                raise ValueError("material_mix: child %r is not a material defined before the mix" % (c,))
+        if isinstance(amount, (int, float)):
+            amount = (float(amount),) * 3
+        self.cur_material = self._add_material(capi.PT_MATERIAL_MIX, (0.5,) * 3 if isinstance(amount, Tex) else amount)
+        m = self.materials[self.cur_material]
+        m.tex_kr, m.tex_kt = int(m1) + 1, int(m2) + 1
+        if isinstance(amount, Tex):
+            m.tex_kd = amount.index + 1
+
     def material_none(self):
         self.cur_material = -1
 
