@@ -252,8 +252,19 @@ typedef struct {
 /* Sphere (src/shapes/sphere.rs:7-41, create_sphere_shape :401-420).  The only analytic shape on the
  * path: pbrt-v3's killeroo-simple lights its scene with two of them.  It lives in the same BVH as
  * the triangles (one primitive), is tested with the reference's EFloat interval arithmetic
- * (core/efloat/efloat.rs) in object space, and carries its own material / area light. */
+ * (core/efloat/efloat.rs) in object space, and carries its own material / area light.
+ *
+ * The same record describes the other analytic shapes, told apart by `kind` (0, what every caller that zeroes the record passes, is the
+ * sphere):
+ *   PT_SHAPE_CYLINDER (src/shapes/cylinder.rs:11-38, create_cylinder_shape :329-363): radius, zmin, zmax and phimax are what
+ *     Cylinder::new takes; zmin / zmax are NOT clamped to the radius and are swapped when zmin > zmax.
+ *   PT_SHAPE_DISK (src/shapes/disk.rs:8-35, create_disk_shape :194-214): radius and phimax keep their meaning, `zmin` is the disk's
+ *     "height", zmax is ignored, inner_radius is "innerradius" (0 <= inner_radius < radius).
+ * material, area_light, before_triangle, object, order, the flags and the two matrices mean for them what they mean for a sphere. */
 #define PT_SPHERE_REVERSE_ORIENTATION 1u
+#define PT_SHAPE_SPHERE   0u
+#define PT_SHAPE_CYLINDER 1u
+#define PT_SHAPE_DISK     2u
 typedef struct {
     float object_to_world[16];  /* row-major Transform.m of the CTM at the Shape directive */
     float world_to_object[16];  /* Transform.m_inv (the reference keeps both; it never re-inverts) */
@@ -268,7 +279,8 @@ typedef struct {
                                  * over spheres[]; equal values keep array order. */
     uint32_t object;            /* 0: world primitive; k: belongs to object k - 1 */
     uint32_t order;             /* creation order among spheres and instances that share a before_triangle value */
-    uint32_t reserved[2];
+    uint32_t kind;              /* PT_SHAPE_SPHERE (0), PT_SHAPE_CYLINDER or PT_SHAPE_DISK */
+    float inner_radius;         /* "innerradius" of a disk; read for a disk only */
 } pt_sphere;
 
 /* ObjectInstance (scene_context.rs:1349-1391): a TransformedPrimitive (core/primitive/transformed_primitive.rs) over the
@@ -518,6 +530,10 @@ pt_status pt_light_sample_li(pt_context* ctx, uint32_t light, uint32_t n, const 
 /* InfiniteAreaLight::pdf_li (infinite.rs:161-180) for n world directions wi (3 floats each).  Infinite lights; a delta light's is 0
  * for every direction (point.rs:65-67, spot.rs:86-88, distant.rs:83-85). */
 pt_status pt_light_pdf_li(pt_context* ctx, uint32_t light, uint32_t n, const float* wi, float* pdf_out);
+/* DiffuseAreaLight::pdf_li = the default Shape::pdf_from (shape.rs:40-54) of area light `light` for n directions wi (3 floats each) from
+ * n reference points ref_p (3 floats each; bare points, as pt_light_sample_li takes them): the light's shape is intersected along wi and
+ * the area density converted to solid angle; 0 where the ray misses the shape or the density is infinite.  Area lights only. */
+pt_status pt_light_pdf_from(pt_context* ctx, uint32_t light, uint32_t n, const float* ref_p, const float* wi, float* pdf_out);
 /* InfiniteAreaLight::le (infinite.rs:111-122) for n world ray directions d (3 floats each): rgb_out 3 floats.  Infinite lights only (a delta
  * light has no le: refused). */
 pt_status pt_light_le(pt_context* ctx, uint32_t light, uint32_t n, const float* d, float* rgb_out);

@@ -60,9 +60,13 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
  * MakeNamedMaterial type "mix" become PT_MATERIAL_MIX records (children before the mix in the material table); without the bit, and through
  * every other entry point, they are refused as before (PT_ERR_UNSUPPORTED, the same message).  The same stop-gap as
  * pth_options.delta_lights, for the same reason (a test pins the refusal of the plain entry points), and it goes away with it.
- * PTH_FEATURE_DELTA_LIGHTS: what pth_options.delta_lights != 0 does; the old field keeps working.  pbrt_gpu sets both. */
+ * PTH_FEATURE_DELTA_LIGHTS: what pth_options.delta_lights != 0 does; the old field keeps working.
+ * PTH_FEATURE_QUADRIC_SHAPES: Shape "cylinder" and Shape "disk" become pt_sphere records of kind PT_SHAPE_CYLINDER / PT_SHAPE_DISK (a
+ * cylinder of radius 0 is skipped with a warning); without the bit they are refused as before, with the same message.  pbrt_gpu sets
+ * all three. */
 #define PTH_FEATURE_MIX_MATERIAL 1u
 #define PTH_FEATURE_DELTA_LIGHTS 2u
+#define PTH_FEATURE_QUADRIC_SHAPES 4u
 pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */

@@ -16,7 +16,8 @@ PT_MATERIAL_GLASS, PT_MATERIAL_METAL, PT_MATERIAL_UBER, PT_MATERIAL_SUBSTRATE = 
 PT_MATERIAL_TRANSLUCENT = 8
 PT_MATERIAL_MIX = 9
 PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
-PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS = 1, 2
+PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES = 1, 2, 4
+PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER, PT_SHAPE_DISK = 0, 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
 PT_MESH_HAS_N, PT_MESH_HAS_S, PT_MESH_HAS_UV = 8, 16, 32
@@ -99,7 +100,7 @@ class pt_sphere(C.Structure):
     _fields_ = [("object_to_world", C.c_float * 16), ("world_to_object", C.c_float * 16),
                 ("radius", C.c_float), ("zmin", C.c_float), ("zmax", C.c_float), ("phimax", C.c_float),
                 ("flags", C.c_uint32), ("material", C.c_int32), ("area_light", C.c_int32),
-                ("before_triangle", C.c_uint32), ("object", C.c_uint32), ("order", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+                ("before_triangle", C.c_uint32), ("object", C.c_uint32), ("order", C.c_uint32), ("kind", C.c_uint32), ("inner_radius", C.c_float)]
 
 
 class pt_instance(C.Structure):
@@ -181,7 +182,7 @@ SYMBOLS = [
     "pt_film_device_xyzw", "pt_film_commit_xyzw", "pt_film_allreduce", "pt_film_add_xyzw", "pt_film_resolve_rgb", "pt_trace_closest", "pt_trace_any", "pt_trace_wavefront",
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
-    "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_le", "pt_scene_set_alpha_masks",
+    "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_pdf_from", "pt_light_le", "pt_scene_set_alpha_masks",
     "pt_scene_set_aov", "pt_scene_set_delta_lights",
 ]
 
@@ -260,9 +261,10 @@ class ParsedScene:
     """A scene parsed from .pbrt text by the C++ front end (include/pbrtgpu_host.h).  Quacks like
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
-    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False):
+    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False):
         """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
-        mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before."""
+        mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before.
+        quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -281,11 +283,12 @@ class ParsedScene:
         err = C.create_string_buffer(2048)
         opts = pth_options(0, 0, 0, 1)
         feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
-        features = PTH_FEATURE_MIX_MATERIAL | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0)
-        if mix_materials and filename is not None:
+        features = (PTH_FEATURE_MIX_MATERIAL if mix_materials else 0) | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0) | \
+                   (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0)
+        if (mix_materials or quadric_shapes) and filename is not None:
             L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
             st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
-        elif mix_materials:
+        elif mix_materials or quadric_shapes:
             L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
             st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
         elif filename is not None and delta_lights:
@@ -636,6 +639,17 @@ class Context:
         wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
         pdf = np.empty(len(wi), np.float32)
         self._check(self.lib.pt_light_pdf_li(self.h, C.c_uint32(light), C.c_uint32(len(wi)), _ptr(wi), _ptr(pdf)))
+        return pdf
+
+    def light_pdf_from(self, light, ref_p, wi):
+        """DiffuseAreaLight::pdf_li (the default Shape::pdf_from) of area light `light` for directions wi from the points ref_p."""
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        ref_p = np.ascontiguousarray(ref_p, np.float32).reshape(-1, 3)
+        if len(ref_p) == 1 and len(wi) > 1:
+            ref_p = np.ascontiguousarray(np.repeat(ref_p, len(wi), axis=0))
+        pdf = np.empty(len(wi), np.float32)
+        self.lib.pt_light_pdf_from.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.pt_light_pdf_from(self.h, C.c_uint32(light), C.c_uint32(len(wi)), _ptr(ref_p), _ptr(wi), _ptr(pdf)))
         return pdf
 
     def light_le(self, light, d):

@@ -216,7 +216,7 @@ int main(int argc, char** argv) {
     opts.delta_lights = 1;           // LightSource "spot" / "distant" render here (pt_scene_set_delta_lights below)
     char err[1024] = {0};
     pth_scene* scene = nullptr;
-    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS, &scene, err, sizeof(err));      // Material "mix" renders here
+    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS | PTH_FEATURE_QUADRIC_SHAPES, &scene, err, sizeof(err));      // Material "mix" renders here
     if (st != PT_OK) { std::fprintf(stderr, "pbrt_gpu: %s\n", err); return 1; }
     if (!quiet && pth_scene_warnings(scene)[0]) std::fprintf(stderr, "%s", pth_scene_warnings(scene));
     uint32_t n_inf_lights = 0;

@@ -147,6 +147,7 @@ public:
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
     std::vector<pt_delta_light> delta_lights;
+    bool accept_quadrics = false;                // PTH_FEATURE_QUADRIC_SHAPES: Shape "cylinder" and Shape "disk" are taken (off: refused, as before)
     bool accept_mix = false;                     // PTH_FEATURE_MIX_MATERIAL: Material "mix" is taken (off: refused, as before)
     bool accept_delta_lights = false;            // pth_options.delta_lights: LightSource "spot" / "distant" are taken (off: refused, as before)
     int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
@@ -816,24 +817,39 @@ public:
 
     void pbrt_shape(const std::string& name, const ParamSet& p) override {
         if (!error.empty()) return;
-        if (name != "trianglemesh" && name != "plymesh" && name != "sphere" && name != "loopsubdiv" && name != "nurbs" && name != "heightfield") {
-            fail("Shape \"" + name + "\": only trianglemesh, plymesh, sphere, loopsubdiv, nurbs and heightfield are on the accelerated path");
+        const bool quadric = accept_quadrics && (name == "cylinder" || name == "disk");
+        if (!quadric && name != "trianglemesh" && name != "plymesh" && name != "sphere" && name != "loopsubdiv" && name != "nurbs" && name != "heightfield") {
+            if (accept_quadrics) fail("Shape \"" + name + "\": only trianglemesh, plymesh, sphere, cylinder, disk, loopsubdiv, nurbs and heightfield are on the accelerated path");
+            else fail("Shape \"" + name + "\": only trianglemesh, plymesh, sphere, loopsubdiv, nurbs and heightfield are on the accelerated path");
             return;
         }
         const TransformSet& ts = transforms.back();
         if (std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) != 0) { fail("animated transforms are outside the accelerated path"); return; }
-        if (name == "sphere") {                                     // create_sphere_shape (shapes/sphere.rs:401-420); "alpha" / "shadowalpha" are not read there
+        if (name == "sphere" || quadric) {                          // create_sphere_shape (shapes/sphere.rs:401-420); "alpha" / "shadowalpha" are not read there
             const Xf& o2w = ts.t[0];
-            if (o2w.m.a[12] != 0.0f || o2w.m.a[13] != 0.0f || o2w.m.a[14] != 0.0f || o2w.m.a[15] != 1.0f) { fail("sphere under a projective transform is outside the accelerated path"); return; }
+            if (o2w.m.a[12] != 0.0f || o2w.m.a[13] != 0.0f || o2w.m.a[14] != 0.0f || o2w.m.a[15] != 1.0f) { fail(name + " under a projective transform is outside the accelerated path"); return; }
             pt_sphere sp;
             std::memset(&sp, 0, sizeof(sp));
             std::memcpy(sp.object_to_world, o2w.m.a, 64);
             std::memcpy(sp.world_to_object, o2w.inv.a, 64);       // create_shapes passes object2world.inverse(): the stored m_inv, not a re-inversion
             sp.radius = p.find_one_float("radius", 1.0f);
-            sp.zmin = p.find_one_float("zmin", -sp.radius);
-            sp.zmax = p.find_one_float("zmax", sp.radius);
             sp.phimax = p.find_one_float("phimax", 360.0f);
-            if (!(sp.radius > 0.0f)) { fail("sphere radius must be positive"); return; }
+            if (name == "cylinder") {                               // create_cylinder_shape (shapes/cylinder.rs:329-363)
+                sp.kind = PT_SHAPE_CYLINDER;
+                sp.zmin = p.find_one_float("zmin", -1.0f);
+                sp.zmax = p.find_one_float("zmax", 1.0f);
+                if (sp.zmin > sp.zmax) std::swap(sp.zmin, sp.zmax);
+                if (sp.radius == 0.0f) { warn("Unable to create cylinder shape: radius=0 (the shape is skipped, as the reference does)"); return; }
+            } else if (name == "disk") {                            // create_disk_shape (shapes/disk.rs:194-214)
+                sp.kind = PT_SHAPE_DISK;
+                sp.zmin = p.find_one_float("height", 0.0f);
+                sp.inner_radius = p.find_one_float("innerradius", 0.0f);
+                if (sp.radius > 0.0f && !(sp.inner_radius >= 0.0f && sp.inner_radius < sp.radius)) { fail("disk innerradius must be in [0, radius)"); return; }
+            } else {
+                sp.zmin = p.find_one_float("zmin", -sp.radius);
+                sp.zmax = p.find_one_float("zmax", sp.radius);
+            }
+            if (!(sp.radius > 0.0f)) { fail(name + " radius must be positive"); return; }
             sp.flags = gstates.back().reverse_orientation ? PT_SPHERE_REVERSE_ORIENTATION : 0u;
             sp.material = material_for_shape(p);
             sp.area_light = area_light_for_shape();
@@ -1234,6 +1250,7 @@ pt_status pth_parse_file_features(const char* filename, const pth_options* opts,
     apply_options(s, opts);
     s->ctx.accept_mix = (features & PTH_FEATURE_MIX_MATERIAL) != 0;
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
+    s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_file(filename, s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);
@@ -1244,6 +1261,7 @@ pt_status pth_parse_string_features(const char* text, const char* work_dir, cons
     apply_options(s, opts);
     s->ctx.accept_mix = (features & PTH_FEATURE_MIX_MATERIAL) != 0;
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
+    s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_string(text, work_dir ? work_dir : ".", s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);

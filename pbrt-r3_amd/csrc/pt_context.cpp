@@ -73,6 +73,7 @@ struct pt_context {
     float next_aov_scale = 1.0f;
     int32_t aov_target = PT_AOV_UV;                 // of the uploaded scene (read when its integrator is PT_INTEGRATOR_AOV)
     float aov_scale = 1.0f;
+    bool quadric_kernels = false;                   // the uploaded scene holds a cylinder or a disk: it runs the kernels of namespace ptq (pt_kernels_quadric.hip)
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
@@ -147,6 +148,30 @@ struct pt_context {
         return e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_DEVICE;
     }
 };
+
+// The launchers whose kernels hold analytic-shape code (traversal, surface reconstruction, light sampling), by the scene: a cylinder or a disk asks for the second build of the kernels
+// (namespace ptq, pt_kernels_quadric.hip), every other scene runs the first.
+#define PTK_BY_SCENE(fn)                                                                                            \
+    template <class... A>                                                                                           \
+    static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        return ctx->quadric_kernels ? ptq::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                 \
+    }
+PTK_BY_SCENE(ptk_light_grid)
+PTK_BY_SCENE(ptk_grid_mark)
+PTK_BY_SCENE(ptk_trace)
+PTK_BY_SCENE(ptk_ao_rays)
+PTK_BY_SCENE(ptk_ao_resolve)
+PTK_BY_SCENE(ptk_aov)
+PTK_BY_SCENE(ptk_rec_init)
+PTK_BY_SCENE(ptk_rec_enter)
+PTK_BY_SCENE(ptk_rec_next)
+PTK_BY_SCENE(ptk_nee_resolve)
+PTK_BY_SCENE(ptk_shade)
+PTK_BY_SCENE(ptk_trace_batch)
+PTK_BY_SCENE(ptk_wavefront_results)
+PTK_BY_SCENE(ptk_light_hooks)
+PTK_BY_SCENE(ptk_light_pdf_from)
+#undef PTK_BY_SCENE
 
 #define PT_HIP(call)                                             \
     do {                                                         \
@@ -413,7 +438,7 @@ pt_status setup_halton(pt_context* ctx, PtSobol& sb, int32_t res_x, int32_t res_
     sb.h_mul[1] = (uint32_t)((stride / scale[1]) * (int32_t)mod_inverse(scale[0], scale[1]));
     return PT_OK;
 }
-// Sphere::new + world_bound (sphere.rs:18-59, transform.rs:134-182): device records and BVH build items
+// Sphere::new + world_bound (sphere.rs:18-59, transform.rs:134-182), or the cylinder's / the disk's by `kind`: device records and BVH build items
 static void build_spheres(const pt_scene_desc* d, std::vector<PtSphere>& sph, std::vector<ptbvh::SpherePrim>& sprims) {
     sph.assign(d->n_spheres, PtSphere());
     sprims.assign(d->n_spheres, ptbvh::SpherePrim());
@@ -428,15 +453,33 @@ static void build_spheres(const pt_scene_desc* d, std::vector<PtSphere>& sph, st
         const bool swaps = det < 0.0f, reverse = (in.flags & PT_SPHERE_REVERSE_ORIENTATION) != 0;
         auto clampf = [](float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); };
         s.radius = in.radius;
-        s.z_min = clampf(std::fmin(in.zmin, in.zmax), -in.radius, in.radius);
-        s.z_max = clampf(std::fmax(s.z_min, in.zmax), -in.radius, in.radius);        // as written (sphere.rs:28)
-        s.theta_min = std::acos(clampf(s.z_min / in.radius, -1.0f, 1.0f));
-        s.theta_max = std::acos(clampf(s.z_max / in.radius, -1.0f, 1.0f));
         s.phi_max = clampf(in.phimax, 0.0f, 360.0f) * (3.14159265358979323846f / 180.0f);
-        s.area = s.phi_max * s.radius * (s.z_max - s.z_min);
         s.flags = (reverse ? PT_SPH_REVERSE : 0u) | ((reverse ^ swaps) ? PT_SPH_FLIP : 0u);
-        const float r = s.radius * 1.001f, diff = r - s.radius;
-        const float lo[3] = {-r, -r, s.z_min - diff}, hi[3] = {r, r, s.z_max + diff};
+        s.kind = in.kind;
+        float lo[3], hi[3];                              // Shape::object_bound
+        if (in.kind == PT_SHAPE_CYLINDER) {              // Cylinder::new, object_bound, area (cylinder.rs:20-49, :289-295) after create_cylinder_shape's swap (:340-342)
+            s.z_min = in.zmin > in.zmax ? in.zmax : in.zmin;
+            s.z_max = in.zmin > in.zmax ? in.zmin : in.zmax;
+            s.area = (s.z_max - s.z_min) * s.radius * s.phi_max;
+            lo[0] = -s.radius; lo[1] = -s.radius; lo[2] = s.z_min;
+            hi[0] = s.radius; hi[1] = s.radius; hi[2] = s.z_max;
+        } else if (in.kind == PT_SHAPE_DISK) {           // Disk::new, object_bound (padded by 0.001 along z, as written), area (disk.rs:17-45, :164-169)
+            s.z_min = in.zmin;                           // the height
+            s.z_max = in.zmin;
+            s.inner_radius = in.inner_radius;
+            s.area = s.phi_max * 0.5f * (s.radius * s.radius - s.inner_radius * s.inner_radius);
+            lo[0] = -s.radius; lo[1] = -s.radius; lo[2] = s.z_min - 0.001f;
+            hi[0] = s.radius; hi[1] = s.radius; hi[2] = s.z_min + 0.001f;
+        } else {
+            s.z_min = clampf(std::fmin(in.zmin, in.zmax), -in.radius, in.radius);
+            s.z_max = clampf(std::fmax(s.z_min, in.zmax), -in.radius, in.radius);        // as written (sphere.rs:28)
+            s.theta_min = std::acos(clampf(s.z_min / in.radius, -1.0f, 1.0f));
+            s.theta_max = std::acos(clampf(s.z_max / in.radius, -1.0f, 1.0f));
+            s.area = s.phi_max * s.radius * (s.z_max - s.z_min);
+            const float r = s.radius * 1.001f, diff = r - s.radius;
+            lo[0] = -r; lo[1] = -r; lo[2] = s.z_min - diff;
+            hi[0] = r; hi[1] = r; hi[2] = s.z_max + diff;
+        }
         ptbvh::SpherePrim& sp = sprims[i];
         for (int c = 0; c < 8; c++) {
             const float x = (c & 4) ? hi[0] : lo[0], y = (c & 2) ? hi[1] : lo[1], z = (c & 1) ? hi[2] : lo[2];
@@ -658,16 +701,24 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     }
     for (uint32_t i = 0; i < d->n_spheres; i++) {
         const pt_sphere& sp = d->spheres[i];
-        if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere material index out of range");
-        if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere area light index out of range");
+        if (sp.kind > PT_SHAPE_DISK) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "analytic shape of unknown kind (PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER and PT_SHAPE_DISK are known)");
+        const std::string shape = sp.kind == PT_SHAPE_CYLINDER ? "cylinder" : (sp.kind == PT_SHAPE_DISK ? "disk" : "sphere");
+        if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " material index out of range");
+        if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " area light index out of range");
         if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_MIX))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
-        if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere before_triangle exceeds n_triangles");
-        if (!(sp.radius > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "sphere radius must be positive");
+        if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " before_triangle exceeds n_triangles");
+        if (sp.kind != PT_SHAPE_SPHERE) {
+            const bool finite = std::isfinite(sp.radius) && std::isfinite(sp.zmin) && std::isfinite(sp.phimax) && (sp.kind == PT_SHAPE_DISK ? std::isfinite(sp.inner_radius) : std::isfinite(sp.zmax));
+            if (!finite) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " parameters must be finite");
+        }
+        if (!(sp.radius > 0.0f)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " radius must be positive");
+        if (sp.kind == PT_SHAPE_DISK && !(sp.inner_radius >= 0.0f && sp.inner_radius < sp.radius))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disk inner_radius must be in [0, radius)");
         for (int k = 0; k < 2; k++) {
             const float* m = k ? sp.world_to_object : sp.object_to_world;
             if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f)
-                return ctx->fail(PT_ERR_UNSUPPORTED, "sphere under a projective transform (last matrix row must be 0 0 0 1)");
+                return ctx->fail(PT_ERR_UNSUPPORTED, shape + " under a projective transform (last matrix row must be 0 0 0 1)");
         }
     }
     for (const pt_infinite_light& il : ctx->inf_lights) {
@@ -1522,6 +1573,8 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     sc.textures = (any_textured || any_alpha) && d->n_textures ? ctx->d_textures.as<pt_texture>() : nullptr;
     sc.tex_prog = (any_textured || any_alpha) ? ctx->d_tex_prog.as<uint32_t>() : nullptr;
     ctx->scene_alpha = any_alpha;
+    ctx->quadric_kernels = false;
+    for (uint32_t i = 0; i < d->n_spheres; i++) ctx->quadric_kernels |= d->spheres[i].kind != PT_SHAPE_SPHERE;
     sc.images = images_on_device ? ctx->d_images.as<PtImage>() : nullptr;
     sc.mat_params = any_textured ? ctx->d_mat_params.as<PtMatParams>() : nullptr;
     sc.spheres = d->n_spheres ? ctx->d_spheres.as<PtSphere>() : nullptr;
@@ -1753,7 +1806,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             if (!ctx->grid_lazy) {
                 PT_HIP(ctx->d_grid.alloc(bytes + 64));
                 g.data = ctx->d_grid.as<float>();
-                PT_HIP(ptk_light_grid(ctx->stream, sc, ctx->d_grid.as<float>(), (uint32_t)nvox));
+                PT_HIP(ptk_light_grid_any(ctx, ctx->stream, sc, ctx->d_grid.as<float>(), (uint32_t)nvox));
                 PT_HIP(hipStreamSynchronize(ctx->stream));
             } else {
                 const size_t row_bytes = (size_t)g.stride * sizeof(float);
@@ -1872,7 +1925,7 @@ static pt_status fill_light_grid(pt_context* ctx, const PtQueues& Q) {
     PtScene& sc = ctx->sc;
     uint32_t* todo = ctx->d_grid_todo.as<uint32_t>();
     uint32_t* todo_count = todo + ctx->grid_nvox;
-    PT_HIP(ptk_grid_mark(ctx->stream, ctx->grid_wide, sc, ctx->paths, Q, ctx->d_grid_rows.as<int32_t>(), todo, todo_count));
+    PT_HIP(ptk_grid_mark_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, Q, ctx->d_grid_rows.as<int32_t>(), todo, todo_count));
     uint32_t n = 0;
     PT_HIP(hipMemcpyAsync(&n, todo_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     PT_HIP(hipStreamSynchronize(ctx->stream));
@@ -1893,7 +1946,7 @@ static pt_status fill_light_grid(pt_context* ctx, const PtQueues& Q) {
         sc.grid.data = ctx->d_grid.as<float>();
     }
     float* rows = ctx->d_grid.as<float>() + ctx->grid_rows_used * (size_t)sc.grid.stride;
-    PT_HIP(ptk_light_grid(ctx->stream, sc, rows, n, todo));
+    PT_HIP(ptk_light_grid_any(ctx, ctx->stream, sc, rows, n, todo));
     PT_HIP(ptk_grid_assign(ctx->stream, ctx->d_grid_rows.as<int32_t>(), todo, n, (uint32_t)ctx->grid_rows_used, todo_count));
     ctx->grid_rows_used += n;
     if (std::getenv("PBRTGPU_BUILD_TRACE")) std::fprintf(stderr, "[light grid] %u voxels filled on first touch (%zu of %zu so far, %zu MiB of rows)\n", n, ctx->grid_rows_used, ctx->grid_nvox,
@@ -2088,9 +2141,9 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 PT_HIP(hipMemsetAsync(ctx->d_ticket.p, 0, 16, ctx->stream));
                 PT_HIP(ptk_ao_tag(ctx->stream, ctx->grid_wide, ctx->paths, n_pix, n_paths, s0));
                 PT_HIP(hipEventRecord(a, ctx->stream));
-                PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                 ctx->trace_launches++;
-                PT_HIP(ptk_ao_rays(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_o, ao_d, ao_w, ao_count, cnt));
+                PT_HIP(ptk_ao_rays_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_o, ao_d, ao_w, ao_count, cnt));
                 {   // the occlusion rays as shadow work items of the wavefront traversal kernel itself (any hit -> occlusion flag);
                     // the item count is read on the device, so the pass never waits for the host
                     PtPaths AP = ctx->paths;
@@ -2098,11 +2151,11 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     PtQueues AQ = Q;
                     AQ.shadow = ao_ids;
                     PT_HIP(ptk_ao_queue(ctx->stream, AQ, ao_count, (uint32_t)sc.ao_samples));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, AP, AQ, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                    PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, AP, AQ, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     ctx->trace_launches++;
                 }
                 PT_HIP(hipEventRecord(b, ctx->stream));
-                PT_HIP(ptk_ao_resolve(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_w, ao_occ));
+                PT_HIP(ptk_ao_resolve_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ao_w, ao_occ));
                 PT_HIP(hipEventRecord(c, ctx->stream));
             } else if (aov) {
                 // camera rays -> closest hits -> one field of the interaction per hit
@@ -2112,10 +2165,10 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 spans.push_back({ev_i, 0});
                 ev_i += 3;
                 PT_HIP(hipEventRecord(a, ctx->stream));
-                PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                 ctx->trace_launches++;
                 PT_HIP(hipEventRecord(b, ctx->stream));
-                PT_HIP(ptk_aov(ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ctx->aov_target, ctx->aov_scale, cnt));
+                PT_HIP(ptk_aov_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, n_paths, ctx->aov_target, ctx->aov_scale, cnt));
                 PT_HIP(hipEventRecord(c, ctx->stream));
             } else if (rec) {
                 // DirectLighting / Whitted: depth-first walk over the specular trees, two traversal launches per tree level
@@ -2149,7 +2202,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                 NP.sh_o = R.sh_o; NP.sh_d = R.sh_d; NP.pr_o = R.pr_o; NP.pr_d = R.pr_d; NP.occluded = R.occ; NP.probe_rec = R.prec;
                 PtQueues Qn = Q;
                 Qn.counts = ctx->d_counts2.as<uint32_t>(); Qn.shadow = nl_shadow; Qn.probe = nl_probe;
-                PT_HIP(ptk_rec_init(ctx->stream, ctx->grid_wide, sc, ctx->paths, R, n_paths));
+                PT_HIP(ptk_rec_init_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, R, n_paths));
                 // The walk ends when no camera sample is live.  That count comes back through page-locked memory ONE LEVEL BEHIND: level i + 1 is
                 // queued before the host looks at level i's count, so the device never waits for the host (a level launched after the last one
                 // finds empty lists and does nothing).
@@ -2163,9 +2216,9 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     if (ev_i < 3000) { spans.push_back({ev_i, 0}); ev_i += 3; }
                     Qn.cur = Q.cur;
                     PT_HIP(hipEventRecord(a, ctx->stream));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                    PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     PT_HIP(ptk_prep(ctx->stream, Qn, 0));
-                    PT_HIP(ptk_rec_enter(ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, Qn, R, cnt, rec_epp));
+                    PT_HIP(ptk_rec_enter_any(ctx, ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, Qn, R, cnt, rec_epp));
                     PtQueues Qt = Qn;
                     if (Qn.shadow_key) {
                         // The node's shadow rays start at the hit points of this level -- scattered through a scene of small triangles -- and head for the
@@ -2181,10 +2234,10 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                             Qt.shadow = sorted;
                         }
                     }
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, NP, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
+                    PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, NP, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 0, ctx->scene_alpha ? 1 : 0));
                     ctx->trace_launches += 2;
                     PT_HIP(hipEventRecord(b, ctx->stream));
-                    PT_HIP(ptk_rec_next(ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, R));
+                    PT_HIP(ptk_rec_next_any(ctx, ctx->stream, ctx->grid_shade, sc, ctx->paths, Q, R));
                     PT_HIP(ptk_prep(ctx->stream, Q, 1));
                     PT_HIP(hipEventRecord(c, ctx->stream));
                     std::swap(Q.cur, Q.next);
@@ -2217,7 +2270,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     if (cont_sorted) Qt.cur = cont_sorted;
                     cont_sorted = nullptr;
                     Q_last_trace = Qt;
-                    return ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err,
+                    return ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Qt, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err,
                                      ctx->trace_far_choice > 0 ? 1 : 0, ctx->scene_alpha ? 1 : 0);
                 };
                 auto far_trial = [&](hipEvent_t near_a, hipEvent_t near_b) -> pt_status {      // right after bounce 1's launch by k_trace (timed by near_a .. near_b)
@@ -2228,7 +2281,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     PT_HIP(hipMemcpyAsync(ctx->d_cnt_save.p, cnt, sizeof(PtCounters), hipMemcpyDeviceToDevice, ctx->stream));
                     PT_HIP(hipMemsetAsync(Q.counts + PT_Q_SEG_TICKET0, 0, 8u * 32u * 4u, ctx->stream));          // the launch's work tickets
                     PT_HIP(hipEventRecord(fa, ctx->stream));
-                    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q_last_trace, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 1, 0));
+                    PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, sc, ctx->paths, Q_last_trace, cnt, ctx->d_spill.as<uint32_t>(), ctx->spill_depth, err, 1, 0));
                     PT_HIP(hipEventRecord(fb, ctx->stream));
                     PT_HIP(hipMemcpyAsync(cnt, ctx->d_cnt_save.p, sizeof(PtCounters), hipMemcpyDeviceToDevice, ctx->stream));
                     PT_HIP(hipStreamSynchronize(ctx->stream));
@@ -2291,14 +2344,14 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                         if (ts != PT_OK) return ts;
                     }
                     bounce_i++;
-                    PT_HIP(ptk_nee_resolve(ctx->stream, ctx->grid_wide, sc, ctx->paths, Q));
+                    PT_HIP(ptk_nee_resolve_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, Q));
                     ctx->trace_launches++;
                     PT_HIP(ptk_prep(ctx->stream, Q, 0));
                     if (ctx->grid_lazy) {
                         const pt_status gs = fill_light_grid(ctx, Q);
                         if (gs != PT_OK) return gs;
                     }
-                    PT_HIP(ptk_shade(ctx->stream, ctx->grid_shade, ctx->sc, ctx->paths, Q, cnt, ctx->nee_split, ctx->shade_local < 0 ? ((ctx->scene_has_lobe_materials && !ctx->sc.textured) ? 1 : 0) : ctx->shade_local));
+                    PT_HIP(ptk_shade_any(ctx, ctx->stream, ctx->grid_shade, ctx->sc, ctx->paths, Q, cnt, ctx->nee_split, ctx->shade_local < 0 ? ((ctx->scene_has_lobe_materials && !ctx->sc.textured) ? 1 : 0) : ctx->shade_local));
                     PT_HIP(ptk_prep(ctx->stream, Q, 1));
                     {
                         const pt_status ss = sort_shadow();
@@ -2319,7 +2372,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                     if (counts[PT_Q_CUR] == 0 && counts[PT_Q_NEE] == 0) break;
                     if (counts[PT_Q_CUR] == 0) {     // only NEE resolves left
                         PT_HIP(trace());
-                        PT_HIP(ptk_nee_resolve(ctx->stream, ctx->grid_wide, sc, ctx->paths, Q));
+                        PT_HIP(ptk_nee_resolve_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, Q));
                         ctx->trace_launches++;
                         PT_HIP(ptk_prep(ctx->stream, Q, 0));
                     } else if ((st = bounce()) != PT_OK) return st;
@@ -2364,7 +2417,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go
         unsigned long long sp[16];
-        if (ptk_shade_prof_read(sp)) {
+        if (ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
             double tot = 0;
             for (int k = 0; k < 16; k++) if (k != 12) tot += (double)sp[k];
             static const char* names[16] = {"surface", "emit+bsdf setup", "grid+pick light", "u_light,u_scat", "light sample+f", "bsdf MIS+probe", "pend stores",
@@ -2531,7 +2584,7 @@ static pt_status trace_batch(pt_context* ctx, uint32_t n, const float* o, const 
     PT_HIP(hipMemsetAsync(ctx->d_ticket.p, 0, 16, ctx->stream));
     hipEvent_t a = get_event(ctx, 0), b = get_event(ctx, 1);
     PT_HIP(hipEventRecord(a, ctx->stream));
-    PT_HIP(ptk_trace_batch(ctx->stream, ctx->grid_trace, ctx->sc, n, d_o.as<float>(), d_d.as<float>(), d_t.as<float>(), any_hit ? nullptr : d_out.as<pt_hit>(),
+    PT_HIP(ptk_trace_batch_any(ctx, ctx->stream, ctx->grid_trace, ctx->sc, n, d_o.as<float>(), d_d.as<float>(), d_t.as<float>(), any_hit ? nullptr : d_out.as<pt_hit>(),
                            any_hit ? d_out.as<uint8_t>() : nullptr, any_hit, ctx->d_ticket.as<uint32_t>(), ctx->d_counters.as<PtCounters>(),
                            ctx->d_spill.as<uint32_t>(), ctx->spill_depth, ctx->d_err.as<uint32_t>(), ctx->scene_alpha ? 1 : 0));
     PT_HIP(hipEventRecord(b, ctx->stream));
@@ -2596,10 +2649,10 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
     PT_HIP(hipMemcpyAsync(d_kind.p, kind, n, hipMemcpyHostToDevice, ctx->stream));
     hipEvent_t a = get_event(ctx, 0), b = get_event(ctx, 1);
     PT_HIP(hipEventRecord(a, ctx->stream));
-    PT_HIP(ptk_trace(ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, ctx->sc, P, Q, ctx->d_counters.as<PtCounters>(), ctx->d_spill.as<uint32_t>(), ctx->spill_depth,
+    PT_HIP(ptk_trace_any(ctx, ctx->stream, ctx->grid_trace, ctx->grid_trace_dist, ctx->sc, P, Q, ctx->d_counters.as<PtCounters>(), ctx->d_spill.as<uint32_t>(), ctx->spill_depth,
                      ctx->d_err.as<uint32_t>(), ctx->trace_far > 0 ? 1 : 0, ctx->scene_alpha ? 1 : 0));      // PBRTGPU_TRACE_FAR=1 forces k_trace_far here too (no trial: the caller's rays are not a bounce)
     PT_HIP(hipEventRecord(b, ctx->stream));
-    PT_HIP(ptk_wavefront_results(ctx->stream, ctx->grid_wide, ctx->sc, P, n, d_kind.as<uint8_t>(), d_out.as<pt_hit>(), d_occ.as<uint8_t>()));
+    PT_HIP(ptk_wavefront_results_any(ctx, ctx->stream, ctx->grid_wide, ctx->sc, P, n, d_kind.as<uint8_t>(), d_out.as<pt_hit>(), d_occ.as<uint8_t>()));
     PT_HIP(hipMemsetAsync(Q.counts, 0, PT_COUNTS_WORDS * 4, ctx->stream));
     PT_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0;
@@ -2671,7 +2724,7 @@ static pt_status light_hook(pt_context* ctx, uint32_t light, uint32_t mode, uint
     PT_HIP(d_a.alloc((size_t)n * 12)); PT_HIP(d_b.alloc((size_t)n * 8)); PT_HIP(d_3a.alloc((size_t)n * 12)); PT_HIP(d_3b.alloc((size_t)n * 12)); PT_HIP(d_1.alloc((size_t)n * 4));
     PT_HIP(hipMemcpy(d_a.p, a, (size_t)n * 12, hipMemcpyHostToDevice));
     if (b) PT_HIP(hipMemcpy(d_b.p, b, (size_t)n * 8, hipMemcpyHostToDevice));
-    PT_HIP(ptk_light_hooks(ctx->stream, ctx->sc, light, mode, n, d_a.as<float>(), d_b.as<float>(), d_3a.as<float>(), d_3b.as<float>(), d_1.as<float>()));
+    PT_HIP(ptk_light_hooks_any(ctx, ctx->stream, ctx->sc, light, mode, n, d_a.as<float>(), d_b.as<float>(), d_3a.as<float>(), d_3b.as<float>(), d_1.as<float>()));
     PT_HIP(hipStreamSynchronize(ctx->stream));
     if (o3a) PT_HIP(hipMemcpy(o3a, d_3a.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     if (o3b) PT_HIP(hipMemcpy(o3b, d_3b.p, (size_t)n * 12, hipMemcpyDeviceToHost));
@@ -2685,6 +2738,24 @@ pt_status pt_light_sample_li(pt_context* ctx, uint32_t light, uint32_t n, const 
 pt_status pt_light_pdf_li(pt_context* ctx, uint32_t light, uint32_t n, const float* wi, float* pdf_out) {
     if (!ctx || !wi || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
     return light_hook(ctx, light, 1, n, wi, nullptr, nullptr, nullptr, pdf_out);
+}
+pt_status pt_light_pdf_from(pt_context* ctx, uint32_t light, uint32_t n, const float* ref_p, const float* wi, float* pdf_out) {
+    if (!ctx || !ref_p || !wi || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    if (light >= ctx->sc.n_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "light index out of range");
+    (void)hipSetDevice(ctx->device);
+    PtLight L;
+    PT_HIP(hipMemcpy(&L, ctx->d_lights.as<PtLight>() + light, sizeof(L), hipMemcpyDeviceToHost));
+    if (L.mesh_flags & (PT_LIGHT_INFINITE | PT_LIGHT_DELTA)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "pt_light_pdf_from: not an area light (pt_light_pdf_li answers for the others)");
+    if (n == 0) return PT_OK;
+    DevBuf d_p, d_w, d_o;
+    PT_HIP(d_p.alloc((size_t)n * 12)); PT_HIP(d_w.alloc((size_t)n * 12)); PT_HIP(d_o.alloc((size_t)n * 4));
+    PT_HIP(hipMemcpy(d_p.p, ref_p, (size_t)n * 12, hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(d_w.p, wi, (size_t)n * 12, hipMemcpyHostToDevice));
+    PT_HIP(ptk_light_pdf_from_any(ctx, ctx->stream, ctx->sc, light, n, d_p.as<float>(), d_w.as<float>(), d_o.as<float>()));
+    PT_HIP(hipStreamSynchronize(ctx->stream));
+    PT_HIP(hipMemcpy(pdf_out, d_o.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 pt_status pt_light_le(pt_context* ctx, uint32_t light, uint32_t n, const float* d, float* rgb_out) {
     if (!ctx || !d || !rgb_out) return PT_ERR_INVALID_ARGUMENT;

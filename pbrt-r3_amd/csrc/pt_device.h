@@ -183,7 +183,9 @@ struct PtLight {
     float n2[3]; uint32_t pad1;
 };
 
-// Sphere (shapes/sphere.rs:7-41), affine transforms only.
+// Sphere (shapes/sphere.rs:7-41), affine transforms only.  The slot also holds the other analytic shapes, told apart by `kind`
+// (PT_SHAPE_* of pbrtgpu.h): Cylinder (shapes/cylinder.rs:11-38: z_min / z_max unclamped, theta_* unused) and Disk (shapes/disk.rs:8-35:
+// its height in z_min, z_max and theta_* unused).  `area` is the kind's Shape::area.
 #define PT_SPH_REVERSE 1u        // reverse_orientation: flips sampled normals (sphere.rs:293-295, :380-382)
 #define PT_SPH_FLIP 2u           // reverse_orientation ^ transform_swaps_handedness: flips the intersection normal
 struct PtSphere {                // 144 bytes
@@ -192,7 +194,9 @@ struct PtSphere {                // 144 bytes
     float radius, z_min, z_max, phi_max;
     float theta_min, theta_max, area;
     uint32_t flags;
-    uint32_t pad[4];
+    uint32_t kind;               // PT_SHAPE_SPHERE 0 / PT_SHAPE_CYLINDER 1 / PT_SHAPE_DISK 2
+    float inner_radius;          // disk only
+    uint32_t pad[2];
 };
 // ObjectInstance: TransformedPrimitive over an object's accelerator (affine, static).
 struct PtInstance {              // 144 bytes
@@ -204,7 +208,7 @@ struct PtInstance {              // 144 bytes
     uint32_t world_prim;         // the instance's index in the world primitive list (pt_hit.prim)
     uint32_t pad[3];
 };
-#define PT_LIGHT_SPHERE 0x80000000u   // PtLight::mesh_flags: the light's shape is sphere number bits(p0[0])
+#define PT_LIGHT_SPHERE 0x80000000u   // PtLight::mesh_flags: the light's shape is entry number bits(p0[0]) of PtScene::spheres (any kind)
 #ifdef __HIPCC__
 #define PT_HOSTDEV_ENVS __host__ __device__
 #else

@@ -21,11 +21,23 @@
 #include "pt_device_math.h"
 #include "pt_bxdf.h"
 #include "pt_sphere.h"
+#include "pt_quadric.h"
 #include "pt_texture.h"
 #include <type_traits>
 #include "pt_lobes.h"
 #include "pt_kernels.h"
 #include "../../include/pbrtgpu.h"
+
+// This file is compiled twice.  As it stands it gives the kernels every scene has run so far: an analytic shape is a sphere (pt_sphere.h).
+// pt_kernels_quadric.hip includes it with PT_QUADRIC set: there the four places that touch an analytic shape branch on its kind
+// (pt_quadric.h), every kernel and launcher lives in namespace ptq, and pt_context.cpp runs that set for a scene that holds a cylinder
+// or a disk.  So a scene without them runs code that does not know them: no register, no branch, no spill of theirs.
+#if PT_QUADRIC
+#define PT_KERNEL __global__
+namespace ptq {
+#else
+#define PT_KERNEL extern "C" __global__
+#endif
 
 #ifndef PT_SHADE_PF_DEEP
 #define PT_SHADE_PF_DEEP 0       // 1: k_shade's one-iteration-ahead prefetch also covers the ray, the throughput and the leaf record
@@ -623,7 +635,7 @@ PT_DEV void ray_step_node(const PtScene& sc, LaneRay& r, TravCtx& c) {
 // A leaf record that stands for a sphere (SPH kernels only): Sphere::intersect / intersect_p, t from its EFloat root.
 PT_DEV bool sphere_rec_test(const PtScene& sc, const TriVerts& tv, const LaneRay& r, bool any_hit, float* t) {
     SphHit sh;
-    if (!sph_hit_test(sc.spheres[__float_as_uint(tv.p0.x)], r.o, r.d, r.ray_tmax, any_hit ? 2.0f * PT_PI : PT_PI, &sh)) return false;
+    if (!shape_hit_test(sc.spheres[__float_as_uint(tv.p0.x)], r.o, r.d, r.ray_tmax, any_hit ? 2.0f * PT_PI : PT_PI, &sh)) return false;
     *t = sh.t;
     return true;
 }
@@ -1513,7 +1525,7 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         // reject inside sph_hit_test_inl ends nearly every shadow ray's test before the interval arithmetic starts)
                         SphHit sh;
                         sh.t = 0.0f; sh.a_hi = 0.0f; sh.b_hi = 0.0f;
-                        const bool ok = sph_hit_test_inl(sc.spheres[__float_as_uint(lf_tv.p0.x)], lf_rp.o, lf_rp.d, lf_tmax, (lf_kk & 64) ? 2.0f * PT_PI : PT_PI, &sh);
+                        const bool ok = shape_hit_test_inl(sc.spheres[__float_as_uint(lf_tv.p0.x)], lf_rp.o, lf_rp.d, lf_tmax, (lf_kk & 64) ? 2.0f * PT_PI : PT_PI, &sh);
                         res = make_float4(ok ? 2.0f : 0.0f, sh.a_hi, sh.b_hi, sh.t);
                         cand = ok;              // a sphere's hit is always a candidate: its owner keeps its own comparison
                     }
@@ -1638,17 +1650,17 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&cnt->nodes_lds, v);
     }
 }
-extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                               uint32_t spill_depth, uint32_t* err) {
     trace_body<true, false>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // the same with nodes fetched pairwise (node_step_coop): scenes whose rays miss the caches, chosen per scene by a timed trial (pt_context.cpp)
-extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_far(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_far(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                    uint32_t spill_depth, uint32_t* err) {
     trace_body<true, false, false, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // leaves of more than 8 triangles ("maxnodeprims" > 8): every lane walks its own leaf
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_WAVES) k_trace_seq(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TRACE_WAVES) k_trace_seq(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                   uint32_t spill_depth, uint32_t* err) {
     trace_body<false, false>(sc, P, Q, cnt, spill, spill_depth, err);
 }
@@ -1657,22 +1669,22 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_WAVES) k_trace_s
 #define PT_TRACE_INST_WAVES 3      // 164 registers, 14 spilled; at two (154 / 41 as the compiler chose) 615 / 1 130 / 433 Mrays/s on three instanced scenes, here 628 / 1 184 / 440;
 #endif                            // a triangle-only instantiation for scenes without spheres (162, nothing spilled) is no faster: 637 / 1 165 / 444
 
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                        uint32_t spill_depth, uint32_t* err) {
     trace_body<false, true, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // scenes with alpha masks, whatever else they hold (spheres, instances): k_trace_inst's per-lane traversal with the mask test at every
 // candidate hit of a masked mesh (prim_test<.., true>).  Every ray kind of every integrator runs here for such a scene.
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_alpha(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TRACE_INST_WAVES) k_trace_alpha(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                         uint32_t spill_depth, uint32_t* err) {
     trace_body<false, true, true, false, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
 // scenes with spheres: a leaf record may stand for a sphere
-extern "C" __global__ void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_sph_dist(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_TBLOCK, PT_TRACE_DIST_WAVES) k_trace_sph_dist(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                            uint32_t spill_depth, uint32_t* err) {
     trace_body<true, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, 2) k_trace_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
+PT_KERNEL void __launch_bounds__(PT_BLOCK, 2) k_trace_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt, uint32_t* spill,
                                                                       uint32_t spill_depth, uint32_t* err) {
     trace_body<false, true>(sc, P, Q, cnt, spill, spill_depth, err);
 }
@@ -1725,22 +1737,22 @@ PT_DEV void trace_batch_body(const PtScene& sc, uint32_t n, const float* o, cons
     if (c.overflow) atomicOr(err, 1u);
     flush_counters(cnt, s_cnt, regular, shadow, c.n_nodes, c.n_tris);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
                                                                     pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
                                                                     uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<false>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_sph(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_sph(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
                                                                         pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
                                                                         uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_inst(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_inst(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
                                                                          pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
                                                                          uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax,
                                                                           pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
                                                                           uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<true, true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
@@ -1750,7 +1762,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha(PtSce
 // pt_trace_wavefront loads caller rays into the path pool as the three kinds of work items a bounce mixes in one launch and
 // runs ptk_trace (k_trace / k_trace_seq / k_trace_sph_dist / k_trace_sph / k_trace_inst -- whatever the scene renders with).
 // This kernel turns what the traversal stored (hit_t / hit_rec / hit_inst, occluded, probe_rec) into the hook's outputs.
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_wavefront_results(PtScene sc, PtPaths P, uint32_t n, const uint8_t* kind, pt_hit* out, uint8_t* occ) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_wavefront_results(PtScene sc, PtPaths P, uint32_t n, const uint8_t* kind, pt_hit* out, uint8_t* occ) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t k = kind[i];
         pt_hit h;
@@ -1788,7 +1800,7 @@ hipError_t ptk_wavefront_results(hipStream_t st, int grid, const PtScene& sc, co
 // One block per tile: writes the tile's pixels (row-major, x | y << 16 relative to the sample bounds) at its offset of the
 // pass's pixel list, and marks them in a bitmap over the sample bounds -- a pixel marked twice means overlapping tiles
 // (k_film folds a pixel's samples with a plain read-modify-write, so the tiles of one call must be disjoint).
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_expand_tiles(const int4* tiles, const uint32_t* tile_off, uint32_t n_tiles, int32_t sb_x0, int32_t sb_y0,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_expand_tiles(const int4* tiles, const uint32_t* tile_off, uint32_t n_tiles, int32_t sb_x0, int32_t sb_y0,
                                                                      uint32_t sb_w, uint32_t* pixels, uint32_t* bitmap, uint32_t* err) {
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const int4 tl = tiles[t];
@@ -1810,7 +1822,7 @@ hipError_t ptk_expand_tiles(hipStream_t st, const int4* tiles, const uint32_t* t
 // ============================================================ K_GEN: camera samples
 // path i of the pass: pixel = pixels[i % n_pix], sample = s0 + i / n_pix
 // (render_tile, sampler.rs:221-251: start_pixel / get_camera_sample / generate_ray_differential)
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_gen(PtScene sc, PtPaths P, PtQueues Q, const uint32_t* pixels, uint32_t n_pix,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_gen(PtScene sc, PtPaths P, PtQueues Q, const uint32_t* pixels, uint32_t n_pix,
                                                             uint32_t s0, uint32_t n_samples, PtCounters* cnt) {
     uint32_t n = n_pix * n_samples;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -1846,7 +1858,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_gen(PtScene sc, PtPaths
 }
 
 // queue bookkeeping between stages (single thread)
-extern "C" __global__ void k_prep(PtQueues Q, int mode) {
+PT_KERNEL void k_prep(PtQueues Q, int mode) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (mode == 0) {            // before SHADE: nee and next start empty
             Q.counts[PT_Q_NEXT] = 0; Q.counts[PT_Q_NEE] = 0; Q.counts[PT_Q_TICKET] = 0; Q.counts[PT_Q_TICKET2] = 0; Q.counts[PT_Q_TICKET3] = 0; Q.counts[PT_Q_SHADOW] = 0; Q.counts[PT_Q_PROBE] = 0;
@@ -1989,8 +2001,8 @@ PT_DEV bool make_surf_any_rec(const PtScene& sc, V3 ro, V3 rd, uint32_t rec, flo
         if (flags & PT_TRI_SPHERE) {
             SphHit sh;
             const PtSphere& sp = sc.spheres[__float_as_uint(a.x)];
-            if (!sph_hit_test(sp, ro, rd, PT_INF, PT_PI, &sh)) return false;
-            sph_interaction(sp, sh, &s.p, &s.p_error, &s.n, &s.wo, &s.sh_n, &s.sh_dpdu, &s.dpdv, &s.uv, &s.sh_dndu, &s.sh_dndv);
+            if (!shape_hit_test(sp, ro, rd, PT_INF, PT_PI, &sh)) return false;
+            shape_interaction(sp, sh, &s.p, &s.p_error, &s.n, &s.wo, &s.sh_n, &s.sh_dpdu, &s.dpdv, &s.uv, &s.sh_dndu, &s.sh_dndv);
             s.dpdu = s.sh_dpdu; s.sh_dpdv = s.dpdv;
             s.prim = __float_as_uint(a.w);
             s.material = (int32_t)(flags >> PT_TRI_MATERIAL_SHIFT) - 1;
@@ -2140,7 +2152,7 @@ PT_DEV bool light_sample_any(const PtScene& sc, const PtLight& l, V3 ref_p, V3 r
         if (l.mesh_flags & PT_LIGHT_SPHERE) {
             V3 p, n, pe;
             float pd;
-            if (!sph_sample_from(sc.spheres[__float_as_uint(l.p0[0])], ref_p, ref_pe, ref_n, u, &p, &n, &pe, &pd)) return false;
+            if (!shape_sample_from(sc.spheres[__float_as_uint(l.p0[0])], ref_p, ref_pe, ref_n, u, &p, &n, &pe, &pd)) return false;
             if (pd <= 0.0f || length_squared(p - ref_p) <= 0.0f) return false;      // diffuse.rs:79-81
             *wi = normalize(p - ref_p);
             *li = light_L(l, n, -*wi);
@@ -2335,7 +2347,7 @@ PT_DEV uint32_t sample_discrete(const float* tab, uint32_t n, float u, float* pd
 // After TRACE: L += beta * ((A + B) / pdf_light) for every path with a pending next-event estimate, where the
 // light-sample term A counts if its shadow ray was unoccluded and the BSDF-sample term B if its probe ray's
 // closest hit is the sampled light's own triangle (sample_lights.rs:372-385, :419-447; path.rs:122-136).
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_nee_resolve(PtScene sc, PtPaths P, PtQueues Q) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_nee_resolve(PtScene sc, PtPaths P, PtQueues Q) {
     const uint32_t n = Q.counts[PT_Q_NEE];
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = Q.nee[i];
@@ -2356,7 +2368,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_nee_resolve(PtScene sc,
     }
 }
 // Scenes with an infinite light: for that light B counts when the probe ray escaped (sample_lights.rs:444-446).
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_nee_resolve_env(PtScene sc, PtPaths P, PtQueues Q) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_nee_resolve_env(PtScene sc, PtPaths P, PtQueues Q) {
     const uint32_t n = Q.counts[PT_Q_NEE];
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = Q.nee[i];
@@ -2416,7 +2428,7 @@ PT_DEV void sort_chunk(uint32_t n, uint32_t* lo, uint32_t* hi) {
     *lo = min(n, blockIdx.x * chunk);
     *hi = min(n, *lo + chunk);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_sort_count(PtScene sc, PtPaths P, PtQueues Q) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_sort_count(PtScene sc, PtPaths P, PtQueues Q) {
     __shared__ uint32_t s_cnt[PT_SORT_BINS];
     s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -2433,7 +2445,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_sort_count(PtScene sc, 
     uint32_t c = s_cnt[threadIdx.x];
     if (c) atomicAdd(&Q.counts[PT_SORT_COUNT0 + threadIdx.x], c);
 }
-extern "C" __global__ void k_sort_scan(PtQueues Q) {          // one block of PT_SORT_BINS threads
+PT_KERNEL void k_sort_scan(PtQueues Q) {          // one block of PT_SORT_BINS threads
     __shared__ uint32_t s[PT_SORT_BINS];
     const uint32_t t = threadIdx.x;
     uint32_t c = Q.counts[PT_SORT_COUNT0 + t];
@@ -2452,7 +2464,7 @@ extern "C" __global__ void k_sort_scan(PtQueues Q) {          // one block of PT
     if (t == PT_SORT_TEX0) Q.counts[PT_Q_TEX_BEGIN] = excl;
     if (t == PT_SORT_BINS - 1) Q.counts[PT_Q_GENERAL_END] = s[t];
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_sort_scatter(PtScene sc, PtPaths P, PtQueues Q) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_sort_scatter(PtScene sc, PtPaths P, PtQueues Q) {
     __shared__ uint32_t s_cnt[PT_SORT_BINS];      // phase A: this block's count per bin; phase C: running cursor
     s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -2494,7 +2506,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_sort_scatter(PtScene sc
 #ifndef PT_LOCAL_CHUNK
 #define PT_LOCAL_CHUNK 4096u
 #endif
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_sort_local(PtScene sc, PtPaths P, PtQueues Q) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_sort_local(PtScene sc, PtPaths P, PtQueues Q) {
     __shared__ uint32_t s_cnt[PT_SORT_BINS + 1];          // per bin (the last one: misses): count, then the bin's cursor inside the run
     __shared__ uint32_t s_p[PT_LOCAL_CHUNK];
     __shared__ uint16_t s_b[PT_LOCAL_CHUNK];
@@ -3242,34 +3254,34 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     __syncthreads();
     if (threadIdx.x == 0 && s_vert) atomicAdd(&cnt->vertices, s_vert);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_WAVES) k_shade(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_WAVES) k_shade(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<false, false>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // the two halves of a material-sorted queue
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_WAVES) k_shade_matte_sorted(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_WAVES) k_shade_matte_sorted(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<false, false>(sc, P, Q, cnt, Q.sorted, 0u, Q.counts[PT_Q_MATTE_END], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_general(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_general(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_TEX_BEGIN], &Q.counts[PT_Q_TICKET2]);
 }
 // scenes with spheres: hits and lights may be spheres
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_matte_sorted_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_matte_sorted_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<false, true>(sc, P, Q, cnt, Q.sorted, 0u, Q.counts[PT_Q_MATTE_END], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_TEX_BEGIN], &Q.counts[PT_Q_TICKET2]);
 }
 // scenes with object instances: hits inside an instance are rebuilt in instance space and transformed back; every material
 // rides in the general half of the sorted queue, so this one kernel shades them all
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET2]);
 }
 // ... without textures and without spheres: the lobe-list kernel with the instance-space reconstruction, nothing else
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_inst_plain(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_inst_plain(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET2]);
 }
 // scenes with textured materials (and possibly spheres): lobes are built per hit for the textured ones
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_general_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_general_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
 }
 
@@ -3339,16 +3351,16 @@ PT_DEV void tex_resolve_body(const PtScene& sc, const PtPaths& P, const PtQueues
 #ifndef PT_TEX_RESOLVE_WAVES
 #define PT_TEX_RESOLVE_WAVES 2
 #endif
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false>(sc, P, Q); }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_sph(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<true>(sc, P, Q); }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_all(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false, true>(sc, P, Q); }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false>(sc, P, Q); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_sph(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<true>(sc, P, Q); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_all(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false, true>(sc, P, Q); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false, false, false, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_general_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_general_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_res_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_res_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
 }
 
@@ -3374,10 +3386,10 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_s
 #define PT_NEE_SPLIT_DEFAULT 0
 #endif
 #define PT_SPLIT_KERNELS(NAME, WN, WC, LIST, BEGIN, END, TN, TC, ...)                                                                              \
-    extern "C" __global__ void __launch_bounds__(PT_BLOCK, WN) NAME##_nee(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                     \
+    PT_KERNEL void __launch_bounds__(PT_BLOCK, WN) NAME##_nee(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                     \
         shade_body<__VA_ARGS__, 1>(sc, P, Q, cnt, LIST, BEGIN, END, &Q.counts[TN]);                                                                \
     }                                                                                                                                              \
-    extern "C" __global__ void __launch_bounds__(PT_BLOCK, WC) NAME##_cont(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                    \
+    PT_KERNEL void __launch_bounds__(PT_BLOCK, WC) NAME##_cont(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                    \
         shade_body<__VA_ARGS__, 2>(sc, P, Q, cnt, LIST, BEGIN, END, &Q.counts[TC]);                                                                \
     }
 PT_SPLIT_KERNELS(k_shade, PT_NEE_WAVES, PT_CONT_WAVES, Q.cur, 0u, Q.counts[PT_Q_CUR], PT_Q_TICKET_N1, PT_Q_TICKET, false, false, false, false, false)
@@ -3391,7 +3403,7 @@ PT_SPLIT_KERNELS(k_shade_general_res_sph, PT_NEE_GEN_WAVES, PT_CONT_SPH_WAVES, Q
 // Sort keys of a bounce's continuation rays, for scenes larger than the Infinity Cache (pt_context.cpp sort_cont): a pass of its own over the
 // list k_shade has just written -- inside the shading kernels the key arithmetic cost the general kernel registers it does not have
 // (mixed materials 857 -> 832 Mrays/s with the sort off), here it is 32 bytes read per ray where traversal is 96 % of the frame
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_cont_keys(PtScene sc, PtPaths P, const uint32_t* list, uint32_t n, uint32_t* keys) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_cont_keys(PtScene sc, PtPaths P, const uint32_t* list, uint32_t n, uint32_t* keys) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = list[i];
         const float4 o = P.ray_o[p], d = P.ray_d[p];
@@ -3401,37 +3413,37 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_cont_keys(PtScene sc, P
 
 // Every material through the lobe-list path in PATH order, no material sort (experiment switch PBRTGPU_SHADE_UNSORTED=1: sorted queues make
 // a wave see one material but walk the path pool with gaps; this form keeps the pool accesses dense and lets the lobe dispatch diverge)
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_all_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_all_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_all_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_all_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // Scenes with an infinite light (LightSource "infinite"): one kernel over the unsorted shade queue, misses included -- a path whose ray left the
 // scene is shaded here before its slot is recycled (its Le at bounce 0 / after a specular bounce).  The lobe-list form with spheres and per-hit
 // textures covers every material; _inst adds the instance-space reconstruction (scenes with ObjectInstance).
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_env(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_env(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, false, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_env_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_env_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // Scenes with a delta light (with or without infinite lights): the same two kernels with the delta branch of next-event estimation
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_delta(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_delta(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, false, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_delta_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_delta_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // Scenes that hold a Material "mix": the same two kernels once more, with the scaled lobe list as their BSDF (MBsdf) -- spheres, per-hit textures,
 // environment and delta lights compiled in, so a mix works beside every light and shape the path has.  Scenes without a mix never launch them.
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_mix(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_mix(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, false, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_mix_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_mix_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, true, true, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 
@@ -3490,7 +3502,7 @@ PT_DEV void film_add(const PtFilm& fm, float4* spill, int32_t px, int32_t py, V2
         }
 }
 // One thread per pixel of the pass; samples are folded in sample order.
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_film(PtScene sc, PtPaths P, const uint32_t* pixels, uint32_t n_pix, uint32_t n_samples,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_film(PtScene sc, PtPaths P, const uint32_t* pixels, uint32_t n_pix, uint32_t n_samples,
                                                              float4* own, float4* spill, float* radiance_out, uint32_t s0, uint32_t spp_total) {
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n_pix; j += gridDim.x * blockDim.x) {
         uint32_t pk = pixels[j];
@@ -3513,7 +3525,7 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_film(PtScene sc, PtPath
     }
 }
 // Film::merge_film_tile's RGB -> XYZ per contribution buffer (film.rs:219-241)
-extern "C" __global__ void k_film_xyzw(const float4* own, const float4* spill, float4* xyzw, uint32_t n) {
+PT_KERNEL void k_film_xyzw(const float4* own, const float4* spill, float4* xyzw, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float4 a = own[i], b = spill[i];
         V3 xa = rgb_to_xyz(mk3(a.x, a.y, a.z)), xb = rgb_to_xyz(mk3(b.x, b.y, b.z));
@@ -3521,14 +3533,14 @@ extern "C" __global__ void k_film_xyzw(const float4* own, const float4* spill, f
     }
 }
 // Film::merge_film_tile across hosts without a collective (film.rs:219-241): another rank's {X,Y,Z,weight} film, staged through the host, is added
-extern "C" __global__ void k_film_add(float4* xyzw, const float4* other, uint32_t n) {
+PT_KERNEL void k_film_add(float4* xyzw, const float4* other, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float4 a = xyzw[i], b = other[i];
         xyzw[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
     }
 }
 // Film::write_image (film.rs:440-484)
-extern "C" __global__ void k_film_rgb(const float4* xyzw, float* rgb, uint32_t n, float scale) {
+PT_KERNEL void k_film_rgb(const float4* xyzw, float* rgb, uint32_t n, float scale) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float4 v = xyzw[i];
         V3 c = xyz_to_rgb(mk3(v.x, v.y, v.z));
@@ -3647,9 +3659,9 @@ PT_DEV void light_grid_cdf(const PtScene& sc, float* data, uint32_t n_vox) {
         cdf[nl + 1] = func_int;
     }
 }
-extern "C" __global__ __launch_bounds__(128) void k_light_grid(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<false>(sc, data, n_vox, vox_list); }
-extern "C" __global__ __launch_bounds__(128) void k_light_grid_sph(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true>(sc, data, n_vox, vox_list); }
-extern "C" __global__ __launch_bounds__(128) void k_light_grid_env(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true, true>(sc, data, n_vox, vox_list); }
+PT_KERNEL __launch_bounds__(128) void k_light_grid(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<false>(sc, data, n_vox, vox_list); }
+PT_KERNEL __launch_bounds__(128) void k_light_grid_sph(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true>(sc, data, n_vox, vox_list); }
+PT_KERNEL __launch_bounds__(128) void k_light_grid_env(PtScene sc, float* data, uint32_t n_vox, const uint32_t* vox_list) { light_grid_sums<true, true>(sc, data, n_vox, vox_list); }
 // ---- the lazily filled grid (PtLightGrid::row_of; SpatialLightDistribution::lookup, spatial.rs:199-260, fills a voxel on its first touch).
 // Before a bounce is shaded, k_grid_mark rebuilds every hit of the bounce's queue exactly as the shading kernels will (same interaction point,
 // same voxel arithmetic) and lists the voxels nobody has asked for yet; the host gives them rows, k_light_grid fills those, k_grid_assign
@@ -3686,24 +3698,24 @@ PT_DEV void grid_mark_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
         if (row_of[vox] == -1 && atomicCAS(&row_of[vox], -1, -2) == -1) todo[atomicAdd(todo_count, 1u)] = vox;      // -2: listed, row pending
     }
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_grid_mark(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_grid_mark(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
     grid_mark_body<false, false>(sc, P, Q, row_of, todo, todo_count);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_grid_mark_sph(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_grid_mark_sph(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
     grid_mark_body<true, false>(sc, P, Q, row_of, todo, todo_count);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_grid_mark_inst(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_grid_mark_inst(PtScene sc, PtPaths P, PtQueues Q, int32_t* row_of, uint32_t* todo, uint32_t* todo_count) {
     grid_mark_body<true, true>(sc, P, Q, row_of, todo, todo_count);
 }
-extern "C" __global__ void k_grid_assign(int32_t* row_of, const uint32_t* todo, uint32_t n, uint32_t row0, uint32_t* todo_count) {
+PT_KERNEL void k_grid_assign(int32_t* row_of, const uint32_t* todo, uint32_t n, uint32_t row0, uint32_t* todo_count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) row_of[todo[i]] = (int32_t)(row0 + i);
     if (i == 0) *todo_count = 0;
 }
-extern "C" __global__ void k_light_grid_cdf(PtScene sc, float* data, uint32_t n_vox) { light_grid_cdf(sc, data, n_vox); }
+PT_KERNEL void k_light_grid_cdf(PtScene sc, float* data, uint32_t n_vox) { light_grid_cdf(sc, data, n_vox); }
 
 // ============================================================ hooks: sampler / camera
-extern "C" __global__ void k_camera_rays(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
+PT_KERNEL void k_camera_rays(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
                                          float* out_pf) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         int32_t px = pixel_xy[2 * i], py = pixel_xy[2 * i + 1];
@@ -3720,7 +3732,7 @@ extern "C" __global__ void k_camera_rays(PtScene sc, uint32_t n, const int32_t* 
         out_pf[2 * i] = pf.x; out_pf[2 * i + 1] = pf.y;
     }
 }
-extern "C" __global__ void k_sobol_samples(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, const uint32_t* dim, float* out) {
+PT_KERNEL void k_sobol_samples(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, const uint32_t* dim, float* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         int32_t px = pixel_xy[2 * i], py = pixel_xy[2 * i + 1];
         uint64_t idx = sampler_index(sc, sample_index[i], px, py);
@@ -3740,7 +3752,7 @@ PT_DEV GBsdf canonical_bsdf(const PtScene& sc, uint32_t material) {
 }
 // Light hooks (pt_light_sample_li / pt_light_pdf_li / pt_light_le): mode 0 sample_li (a: ref points, b: u; o3a: Li, o3b: wi, o1: pdf),
 // 1 pdf_li of an infinite light (a: wi; o1), 2 its le (a: d; o3a)
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_hooks(PtScene sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_light_hooks(PtScene sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b,
                                                                     float* o3a, float* o3b, float* o1) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3762,7 +3774,24 @@ extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_hooks(PtScene sc,
     const V3 le = env_le(sc, e, va);
     o3a[3 * i] = le.x; o3a[3 * i + 1] = le.y; o3a[3 * i + 2] = le.z;
 }
-extern "C" __global__ void k_bsdf_eval(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
+// pt_light_pdf_from: DiffuseAreaLight::pdf_li = the default Shape::pdf_from (shape.rs:40-54) of an area light for directions wi from reference
+// points ref (bare points: no error, no normal, so spawn_ray starts at the point itself) -- the route the BSDF-sampling half of MIS takes:
+// the light's own shape is intersected again (make_surf_any) and the area density converted, infinite -> 0
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_light_pdf_from(PtScene sc, uint32_t light, uint32_t n, const float* ref, const float* wi, float* pdf) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PtLight& lt = sc.lights[light];
+    const V3 p = ld3(ref + 3 * i), w = ld3(wi + 3 * i);
+    Surf ls;
+    float t;
+    float pd = 0.0f;
+    if (make_surf_any<true>(sc, p, w, lt.tri_rec, ls, &t)) {
+        pd = distance_squared(p, ls.p) / (abs_dot(ls.n, -w) * lt.area);
+        if (isinf(pd)) pd = 0.0f;
+    }
+    pdf[i] = pd;
+}
+PT_KERNEL void k_bsdf_eval(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         GBsdf gb = canonical_bsdf(sc, material);
         V3 o = ld3(wo + 3 * i), w = ld3(wi + 3 * i);
@@ -3771,7 +3800,7 @@ extern "C" __global__ void k_bsdf_eval(PtScene sc, uint32_t material, uint32_t n
         pdf[i] = gbsdf_pdf(gb, o, w, flags);
     }
 }
-extern "C" __global__ void k_bsdf_sample(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f, float* wi,
+PT_KERNEL void k_bsdf_sample(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f, float* wi,
                                          float* pdf, uint32_t* type) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         GBsdf gb = canonical_bsdf(sc, material);
@@ -3798,7 +3827,7 @@ PT_DEV MBsdf canonical_mbsdf(const PtScene& sc, uint32_t material) {
     if (mix1 && mix1 <= scene_n_mix(sc)) { const PtMix& mx = material_mix(sc, sc.materials[material]); mb.lobes = mx.lobes; mb.n_lobes = mx.n_lobes; mb.scales = &mx.scales; }
     return mb;
 }
-extern "C" __global__ void k_bsdf_eval_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
+PT_KERNEL void k_bsdf_eval_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f, float* pdf) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         MBsdf mb = canonical_mbsdf(sc, material);
         V3 o = ld3(wo + 3 * i), w = ld3(wi + 3 * i);
@@ -3807,7 +3836,7 @@ extern "C" __global__ void k_bsdf_eval_mix(PtScene sc, uint32_t material, uint32
         pdf[i] = mbsdf_pdf(mb, o, w, flags);
     }
 }
-extern "C" __global__ void k_bsdf_sample_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f, float* wi,
+PT_KERNEL void k_bsdf_sample_mix(PtScene sc, uint32_t material, uint32_t n, const float* wo, const float* u, uint32_t flags, float* f, float* wi,
                                              float* pdf, uint32_t* type) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         MBsdf mb = canonical_mbsdf(sc, material);
@@ -3974,7 +4003,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
     return nee;
 }
 // camera rays carry differentials: the offset rays of every camera sample (k_gen made the main ray), the sampler past its arrays
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_rec_init(PtScene sc, PtPaths P, PtRec R, uint32_t n) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_rec_init(PtScene sc, PtPaths P, PtRec R, uint32_t n) {
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
         Sampler sl;
         sl.index = P.sobol_index[p];
@@ -4178,14 +4207,14 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
     __syncthreads();
     if (threadIdx.x == 0 && s_vert) atomicAdd(&cnt->vertices, s_vert);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
     rec_enter_body<true>(sc, P, Q, Qn, R, cnt);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_plain(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_plain(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
     rec_enter_body<false>(sc, P, Q, Qn, R, cnt);
 }
 // scenes with an infinite light
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_env(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_env(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
     rec_enter_body<true, true>(sc, P, Q, Qn, R, cnt);
 }
 // specular_reflect / specular_transmit at the frame `depth` (sampler.rs:37-143): true = a child ray was set up (cur ray, differentials, pending f / scale)
@@ -4411,14 +4440,14 @@ PT_DEV void rec_next_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q
     }
     flush();
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true>(sc, P, Q, R); }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_plain(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<false>(sc, P, Q, R); }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_env(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true>(sc, P, Q, R); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true>(sc, P, Q, R); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_plain(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<false>(sc, P, Q, R); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_env(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true>(sc, P, Q, R); }
 // Scenes that hold a Material "mix": everything compiled in as in the _env pair, with the scaled lobe list as the node's BSDF
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_mix(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_enter_mix(PtScene sc, PtPaths P, PtQueues Q, PtQueues Qn, PtRec R, PtCounters* cnt) {
     rec_enter_body<true, true, true>(sc, P, Q, Qn, R, cnt);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_mix(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true, true>(sc, P, Q, R); }
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_rec_next_mix(PtScene sc, PtPaths P, PtQueues Q, PtRec R) { rec_next_body<true, true, true>(sc, P, Q, R); }
 hipError_t ptk_rec_init(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtRec& R, uint32_t n) {
     hipLaunchKernelGGL(k_rec_init, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, R, n);
     return hipGetLastError();
@@ -4538,14 +4567,14 @@ PT_DEV void aov_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, int3
         if (lane == 0 && hits) atomicAdd(&cnt->vertices, (unsigned long long)__popcll(hits));
     }
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
     aov_body<true>(sc, P, n_paths, target, scale, cnt);
 }
 // scenes without spheres, instances and textured materials (no bump map either: it makes a material textured)
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_aov_plain(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_aov_plain(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
     aov_body<false>(sc, P, n_paths, target, scale, cnt);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov_mix(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_aov_mix(PtScene sc, PtPaths P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
     aov_body<true, true>(sc, P, n_paths, target, scale, cnt);
 }
 hipError_t ptk_aov(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, uint32_t n_paths, int32_t target, float scale, PtCounters* cnt) {
@@ -4595,7 +4624,7 @@ hipError_t ptk_nee_resolve(hipStream_t st, int grid, const PtScene& sc, const Pt
 }
 // Scenes with an infinite light: an area light's index moves up by the infinite lights put before it in the light list; the hit records
 // (light1, tri_info.light) were numbered without them
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_light_renumber(PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_light_renumber(PtTri* tris, PtTriInfo* tinfo, const PtLight* lights, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || (lights[i].mesh_flags & (PT_LIGHT_INFINITE | PT_LIGHT_DELTA))) return;
     const uint32_t r = lights[i].tri_rec;
@@ -4610,6 +4639,10 @@ hipError_t ptk_light_renumber(hipStream_t st, PtTri* tris, PtTriInfo* tinfo, con
 hipError_t ptk_light_hooks(hipStream_t st, const PtScene& sc, uint32_t light, uint32_t mode, uint32_t n, const float* a, const float* b, float* o3a, float* o3b,
                            float* o1) {
     hipLaunchKernelGGL(k_light_hooks, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, light, mode, n, a, b, o3a, o3b, o1);
+    return PT_LAUNCH_CHECK();
+}
+hipError_t ptk_light_pdf_from(hipStream_t st, const PtScene& sc, uint32_t light, uint32_t n, const float* ref, const float* wi, float* pdf) {
+    hipLaunchKernelGGL(k_light_pdf_from, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, light, n, ref, wi, pdf);
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_trace_batch(hipStream_t st, int grid, const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out,
@@ -4681,23 +4714,23 @@ PT_DEV void ao_rays_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, 
         }
     }
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_ao_rays(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_ao_rays(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
                                                                 uint32_t* counter, PtCounters* cnt) {
     ao_rays_body<false, false>(sc, P, n_paths, ao_o, ao_d, ao_w, counter, cnt);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_ao_rays_sph(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_ao_rays_sph(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
                                                                     uint32_t* counter, PtCounters* cnt) {
     ao_rays_body<true, false>(sc, P, n_paths, ao_o, ao_d, ao_w, counter, cnt);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_ao_rays_inst(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_ao_rays_inst(PtScene sc, PtPaths P, uint32_t n_paths, float4* ao_o, float4* ao_d, float* ao_w,
                                                                      uint32_t* counter, PtCounters* cnt) {
     ao_rays_body<true, true>(sc, P, n_paths, ao_o, ao_d, ao_w, counter, cnt);
 }
 // path i of the pass took pixel-sample number s0 + i / n_pix (k_gen); the array slice of get_2d_array starts at n_s times that
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_ao_tag(PtPaths P, uint32_t n_pix, uint32_t n_paths, uint32_t s0) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_ao_tag(PtPaths P, uint32_t n_pix, uint32_t n_paths, uint32_t s0) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_paths; i += gridDim.x * blockDim.x) P.probe_rec[i] = (int32_t)(s0 + i / n_pix);
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_ao_resolve(PtScene sc, PtPaths P, uint32_t n_paths, const float* ao_w, const uint8_t* occ) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_ao_resolve(PtScene sc, PtPaths P, uint32_t n_paths, const float* ao_w, const uint8_t* occ) {
     const uint32_t n_s = (uint32_t)sc.ao_samples;
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n_paths; p += gridDim.x * blockDim.x) {
         float l = 0.0f;
@@ -4724,13 +4757,13 @@ hipError_t ptk_ao_rays(hipStream_t st, int grid, const PtScene& sc, const PtPath
 }
 // The occlusion rays become the shadow work items of one wavefront traversal launch: item i is ray i (identity list), the count
 // comes from the device-side hit counter -- no host round trip between the two traversals of a pass.
-extern "C" __global__ void k_ao_queue(PtQueues Q, const uint32_t* counter, uint32_t n_s) {
+PT_KERNEL void k_ao_queue(PtQueues Q, const uint32_t* counter, uint32_t n_s) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         Q.counts[PT_Q_CUR] = 0; Q.counts[PT_Q_SHADOW] = counter[0] * n_s; Q.counts[PT_Q_PROBE] = 0; Q.counts[PT_Q_NEE] = 0;
         for (uint32_t k = 0; k < 8u; k++) Q.counts[PT_Q_SEG_TICKET0 + 32u * k] = 0;
     }
 }
-extern "C" __global__ void __launch_bounds__(PT_BLOCK) k_iota(uint32_t* out, uint32_t n) {
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_iota(uint32_t* out, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = i;
 }
 hipError_t ptk_ao_queue(hipStream_t st, const PtQueues& Q, const uint32_t* counter, uint32_t n_s) {
@@ -4905,3 +4938,6 @@ hipError_t ptk_sobol_samples(hipStream_t st, const PtScene& sc, uint32_t n, cons
     hipLaunchKernelGGL(k_sobol_samples, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, n, pixel_xy, sample_index, dim, out);
     return PT_LAUNCH_CHECK();
 }
+#if PT_QUADRIC
+}  // namespace ptq
+#endif

@@ -787,6 +787,9 @@ class SceneBuilder:
         sp.zmin = -radius if zmin is None else zmin
         sp.zmax = radius if zmax is None else zmax
         sp.phimax = phimax
+        return self._append_analytic(sp)
+
+    def _append_analytic(self, sp):
         sp.flags = capi.PT_SPHERE_REVERSE_ORIENTATION if self.reverse_orientation else 0
         sp.material, sp.area_light = self.cur_material, self.cur_area_light
         sp.before_triangle = sum(len(i) for i in self.idx)
@@ -794,6 +797,37 @@ class SceneBuilder:
         self.n_extra += 1
         self.spheres.append(sp)
         return len(self.spheres) - 1
+
+    def _analytic(self, kind, object_to_world, world_to_object):
+        sp = capi.pt_sphere()
+        m = np.eye(4, dtype=np.float32).reshape(-1) if object_to_world is None else np.asarray(object_to_world, np.float32).reshape(-1)
+        if world_to_object is None:
+            assert object_to_world is None, "pass the inverse too: the reference never re-inverts a CTM"
+            mi = m.copy()
+        else:
+            mi = np.asarray(world_to_object, np.float32).reshape(-1)
+        sp.object_to_world[:] = [float(v) for v in m]
+        sp.world_to_object[:] = [float(v) for v in mi]
+        sp.kind = kind
+        return sp
+
+    def shape_cylinder(self, radius=1.0, zmin=-1.0, zmax=1.0, phimax=360.0, object_to_world=None, world_to_object=None):
+        """Shape "cylinder" (shapes/cylinder.rs:329-363) under the given CTM, in the sphere's slot of the scene (pt_sphere.kind): it takes the
+        current material, area light and orientation and its place in the primitive order as a sphere does.  zmin > zmax swaps; the two
+        are not clamped to the radius."""
+        sp = self._analytic(capi.PT_SHAPE_CYLINDER, object_to_world, world_to_object)
+        sp.radius, sp.phimax = radius, phimax
+        sp.zmin, sp.zmax = (zmax, zmin) if zmin > zmax else (zmin, zmax)
+        return self._append_analytic(sp)
+
+    def shape_disk(self, height=0.0, radius=1.0, innerradius=0.0, phimax=360.0, object_to_world=None, world_to_object=None):
+        """Shape "disk" (shapes/disk.rs:194-214): an annulus sector in the plane z = height of its object space.  The height rides in
+        pt_sphere.zmin."""
+        sp = self._analytic(capi.PT_SHAPE_DISK, object_to_world, world_to_object)
+        sp.radius, sp.phimax = radius, phimax
+        sp.zmin, sp.zmax = height, height
+        sp.inner_radius = innerradius
+        return self._append_analytic(sp)
 
     # ---- object instancing (scene_context.rs:1327-1391)
     def object_begin(self, name):
