@@ -368,7 +368,7 @@ struct PtPaths {
     float4* pr_d;
     float4* beta;        // xyz, w = eta_scale
     float4* L;           // xyz radiance, w unused
-    float4* pendA;       // light-sample term f*Li*(w/pdf), w = selection pdf
+    float4* pendA;       // light-sample term f*Li*(w/pdf), w = selection pdf; w = +0: the folded estimate beta*((0+A)/pdf), pendB / pbeta / nee not written (shade_body)
     float4* pendB;       // BSDF-sample term,              w = beta snapshot index unused
     float4* pbeta;       // beta at NEE time
     float2* p_film;

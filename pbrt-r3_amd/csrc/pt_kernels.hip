@@ -2347,12 +2347,22 @@ PT_DEV uint32_t sample_discrete(const float* tab, uint32_t n, float u, float* pd
 // After TRACE: L += beta * ((A + B) / pdf_light) for every path with a pending next-event estimate, where the
 // light-sample term A counts if its shadow ray was unoccluded and the BSDF-sample term B if its probe ray's
 // closest hit is the sampled light's own triangle (sample_lights.rs:372-385, :419-447; path.rs:122-136).
+// A vertex without a probe ray has everything but the shadow ray's answer when it is shaded: shade_body stores beta * ((0 + A) / pdf_light) in
+// pendA with .w = +0 as the mark (a selection pdf is > 0) and writes no pendB, pbeta or nee; such an entry costs 53 bytes here instead of 73.
 PT_KERNEL void __launch_bounds__(PT_BLOCK) k_nee_resolve(PtScene sc, PtPaths P, PtQueues Q) {
     const uint32_t n = Q.counts[PT_Q_NEE];
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = Q.nee[i];
-        const uint32_t nee = P.nee[p];
         const float4 A = P.pendA[p];
+        if (__float_as_uint(A.w) == 0u) {           // folded in shade_body: A.xyz is the whole term, the shadow ray's answer is all that was missing
+            if (P.occluded[p] == 0) {
+                float4 L = P.L[p];
+                L.x += A.x; L.y += A.y; L.z += A.z;
+                P.L[p] = L;
+            }
+            continue;
+        }
+        const uint32_t nee = P.nee[p];
         V3 ld = mk3(0.0f, 0.0f, 0.0f);
         if ((nee & PT_NEE_SHADOW) && P.occluded[p] == 0) ld = ld + mk3(A.x, A.y, A.z);
         if (nee & PT_NEE_PROBE) {
@@ -2372,8 +2382,16 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_nee_resolve_env(PtScene sc, PtPaths
     const uint32_t n = Q.counts[PT_Q_NEE];
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = Q.nee[i];
-        const uint32_t nee = P.nee[p];
         const float4 A = P.pendA[p];
+        if (__float_as_uint(A.w) == 0u) {           // folded in shade_body: A.xyz is the whole term, the shadow ray's answer is all that was missing
+            if (P.occluded[p] == 0) {
+                float4 L = P.L[p];
+                L.x += A.x; L.y += A.y; L.z += A.z;
+                P.L[p] = L;
+            }
+            continue;
+        }
+        const uint32_t nee = P.nee[p];
         V3 ld = mk3(0.0f, 0.0f, 0.0f);
         if ((nee & PT_NEE_SHADOW) && P.occluded[p] == 0) ld = ld + mk3(A.x, A.y, A.z);
         if (nee & PT_NEE_PROBE) {
@@ -2849,6 +2867,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         float4 o_ray_o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), o_ray_d = o_ray_o, o_beta = o_ray_o;
         auto commit = [&]() {
             if constexpr (PART != 2) {
+                if (wr & 64u) { P.pendA[p] = s_stage[4][threadIdx.x]; if constexpr (PART == 1) P.nee[p] = o_nee; }      // the folded estimate: one row (part 2 still reads the dimension count)
                 if (wr & 4u) { P.sh_o[p] = s_stage[0][threadIdx.x]; P.sh_d[p] = s_stage[1][threadIdx.x]; }
                 if (wr & 8u) { P.pr_o[p] = s_stage[2][threadIdx.x]; P.pr_d[p] = s_stage[3][threadIdx.x]; }
                 if (wr & 16u) { P.pendA[p] = s_stage[4][threadIdx.x]; P.pendB[p] = s_stage[5][threadIdx.x]; P.pbeta[p] = s_stage[6][threadIdx.x]; P.nee[p] = o_nee; }
@@ -3080,11 +3099,11 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             V2 u_light = sm.get_2d(sc);
                             V2 u_scat = sm.get_2d(sc);
                             PT_SHP(3);
-#if PT_LIGHTS_IN_LDS
-                            const PtLight& lt = lights_lds ? s_lights[light_num] : sc.lights[light_num];
-#else
-                            const PtLight& lt = sc.lights[light_num];
-#endif
+                            // The record is read through a reference whose address space the compiler knows: the block below is instantiated
+                            // once over the LDS copy (ds_read, counted by lgkmcnt alone) and once over the global table (global_load), under the
+                            // kernel-uniform lights_lds.  Through one generic reference every field was a flat load, each followed by a wait for
+                            // BOTH counters -- the next iteration's prefetches included.
+                            auto estimate = [&](const PtLight& lt) __attribute__((always_inline)) {
                             uint32_t nee = (light_num << 8) | (PART == 1 ? PT_NEE_DIMS5 : 0u);
                             V3 A = mk3(0.0f, 0.0f, 0.0f), B = mk3(0.0f, 0.0f, 0.0f);
                             V3 li, wi, lp, lperr, ln;
@@ -3174,7 +3193,24 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 }
                             }
                             PT_SHP(5);
-                            if (nee & (PT_NEE_SHADOW | PT_NEE_PROBE)) {
+                            bool folded = false;
+                            // A vertex with a shadow ray and no probe: k_nee_resolve would add beta * ((0 + A) / light_pdf) if the ray is unoccluded and
+                            // beta * ((0) / light_pdf) if it is not.  The first is computed here, operation for operation, and stored in pendA with
+                            // .w = +0 as the mark (a real .w is a selection pdf > 0).  The second is beta * (+0): light_pdf > 0 makes the quotient +0,
+                            // and with beta finite the product is +0 or -0 per channel.  L starts as +0 (k_gen) and every write to it is a sum; a sum
+                            // is -0 only if both terms are, so L never is -0, and L + (+-0) = L bit for bit: skipping the add changes nothing.
+                            // Anything non-finite (inf * 0 = NaN would reach L) keeps the three-array form.  tests/test_nee_fold_zero.py restates this.
+                            if ((nee & (PT_NEE_SHADOW | PT_NEE_PROBE)) == PT_NEE_SHADOW) {
+                                const V3 add = beta * ((mk3(0.0f, 0.0f, 0.0f) + A) / light_pdf);
+                                if (isfinite(beta.x) && isfinite(beta.y) && isfinite(beta.z) && isfinite(A.x) && isfinite(A.y) && isfinite(A.z) && isfinite(light_pdf)) {
+                                    s_stage[4][threadIdx.x] = make_float4(add.x, add.y, add.z, 0.0f);
+                                    o_nee = nee; wr |= 64u; PT_COMMIT_NOW(3);
+                                    want_nee = true; want_sh = true;
+                                    folded = true;
+                                }
+                            }
+                            if (folded) { }          // stored above
+                            else if (nee & (PT_NEE_SHADOW | PT_NEE_PROBE)) {
                                 s_stage[4][threadIdx.x] = make_float4(A.x, A.y, A.z, light_pdf);
                                 s_stage[5][threadIdx.x] = make_float4(B.x, B.y, B.z, 0.0f);
                                 s_stage[6][threadIdx.x] = make_float4(beta.x, beta.y, beta.z, 0.0f);
@@ -3183,6 +3219,12 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 want_sh = (nee & PT_NEE_SHADOW) != 0;
                                 want_pr = (nee & PT_NEE_PROBE) != 0;
                             } else if constexpr (PART == 1) { P.nee[p] = nee; }        // nothing pending, but part 2 reads the dimension count
+                            };
+#if PT_LIGHTS_IN_LDS
+                            if (lights_lds) estimate(s_lights[light_num]); else estimate(sc.lights[light_num]);
+#else
+                            estimate(sc.lights[light_num]);
+#endif
                         } else if constexpr (PART == 1) { P.nee[p] = 0u; }              // light_pdf == 0: one dimension drawn
                     }
                     PT_SHP(6);
