@@ -115,12 +115,12 @@ struct pt_context {
     int trace_far = -1, trace_far_choice = -1;
     DevBuf d_cnt_save;
     // PBRTGPU_SHADE_LOCAL: the material sort inside runs of 4 096 queue entries + one lobe-list kernel (k_sort_local) instead of the global sort and a
-    // kernel per class: 0 never, 1 wherever possible, default -1 = scenes that have lobe-list (non-Matte) constant materials, no textured ones and no
-    // instances (mixed materials 889 -> 916 Mrays/s, with a sphere light as well 834 -> 843; a Matte scene lit by a sphere, where the sorted queue exists
+    // kernel per class, for scenes without textured materials, instances, infinite or delta lights or a Material "mix" (every other scene keeps its own
+    // path whatever this says): 0 never, 1 always -- a Matte scene lit by a sphere included --, default -1 = scenes that have lobe-list (non-Matte) constant
+    // materials (mixed materials 889 -> 916 Mrays/s, with a sphere light as well 834 -> 843; a Matte scene lit by a sphere, where the sorted queue exists
     // only to select the sphere-capable kernels, loses 1.4 % and keeps the global sort)
     int shade_local = -1;
     bool scene_has_lobe_materials = false;
-    int nee_split = 0;                                 // PBRTGPU_NEE_SPLIT: kernel families that shade a vertex in two kernels (ptk_shade)
     int sort_cont = -1;                                // continuation rays of a bounce ordered like the shadow rays: 0 never, 1 for the traversal kernel only
                                                        // (shading keeps path order), 2 for both, -1 (default): mode 1 for scenes larger than the Infinity Cache
     int sort_cont_min = 1 << 20;                       // ... and the continuation rays (when sort_cont is on) from this many up: its own threshold (PBRTGPU_SORT_CONT_MIN)
@@ -309,8 +309,6 @@ pt_status pt_context_create(int device, pt_context** out) {
     if (const char* e = std::getenv("PBRTGPU_SORT_CONT")) ctx->sort_cont = std::min(2, std::max(-1, std::atoi(e)));
     if (const char* e = std::getenv("PBRTGPU_TRACE_FAR")) ctx->trace_far = std::atoi(e);
     if (const char* e = std::getenv("PBRTGPU_SHADE_LOCAL")) ctx->shade_local = std::atoi(e);
-    ctx->nee_split = ptk_nee_split_default();
-    if (const char* e = std::getenv("PBRTGPU_NEE_SPLIT")) ctx->nee_split = std::atoi(e);
     ctx->grid_wide = ctx->n_cu * 8;
     // Sobol' tables: $PBRTGPU_DATA_DIR, else <directory of this shared library>/../data
     const char* dd = std::getenv("PBRTGPU_DATA_DIR");
@@ -2351,7 +2349,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
                         const pt_status gs = fill_light_grid(ctx, Q);
                         if (gs != PT_OK) return gs;
                     }
-                    PT_HIP(ptk_shade_any(ctx, ctx->stream, ctx->grid_shade, ctx->sc, ctx->paths, Q, cnt, ctx->nee_split, ctx->shade_local < 0 ? ((ctx->scene_has_lobe_materials && !ctx->sc.textured) ? 1 : 0) : ctx->shade_local));
+                    PT_HIP(ptk_shade_any(ctx, ctx->stream, ctx->grid_shade, ctx->sc, ctx->paths, Q, cnt, ctx->shade_local < 0 ? ((ctx->scene_has_lobe_materials && !ctx->sc.textured) ? 1 : 0) : ctx->shade_local));
                     PT_HIP(ptk_prep(ctx->stream, Q, 1));
                     {
                         const pt_status ss = sort_shadow();

@@ -39,20 +39,8 @@ namespace ptq {
 #define PT_KERNEL extern "C" __global__
 #endif
 
-#ifndef PT_SHADE_PF_DEEP
-#define PT_SHADE_PF_DEEP 0       // 1: k_shade's one-iteration-ahead prefetch also covers the ray, the throughput and the leaf record
-#endif
-#ifndef PT_LOBES_IN_LDS
-#define PT_LOBES_IN_LDS 1       // the lobe-list kernels keep the lobes of the material a wave's lanes share in LDS (shade_body): mixed materials 927 -> 942 Mrays/s
-#endif
-#ifndef PT_TEX_PROGS_GLOBAL
-#define PT_TEX_PROGS_GLOBAL 1       // the texture programs' offsets are read from the material table, not from the per-lane copy (indexed by the job loop: scratch): crown-class 795 -> 813 Mrays/s
-#endif
 #ifndef PT_LIGHTS_IN_LDS
 #define PT_LIGHTS_IN_LDS 8       // the shading kernels keep the light records of scenes with at most this many lights in LDS (0: never); RT1M 1 075 -> 1 081 Mrays/s
-#endif
-#ifndef PT_TEX_NOUNROLL
-#define PT_TEX_NOUNROLL 0
 #endif
 
 // ============================================================ Sobol' sampler
@@ -177,12 +165,7 @@ PT_DEV uint64_t sampler_index(const PtScene& sc, uint64_t sample_num, int32_t px
     return sobol_interval_to_index(sc.sobol, sample_num, px - sc.film.sample_bounds[0], py - sc.film.sample_bounds[1]);
 }
 // SobolSampler::sample_dimension (samplers/sobol.rs:167-185)
-#ifdef PT_SAMPLER_NOINLINE
-__device__ __noinline__ float sample_dimension(
-#else
-PT_DEV float sample_dimension(
-#endif
-const PtScene& sc, uint64_t index, uint32_t dim, int32_t px, int32_t py) {
+PT_DEV float sample_dimension(const PtScene& sc, uint64_t index, uint32_t dim, int32_t px, int32_t py) {
     if (sc.sobol.kind == PT_SAMPLER_HALTON) return halton_sample_dimension(sc.sobol, index, dim);
     float s = sobol_sample_float(sc.sobol, index, dim);
     if (dim == 0 || dim == 1) {
@@ -1026,7 +1009,7 @@ PT_DEV void node_step_lean(const PtScene& sc, LaneRay& r, TravCtx& c) {
 // the OWNER computed and handed over by DPP), in loads 4-6 both read node B; the child references each lane fetches for itself.  Six of the seven loads of
 // a visit then see two lanes per 128-byte line -- four tag look-ups per visit instead of seven, still 64 rays per wave.  The odd lanes swap the address
 // registers before and the data registers after the loads (v_swap_b32 under EXEC = odd lanes), so that every lane finds its near rows in x1-3 and its far
-// rows in the PARTNER's x4-6, read through DPP as a source modifier of the slab arithmetic.  A lane whose partner visits a node while it does not helps
+// rows in the partner's x4-6, read through DPP as a source modifier of the slab arithmetic.  A lane whose partner visits a node while it does not helps
 // with the partner's far rows and does nothing else.  m_node = __ballot(w_node).  Measured (Mrays/s at 64 spp, k_trace / this): 16 M sparse triangles
 // 421 / 485, 8 M sparse 525 / 603; where nodes hit the caches the 19 extra instructions per visit cost more than the look-ups save (RT1M 1083 / 1040,
 // 4 M triangles 1288 / 1241), hence the trial.
@@ -1862,7 +1845,6 @@ PT_KERNEL void k_prep(PtQueues Q, int mode) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (mode == 0) {            // before SHADE: nee and next start empty
             Q.counts[PT_Q_NEXT] = 0; Q.counts[PT_Q_NEE] = 0; Q.counts[PT_Q_TICKET] = 0; Q.counts[PT_Q_TICKET2] = 0; Q.counts[PT_Q_TICKET3] = 0; Q.counts[PT_Q_SHADOW] = 0; Q.counts[PT_Q_PROBE] = 0;
-            Q.counts[PT_Q_TICKET_N1] = 0; Q.counts[PT_Q_TICKET_N2] = 0; Q.counts[PT_Q_TICKET_N3] = 0;
             for (uint32_t k = 0; k < 8u; k++) Q.counts[PT_Q_SEG_TICKET0 + 32u * k] = 0;
         } else {                    // after SHADE: next becomes cur (host swaps the pointers)
             Q.counts[PT_Q_CUR] = Q.counts[PT_Q_NEXT]; Q.counts[PT_Q_NEXT] = 0; Q.counts[PT_Q_TICKET] = 0;
@@ -2594,7 +2576,7 @@ PT_DEV void textured_params_t(const PtScene& sc, int32_t material, const TexHit&
     mp = sc.mat_params[material];
     // k_tex_resolve reads the program offsets where they lie: indexed by the job loop's variable, the copy in `mp` lives in scratch (the out-of-line
     // form, inside the one-kernel textured shading, spills more with it and keeps the copy)
-    const uint32_t* progs = (PT_TEX_PROGS_GLOBAL && INL) ? sc.mat_params[material].prog : mp.prog;
+    const uint32_t* progs = INL ? sc.mat_params[material].prog : mp.prog;
     // One call site for every texture program of the hit (the evaluations are independent of one another, so their order is free): jobs 0-2
     // are the bump map's displacement at p + du * dpdu, p + dv * dpdv and p (core/material.rs:31-72), jobs 3-10 the parameters Kd Ks Kr Kt
     // opacity sigma metal-eta metal-k, jobs 11-14 roughness uroughness vroughness eta.
@@ -2606,9 +2588,6 @@ PT_DEV void textured_params_t(const PtScene& sc, int32_t material, const TexHit&
         if (dv == 0.0f) dv = 0.0005f;
     }
     float a_r = mp.a_r, a_u = mp.a_u, a_v = mp.a_v;
-#if PT_TEX_NOUNROLL
-#pragma nounroll
-#endif
     for (int j = 0; j < 15; j++) {
         const int k = j < 3 ? 8 : (j < 11 ? j - 3 : j - 2);          // index into PtMatParams::prog
         const uint32_t pr = progs[k];
@@ -2753,32 +2732,26 @@ __device__ unsigned long long g_shade_prof[16];
 #endif
 // 0.0f the optimiser cannot see through (one v_mov): see the continuation store in shade_body
 PT_DEV float opaque_zero() { float z = 0.0f; asm volatile("" : "+v"(z)); return z; }
-// PART: 0 = the whole vertex in one kernel.  1 = next-event estimation only (light pick, light sample, BSDF sample for MIS; writes the
-// shadow / probe rays, the pending terms and -- for every vertex with a BSDF -- the nee word, whose PT_NEE_DIMS bits tell part 2 how many
-// sample dimensions were drawn); 2 = everything else (emission, pass-through, continuation, Russian roulette), run AFTER part 1 on the same
-// list because it overwrites the ray.  Both halves rebuild the interaction from (ray, record): the split trades that for register room.
 // ENV: the scene has an infinite light (the *_env kernels): escaped rays add its Le, next-event estimation samples it.
 // DELTA (with ENV): the scene has a delta light (k_shade_delta, k_shade_delta_inst): its estimate is f Li / pdf with no power heuristic, no BSDF half, no probe ray.
 // MIX (with TEX, ENV and DELTA): the scene holds a Material "mix" (k_shade_mix, k_shade_mix_inst): the BSDF is the scaled lobe list (MBsdf, pt_bxdf.h).
-template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, int PART = 0, bool ENV = false, bool DELTA = false, bool MIX = false>
+template <bool GENERAL, bool SPH, bool TEX = false, bool INST = false, bool RES = false, bool ENV = false, bool DELTA = false, bool MIX = false>
 PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, const uint32_t* list, uint32_t begin, uint32_t end,
                        uint32_t* ticket) {
     __shared__ unsigned long long s_vert;
     // A vertex's next-event outputs wait here (28 KB per block) until every load of the iteration has come back: on this ISA loads and
     // stores share one in-order counter (vmcnt), so a store issued in the middle of the dependent chain grid -> light table -> light
     // makes each later wait sit out the store's round trip as well.
-    __shared__ float4 s_stage[PART == 2 ? 1 : 7][PT_BLOCK];
+    __shared__ float4 s_stage[7][PT_BLOCK];
     __shared__ uint32_t s_pend[PT_SHADE_FLUSH][PT_BLOCK];      // per lane: path ids of the iterations not yet queued (their queue bits: `pend_want`)
-#if PT_LOBES_IN_LDS
     __shared__ uint32_t s_lobes[GENERAL ? PT_BLOCK / 64 : 1][PT_MAX_LOBES * (sizeof(PtLobe) / 4)];      // per wave: the lobe list of the material its lanes share
-#endif
     __shared__ uint32_t s_pkey[PT_SHADE_FLUSH][PT_BLOCK];      // per lane: the sort key of those iterations' shadow rays
     if (threadIdx.x == 0) s_vert = 0;
 #if PT_LIGHTS_IN_LDS
     // Scenes with a handful of lights (BASELINE's have two): the light records sit in LDS for the kernel's life, which takes one round trip out of
     // every vertex's dependent chain grid row -> light number -> light record -> sample.
     __shared__ PtLight s_lights[PT_LIGHTS_IN_LDS];
-    const bool lights_lds = sc.n_lights <= (uint32_t)PT_LIGHTS_IN_LDS && PART != 2;
+    const bool lights_lds = sc.n_lights <= (uint32_t)PT_LIGHTS_IN_LDS;
     if (lights_lds) {
         const uint32_t nd = sc.n_lights * (uint32_t)(sizeof(PtLight) / 4);
         const uint32_t* src = reinterpret_cast<const uint32_t*>(sc.lights);
@@ -2803,10 +2776,6 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
     uint32_t pf_st = 0, pf_pk = 0;
     uint64_t pf_idx = 0;
     bool pf_valid = false;
-    // PT_SHADE_PF_DEEP: the next iteration's ray, throughput and leaf record come one iteration ahead as well, so that an iteration starts with
-    // everything its surface needs and its dependent chain is grid -> light instead of path state -> record -> grid -> light
-    constexpr bool DEEP = PT_SHADE_PF_DEEP && !GENERAL && !SPH && !INST && PART == 0;      // the Matte kernels have the 21 registers it takes (232 -> 253); the lobe-list kernels sit at 256
-    float4 pf_ro = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pf_rd = pf_ro, pf_beta = pf_ro, pf_ra = pf_ro, pf_rb = pf_ro, pf_rc = pf_ro;
     const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     auto flush_batch = [&]() {
         if (n_batch == 0) return;
@@ -2866,12 +2835,10 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         uint32_t wr = 0, o_nee = 0, o_state = 0;     // outputs held back to the end of the iteration: 1 ray_o, 2 ray_d + beta, 4 shadow ray, 8 probe ray, 16 pending NEE, 32 state
         float4 o_ray_o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), o_ray_d = o_ray_o, o_beta = o_ray_o;
         auto commit = [&]() {
-            if constexpr (PART != 2) {
-                if (wr & 64u) { P.pendA[p] = s_stage[4][threadIdx.x]; if constexpr (PART == 1) P.nee[p] = o_nee; }      // the folded estimate: one row (part 2 still reads the dimension count)
-                if (wr & 4u) { P.sh_o[p] = s_stage[0][threadIdx.x]; P.sh_d[p] = s_stage[1][threadIdx.x]; }
-                if (wr & 8u) { P.pr_o[p] = s_stage[2][threadIdx.x]; P.pr_d[p] = s_stage[3][threadIdx.x]; }
-                if (wr & 16u) { P.pendA[p] = s_stage[4][threadIdx.x]; P.pendB[p] = s_stage[5][threadIdx.x]; P.pbeta[p] = s_stage[6][threadIdx.x]; P.nee[p] = o_nee; }
-            }
+            if (wr & 64u) P.pendA[p] = s_stage[4][threadIdx.x];      // the folded estimate: one row
+            if (wr & 4u) { P.sh_o[p] = s_stage[0][threadIdx.x]; P.sh_d[p] = s_stage[1][threadIdx.x]; }
+            if (wr & 8u) { P.pr_o[p] = s_stage[2][threadIdx.x]; P.pr_d[p] = s_stage[3][threadIdx.x]; }
+            if (wr & 16u) { P.pendA[p] = s_stage[4][threadIdx.x]; P.pendB[p] = s_stage[5][threadIdx.x]; P.pbeta[p] = s_stage[6][threadIdx.x]; P.nee[p] = o_nee; }
             if (wr & 1u) P.ray_o[p] = o_ray_o;
             if (wr & 2u) { P.ray_d[p] = o_ray_d; P.beta[p] = o_beta; }
             if (wr & 32u) P.state[p] = o_state;
@@ -2894,16 +2861,13 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
         const int32_t pf_rec_now = pf_rec;
         const uint32_t pf_st_now = pf_st, pf_pk_now = pf_pk;
         const uint64_t pf_idx_now = pf_idx;
-        const float4 pf_ro_now = pf_ro, pf_rd_now = pf_rd, pf_beta_now = pf_beta, pf_ra_now = pf_ra, pf_rb_now = pf_rb, pf_rc_now = pf_rc;
         pf_valid = chunk_left > 0;
         const bool pf_lane = pf_valid && next_base + lane < end;
         if (pf_lane) pf_p = list[next_base + lane];
         if (active) {
             p = had_pf ? pf_p_now : list[item];
             PT_SHP_SYNC(13);
-            float4 ro4, rd4, beta4;
-            if (DEEP && had_pf) { ro4 = pf_ro_now; rd4 = pf_rd_now; beta4 = pf_beta_now; }
-            else { ro4 = P.ray_o[p]; rd4 = P.ray_d[p]; beta4 = P.beta[p]; }
+            const float4 ro4 = P.ray_o[p], rd4 = P.ray_d[p], beta4 = P.beta[p];
             V3 ro = f4_3(ro4), rd = f4_3(rd4);
             int32_t rec = had_pf ? pf_rec_now : P.hit_rec[p];
             uint32_t st = had_pf ? pf_st_now : P.state[p];
@@ -2913,8 +2877,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             PT_SHP_SYNC(14);
             // the hit's leaf record: asked for first, so that it travels while the sample tables are read
             float4 rec_a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rec_b = rec_a, rec_c = rec_a;
-            if (DEEP && had_pf) { rec_a = pf_ra_now; rec_b = pf_rb_now; rec_c = pf_rc_now; }
-            else if (rec >= 0) {
+            if (rec >= 0) {
                 const float4* q = reinterpret_cast<const float4*>(sc.tris) + (size_t)(uint32_t)rec * 3;
                 rec_a = q[0]; rec_b = q[1]; rec_c = q[2];
             }
@@ -2939,9 +2902,8 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             if (pf_lane) {                                   // pf_p has long arrived: the head of the next iteration's dependent chain, one iteration early
                 pf_rec = P.hit_rec[pf_p];
                 pf_st = P.state[pf_p]; pf_idx = P.sobol_index[pf_p]; pf_pk = P.pixel[pf_p];
-                if constexpr (DEEP) { pf_ro = P.ray_o[pf_p]; pf_rd = P.ray_d[pf_p]; pf_beta = P.beta[pf_p]; }
             }
-            if constexpr (ENV && PART != 1) {         // a ray that left the scene: every infinite light's Le (path.rs:86-98)
+            if constexpr (ENV) {       // a ray that left the scene: every infinite light's Le (path.rs:86-98)
                 if (rec < 0 && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
                     float4 L = P.L[p];
                     for (uint32_t k = 0; k < sc.n_envs; k++) {      // `l += beta * light.le(ray)` light by light, not beta times their sum
@@ -2952,7 +2914,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 }
             }
             // emitted radiance at the first vertex / after a specular bounce (path.rs:87-98)
-            if (PART != 1 && found && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
+            if (found && (bounces == 0 || (flags & PT_ST_SPECULAR))) {
                 int32_t li = s.light;
                 if (li >= 0) {
                     V3 le = light_L(sc.lights[li], s.n, -rd);
@@ -3014,13 +2976,11 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 if constexpr (GENERAL) { if (!no_bsdf && !use_tm) no_bsdf = sc.materials[s.material].has_bsdf == 0; }
                 if (no_bsdf) {
                     // no BSDF: continue through the surface, same bounce count (path.rs:108-111)
-                    if constexpr (PART != 1) {
-                        V3 no = offset_ray_origin(s.p, s.p_error, s.n, rd);
-                        o_ray_o = make_float4(no.x, no.y, no.z, PT_INF); wr |= 1u;
-                        cont = true; PT_COMMIT_NOW(0);
-                    }
+                    V3 no = offset_ray_origin(s.p, s.p_error, s.n, rd);
+                    o_ray_o = make_float4(no.x, no.y, no.z, PT_INF); wr |= 1u;
+                    cont = true; PT_COMMIT_NOW(0);
                 } else {
-                    if constexpr (PART != 1) n_vert++;
+                    n_vert++;
                     Bsdf b;
                     std::conditional_t<MIX, MBsdf, GBsdf> gb;
                     bool nonspecular;
@@ -3038,7 +2998,6 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 else { const PtMix& mx = material_mix(sc, sc.materials[s.material]); gb.lobes = mx.lobes; gb.n_lobes = mx.n_lobes; gb.scales = &mx.scales; }
                             }
                         }
-#if PT_LOBES_IN_LDS
                         if constexpr (!INST && !TEX) {          // (the one-kernel textured form spills as it is: 109 registers, 171 with this)
                             // The lobe evaluators walk the material's lobe list four times per vertex (f, pdf, two sample_f), a dependent chain of
                             // small loads each time.  The queue is ordered by material, so the lanes that got here nearly always share one: then
@@ -3057,7 +3016,6 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 gb.lobes = reinterpret_cast<const PtLobe*>(dst);
                             }
                         }
-#endif
                         nonspecular = m.nonspecular > 0;
                         bsdf_eta = m.bsdf_eta;
                     } else {
@@ -3087,10 +3045,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                     };
                     PT_SHP(1);
                     // ---- next-event estimation (uniform_sample_one_light_surface, sample_lights.rs:129-176)
-                    if constexpr (PART == 2) {           // part 1 drew this vertex's next-event dimensions and noted how many
-                        if (nonspecular && sc.n_lights > 0) sm.s.dim += (P.nee[p] & PT_NEE_DIMS5) ? 5u : 1u;
-                    }
-                    if (PART != 2 && nonspecular && sc.n_lights > 0) {
+                    if (nonspecular && sc.n_lights > 0) {
                         const float* tab = grid_lookup(sc.grid, s.p);
                         float light_pdf;
                         uint32_t light_num = sample_discrete(tab, sc.n_lights, sm.get_1d(sc), &light_pdf);
@@ -3104,7 +3059,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             // kernel-uniform lights_lds.  Through one generic reference every field was a flat load, each followed by a wait for
                             // BOTH counters -- the next iteration's prefetches included.
                             auto estimate = [&](const PtLight& lt) __attribute__((always_inline)) {
-                            uint32_t nee = (light_num << 8) | (PART == 1 ? PT_NEE_DIMS5 : 0u);
+                            uint32_t nee = light_num << 8;
                             V3 A = mk3(0.0f, 0.0f, 0.0f), B = mk3(0.0f, 0.0f, 0.0f);
                             V3 li, wi, lp, lperr, ln;
                             float lpdf;
@@ -3218,18 +3173,17 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                 want_nee = true;
                                 want_sh = (nee & PT_NEE_SHADOW) != 0;
                                 want_pr = (nee & PT_NEE_PROBE) != 0;
-                            } else if constexpr (PART == 1) { P.nee[p] = nee; }        // nothing pending, but part 2 reads the dimension count
+                            }
                             };
 #if PT_LIGHTS_IN_LDS
                             if (lights_lds) estimate(s_lights[light_num]); else estimate(sc.lights[light_num]);
 #else
                             estimate(sc.lights[light_num]);
 #endif
-                        } else if constexpr (PART == 1) { P.nee[p] = 0u; }              // light_pdf == 0: one dimension drawn
+                        }
                     }
                     PT_SHP(6);
                     // ---- continuation (path.rs:139-233)
-                    if constexpr (PART != 1) {
                     V2 u = sm.get_2d(sc);
                     PT_SHP(7);
                     V3 f, wi;
@@ -3265,16 +3219,9 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             cont = true;
                         }
                     }
-                    }
                     dim = sm.s.dim;
                 }
                 if (cont) { o_state = (dim & 0xffffu) | ((bounces & 0xffu) << 16) | ((flags & ~PT_ST_CAMERA) << 24); wr |= 32u; } PT_COMMIT_NOW(5);     // later rays are plain Rays
-            }
-        }
-        if constexpr (DEEP) {          // the next iteration's leaf record: its index has arrived by now (asked for at the top of this iteration's work)
-            if (pf_lane && pf_rec >= 0) {
-                const float4* q = reinterpret_cast<const float4*>(sc.tris) + (size_t)(uint32_t)pf_rec * 3;
-                pf_ra = q[0]; pf_rb = q[1]; pf_rc = q[2];
             }
         }
         PT_SHP(8);
@@ -3322,31 +3269,20 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_inst_plain(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET2]);
 }
-// scenes with textured materials (and possibly spheres): lobes are built per hit for the textured ones
-PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_general_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
-}
 
-// The textured segment in two kernels (PBRTGPU_TEX_SPLIT, default on; scenes without instances).  k_shade_general_tex carries the texture
-// interpreter, the MIP lookups and the lobe builder next to next-event estimation: 256 registers, 130 spilled, 3 KB of scratch per lane, and
-// everything AFTER the textures runs 1.6x slower than in k_shade_general for it (profiles/r03_q_tex_kernel_experiments.txt).  k_tex_resolve
+// The textured segment of the sorted queue in two kernels (scenes without instances).  One kernel that carries the texture interpreter, the
+// MIP lookups and the lobe builder next to next-event estimation came out at 256 registers, 130 spilled, 3 KB of scratch per lane, and
+// everything AFTER the textures ran 1.6x slower than in k_shade_general for it (profiles/r03_q_tex_kernel_experiments.txt).  k_tex_resolve
 // does the per-hit half of Material::compute_scattering_functions alone -- surface, ray differentials, bump map, every programmed
 // parameter -- and leaves 36 floats per path (PtPaths::tex_res); k_shade_general_res is k_shade_general with the lobe list built from them.
-// ALL: the locally sorted queue (k_sort_local) -- every entry of Q.cur is looked at, the ones whose material is not textured are passed over
-// after one look at the hit record's material field.
-template <bool SPH, bool ALL = false>
+template <bool SPH>
 PT_DEV void tex_resolve_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q) {
-    const uint32_t begin = ALL ? 0u : Q.counts[PT_Q_TEX_BEGIN], end = ALL ? Q.counts[PT_Q_CUR] : Q.counts[PT_Q_GENERAL_END];
-    const uint32_t* list = ALL ? Q.cur : Q.sorted;
+    const uint32_t begin = Q.counts[PT_Q_TEX_BEGIN], end = Q.counts[PT_Q_GENERAL_END];
+    const uint32_t* list = Q.sorted;
     __shared__ float s_texval[3 * PT_TEX_PROG_MAX][PT_BLOCK];          // the texture interpreter's node values (tex_eval_inl), a column per lane
     for (uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x; i < end; i += gridDim.x * blockDim.x) {
         const uint32_t p = list[i];
         const int32_t rec = P.hit_rec[p];
-        if constexpr (ALL) {
-            if (rec < 0) continue;
-            const uint32_t m1 = sc.tris[rec].flags >> PT_TRI_MATERIAL_SHIFT;
-            if (m1 == 0u || !sc.materials[m1 - 1u].textured) continue;
-        }
         const uint32_t st = P.state[p];
         const uint32_t bounces = (st >> 16) & 0xffu, flags = st >> 24;
         if (rec < 0 || (int32_t)bounces >= sc.max_depth) continue;         // shade_body builds no BSDF there either
@@ -3395,52 +3331,12 @@ PT_DEV void tex_resolve_body(const PtScene& sc, const PtPaths& P, const PtQueues
 #endif
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false>(sc, P, Q); }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_sph(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<true>(sc, P, Q); }
-PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_TEX_RESOLVE_WAVES) k_tex_resolve_all(PtScene sc, PtPaths P, PtQueues Q) { tex_resolve_body<false, true>(sc, P, Q); }
-PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, false, false, false, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
-}
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_general_res(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
 }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_general_res_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true, false, false, true>(sc, P, Q, cnt, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], &Q.counts[PT_Q_TICKET3]);
 }
-
-// ---- the vertex in two kernels (shade_body PART 1 / PART 2; PBRTGPU_NEE_SPLIT selects the kernel families that run this way).  Next-event
-// estimation is the register peak of every shading kernel and, in scenes with sphere lights, the only place where Sphere::sample_from and the
-// EFloat quadratic of Shape::pdf_from are needed: on its own it leaves the continuation half lean, and the sphere code out of it.
-#ifndef PT_NEE_WAVES
-#define PT_NEE_WAVES 2
-#endif
-#ifndef PT_CONT_WAVES
-#define PT_CONT_WAVES 3
-#endif
-#ifndef PT_NEE_GEN_WAVES
-#define PT_NEE_GEN_WAVES 2
-#endif
-#ifndef PT_CONT_GEN_WAVES
-#define PT_CONT_GEN_WAVES 3
-#endif
-#ifndef PT_CONT_SPH_WAVES
-#define PT_CONT_SPH_WAVES 2      // the sphere-capable continuation halves rebuild hits on spheres (Sphere::intersect + its interaction): 185-200 registers
-#endif
-#ifndef PT_NEE_SPLIT_DEFAULT
-#define PT_NEE_SPLIT_DEFAULT 0
-#endif
-#define PT_SPLIT_KERNELS(NAME, WN, WC, LIST, BEGIN, END, TN, TC, ...)                                                                              \
-    PT_KERNEL void __launch_bounds__(PT_BLOCK, WN) NAME##_nee(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                     \
-        shade_body<__VA_ARGS__, 1>(sc, P, Q, cnt, LIST, BEGIN, END, &Q.counts[TN]);                                                                \
-    }                                                                                                                                              \
-    PT_KERNEL void __launch_bounds__(PT_BLOCK, WC) NAME##_cont(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {                    \
-        shade_body<__VA_ARGS__, 2>(sc, P, Q, cnt, LIST, BEGIN, END, &Q.counts[TC]);                                                                \
-    }
-PT_SPLIT_KERNELS(k_shade, PT_NEE_WAVES, PT_CONT_WAVES, Q.cur, 0u, Q.counts[PT_Q_CUR], PT_Q_TICKET_N1, PT_Q_TICKET, false, false, false, false, false)
-PT_SPLIT_KERNELS(k_shade_matte_sorted, PT_NEE_WAVES, PT_CONT_WAVES, Q.sorted, 0u, Q.counts[PT_Q_MATTE_END], PT_Q_TICKET_N1, PT_Q_TICKET, false, false, false, false, false)
-PT_SPLIT_KERNELS(k_shade_general, PT_NEE_GEN_WAVES, PT_CONT_GEN_WAVES, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_TEX_BEGIN], PT_Q_TICKET_N2, PT_Q_TICKET2, true, false, false, false, false)
-PT_SPLIT_KERNELS(k_shade_matte_sorted_sph, PT_NEE_WAVES, PT_CONT_SPH_WAVES, Q.sorted, 0u, Q.counts[PT_Q_MATTE_END], PT_Q_TICKET_N1, PT_Q_TICKET, false, true, false, false, false)
-PT_SPLIT_KERNELS(k_shade_general_sph, PT_NEE_GEN_WAVES, PT_CONT_SPH_WAVES, Q.sorted, Q.counts[PT_Q_MATTE_END], Q.counts[PT_Q_TEX_BEGIN], PT_Q_TICKET_N2, PT_Q_TICKET2, true, true, false, false, false)
-PT_SPLIT_KERNELS(k_shade_general_res, PT_NEE_GEN_WAVES, PT_CONT_GEN_WAVES, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], PT_Q_TICKET_N3, PT_Q_TICKET3, true, false, false, false, true)
-PT_SPLIT_KERNELS(k_shade_general_res_sph, PT_NEE_GEN_WAVES, PT_CONT_SPH_WAVES, Q.sorted, Q.counts[PT_Q_TEX_BEGIN], Q.counts[PT_Q_GENERAL_END], PT_Q_TICKET_N3, PT_Q_TICKET3, true, true, false, false, true)
 
 // Sort keys of a bounce's continuation rays, for scenes larger than the Infinity Cache (pt_context.cpp sort_cont): a pass of its own over the
 // list k_shade has just written -- inside the shading kernels the key arithmetic cost the general kernel registers it does not have
@@ -3453,40 +3349,38 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_cont_keys(PtScene sc, PtPaths P, co
     }
 }
 
-// Every material through the lobe-list path in PATH order, no material sort (experiment switch PBRTGPU_SHADE_UNSORTED=1: sorted queues make
-// a wave see one material but walk the path pool with gaps; this form keeps the pool accesses dense and lets the lobe dispatch diverge)
+// Every constant material through the lobe-list path in ONE kernel over a whole queue: what walks the locally sorted queue (k_sort_local,
+// ptk_shade).  A run of that queue is ordered by material, so a wave still sees one, and the path pool is walked without the gaps that the
+// global sort's per-kernel lists leave.
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_GEN_WAVES) k_shade_all(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, false>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_all_sph(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
     shade_body<true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
-PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_all_tex(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
-}
 // Scenes with an infinite light (LightSource "infinite"): one kernel over the unsorted shade queue, misses included -- a path whose ray left the
 // scene is shaded here before its slot is recycled (its Le at bounce 0 / after a specular bounce).  The lobe-list form with spheres and per-hit
 // textures covers every material; _inst adds the instance-space reconstruction (scenes with ObjectInstance).
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_env(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, false, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, false, false, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_env_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, true, false, 0, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, true, false, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // Scenes with a delta light (with or without infinite lights): the same two kernels with the delta branch of next-event estimation
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_delta(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, false, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, false, false, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_delta_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, true, false, 0, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, true, false, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 // Scenes that hold a Material "mix": the same two kernels once more, with the scaled lobe list as their BSDF (MBsdf) -- spheres, per-hit textures,
 // environment and delta lights compiled in, so a mix works beside every light and shape the path has.  Scenes without a mix never launch them.
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_SHADE_TEX_WAVES) k_shade_mix(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, false, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, false, false, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 PT_KERNEL void __launch_bounds__(PT_BLOCK, PT_WIDE_KERNEL_WAVES) k_shade_mix_inst(PtScene sc, PtPaths P, PtQueues Q, PtCounters* cnt) {
-    shade_body<true, true, true, true, false, 0, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
+    shade_body<true, true, true, true, false, true, true, true>(sc, P, Q, cnt, Q.cur, 0u, Q.counts[PT_Q_CUR], &Q.counts[PT_Q_TICKET]);
 }
 
 // ============================================================ film
@@ -4649,10 +4543,9 @@ hipError_t ptk_trace(hipStream_t st, int grid, int grid_dist, const PtScene& sc,
         hipLaunchKernelGGL(k_trace_alpha, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
         return PT_LAUNCH_CHECK();
     }
-    static const bool force_sph = std::getenv("PBRTGPU_FORCE_SPH_TRACE") != nullptr;      // diagnosis: what the sphere-capable kernel costs a scene without spheres
     if (sc.dist_leaves && !sc.n_instances) grid = grid_dist;      // the pooled-leaf kernels fit three blocks per CU, the others four
     if (sc.n_instances) hipLaunchKernelGGL(k_trace_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
-    else if ((sc.n_spheres || force_sph) && sc.dist_leaves) hipLaunchKernelGGL(k_trace_sph_dist, dim3(grid), dim3(PT_TBLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
+    else if (sc.n_spheres && sc.dist_leaves) hipLaunchKernelGGL(k_trace_sph_dist, dim3(grid), dim3(PT_TBLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
     else if (sc.n_spheres) hipLaunchKernelGGL(k_trace_sph, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
     else if (sc.dist_leaves && far) hipLaunchKernelGGL(k_trace_far, dim3(grid), dim3(PT_TBLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
     else if (sc.dist_leaves) hipLaunchKernelGGL(k_trace, dim3(grid), dim3(PT_TBLOCK), 0, st, sc, P, Q, cnt, spill, spill_depth, err);
@@ -4829,34 +4722,24 @@ hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode) {
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, st, Q, mode);
     return PT_LAUNCH_CHECK();
 }
-int ptk_nee_split_default() { return PT_NEE_SPLIT_DEFAULT; }
-hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nsplit, int local_sort) {
+hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int local_sort) {
     if (scene_n_mix(sc)) {          // a Material "mix": one kernel over the unsorted queue as well, every light and shape compiled in
         if (sc.n_instances) hipLaunchKernelGGL(k_shade_mix_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         else hipLaunchKernelGGL(k_shade_mix, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         return PT_LAUNCH_CHECK();
     }
     if (sc.n_envs || sc.n_deltas) {
-        // an infinite or a delta light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort, the split next-event kernels
-        // (PBRTGPU_NEE_SPLIT), the local sort (PBRTGPU_SHADE_LOCAL), the textured split (PBRTGPU_TEX_SPLIT) and PBRTGPU_SHADE_UNSORTED are routed around
+        // an infinite or a delta light: one kernel over the unsorted queue, misses included (k_shade_env).  The material sort and the local sort
+        // (PBRTGPU_SHADE_LOCAL) are routed around
         if (sc.n_deltas && sc.n_instances) hipLaunchKernelGGL(k_shade_delta_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         else if (sc.n_deltas) hipLaunchKernelGGL(k_shade_delta, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         else if (sc.n_instances) hipLaunchKernelGGL(k_shade_env_inst, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         else hipLaunchKernelGGL(k_shade_env, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
         return PT_LAUNCH_CHECK();
     }
-    if (sc.general_materials && local_sort && !sc.n_instances && sc.textured && !sc.n_spheres && P.tex_res) {
-        // ... with textured materials: the texture half over the same list (it passes over the untextured entries), then the lobe-list kernel that
-        // takes a textured hit's parameters from what the texture half left
-        hipLaunchKernelGGL(k_sort_local, dim3(grid * 4), dim3(PT_BLOCK), 0, st, sc, P, Q);
-        PtQueues Ql = Q;
-        Ql.cur = Q.sorted;
-        hipLaunchKernelGGL(k_tex_resolve_all, dim3(4096), dim3(PT_BLOCK), 0, st, sc, P, Ql);
-        hipLaunchKernelGGL(k_shade_all_res, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Ql, cnt);
-        return PT_LAUNCH_CHECK();
-    }
     if (sc.general_materials && local_sort && !sc.n_instances && !sc.textured) {
-        // the shade queue ordered by material inside runs of 4 096 entries, one lobe-list kernel over all of it (see k_sort_local)
+        // the shade queue ordered by material inside runs of 4 096 entries, one lobe-list kernel over all of it (see k_sort_local).  A textured scene
+        // takes the global sort below whatever local_sort says: its textured segment needs a list of its own (k_tex_resolve)
         hipLaunchKernelGGL(k_sort_local, dim3(grid * 4), dim3(PT_BLOCK), 0, st, sc, P, Q);
         PtQueues Ql = Q;
         Ql.cur = Q.sorted;
@@ -4864,56 +4747,30 @@ hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths&
         else hipLaunchKernelGGL(k_shade_all, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Ql, cnt);
         return PT_LAUNCH_CHECK();
     }
-    static const int unsorted = [] { const char* e = std::getenv("PBRTGPU_SHADE_UNSORTED"); return e ? std::atoi(e) : 0; }();
-    if (sc.general_materials && unsorted && !sc.n_instances && (!sc.n_spheres || sc.textured)) {
-        if (sc.textured) hipLaunchKernelGGL(k_shade_all_tex, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
-        else hipLaunchKernelGGL(k_shade_all, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt);
-        return PT_LAUNCH_CHECK();
-    }
-    // nsplit (the context's PBRTGPU_NEE_SPLIT): which kernel families run a vertex as two kernels (next-event estimation, then everything else):
-    // 1 the Matte kernels, 2 the lobe-list kernels, 4 the sphere-capable kernels (Matte and lobe-list), 8 the textured segment's second half
-    const int per_cu = grid / 2;          // grid = two blocks per CU (the whole-vertex kernels' occupancy)
 #define PT_RUN(K) hipLaunchKernelGGL(K, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt)
-#define PT_RUN2(K, WN, WC) do { hipLaunchKernelGGL(K##_nee, dim3(per_cu * (WN)), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt); \
-                                hipLaunchKernelGGL(K##_cont, dim3(per_cu * (WC)), dim3(PT_BLOCK), 0, st, sc, P, Q, cnt); } while (0)
-    auto matte_sorted = [&]() {
-        if (sc.n_spheres) { if (nsplit & 4) PT_RUN2(k_shade_matte_sorted_sph, PT_NEE_WAVES, PT_CONT_SPH_WAVES); else PT_RUN(k_shade_matte_sorted_sph); }
-        else { if (nsplit & 1) PT_RUN2(k_shade_matte_sorted, PT_NEE_WAVES, PT_CONT_WAVES); else PT_RUN(k_shade_matte_sorted); }
-    };
-    auto general = [&]() {
-        if (sc.n_spheres) { if (nsplit & 4) PT_RUN2(k_shade_general_sph, PT_NEE_GEN_WAVES, PT_CONT_SPH_WAVES); else PT_RUN(k_shade_general_sph); }
-        else { if (nsplit & 2) PT_RUN2(k_shade_general, PT_NEE_GEN_WAVES, PT_CONT_GEN_WAVES); else PT_RUN(k_shade_general); }
-    };
     if (sc.general_materials) {
         hipLaunchKernelGGL(k_sort_count, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
         hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(PT_SORT_BINS), 0, st, Q);
         hipLaunchKernelGGL(k_sort_scatter, dim3(grid), dim3(PT_BLOCK), 0, st, sc, P, Q);
         if (sc.n_instances) {
             if (!sc.textured && !sc.n_spheres) PT_RUN(k_shade_general_inst_plain); else PT_RUN(k_shade_general_inst);
-        } else if (sc.textured) {       // three segments: Matte | other constant materials | textured materials
-            matte_sorted();
-            general();
-            static const int split = [] { const char* e = std::getenv("PBRTGPU_TEX_SPLIT"); return e ? std::atoi(e) : 1; }();
-            if (split && P.tex_res) {
+        } else {                        // up to three segments: Matte | other constant materials | textured materials
+            if (sc.n_spheres) { PT_RUN(k_shade_matte_sorted_sph); PT_RUN(k_shade_general_sph); }
+            else { PT_RUN(k_shade_matte_sorted); PT_RUN(k_shade_general); }
+            if (sc.textured) {          // P.tex_res: ensure_pool (pt_context.cpp) allocates it for exactly these scenes, textured and without instances
                 if (sc.n_spheres) {
                     hipLaunchKernelGGL(k_tex_resolve_sph, dim3(4096), dim3(PT_BLOCK), 0, st, sc, P, Q);
-                    if (nsplit & 4) PT_RUN2(k_shade_general_res_sph, PT_NEE_GEN_WAVES, PT_CONT_SPH_WAVES); else PT_RUN(k_shade_general_res_sph);
+                    PT_RUN(k_shade_general_res_sph);
                 } else {
                     hipLaunchKernelGGL(k_tex_resolve, dim3(4096), dim3(PT_BLOCK), 0, st, sc, P, Q);
-                    if (nsplit & 8) PT_RUN2(k_shade_general_res, PT_NEE_GEN_WAVES, PT_CONT_GEN_WAVES); else PT_RUN(k_shade_general_res);
+                    PT_RUN(k_shade_general_res);
                 }
-            } else {
-                PT_RUN(k_shade_general_tex);
             }
-        } else {
-            matte_sorted();
-            general();
         }
     } else {
-        if (nsplit & 1) PT_RUN2(k_shade, PT_NEE_WAVES, PT_CONT_WAVES); else PT_RUN(k_shade);
+        PT_RUN(k_shade);
     }
 #undef PT_RUN
-#undef PT_RUN2
     return PT_LAUNCH_CHECK();
 }
 hipError_t ptk_cont_keys(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const uint32_t* list, uint32_t n, uint32_t* keys) {

@@ -13,8 +13,7 @@ hipError_t ptk_light_hooks(hipStream_t st, const PtScene& sc, uint32_t light, ui
                            float* o1);
 hipError_t ptk_light_pdf_from(hipStream_t st, const PtScene& sc, uint32_t light, uint32_t n, const float* ref, const float* wi, float* pdf);
 hipError_t ptk_prep(hipStream_t st, const PtQueues& Q, int mode);
-hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int nee_split, int local_sort = 0);
-int ptk_nee_split_default();
+hipError_t ptk_shade(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const PtQueues& Q, PtCounters* cnt, int local_sort = 0);
 int ptk_trace_wide();
 hipError_t ptk_film(hipStream_t st, int grid, const PtScene& sc, const PtPaths& P, const uint32_t* pixels, uint32_t n_pix, uint32_t n_samples,
                     float4* own, float4* spill, float* radiance_out, uint32_t s0, uint32_t spp_total);

@@ -1,4 +1,5 @@
-// The eight texture functions that k_shade_general_tex and the recursion kernels need OUT of line (their register budgets), included twice
+// The eight texture functions that the shading kernels which evaluate textures inside the vertex (k_shade_general_inst, k_shade_env, k_shade_delta,
+// k_shade_mix and their _inst forms) and the recursion kernels need OUT of line (their register budgets), included twice
 // by pt_texture.h: once as calls (PT_TEXN(x) = x, __noinline__) and once inlined (x_inl, __forceinline__) for k_tex_resolve, which has the
 // budget -- every call level keeps a frame of saved registers in scratch, and the scratch of all waves in flight is more than L2 holds
 // (k_tex_resolve: 2.4 KB of scratch per lane and 138 ms per two textured frames as calls, 0.4 KB and 105 ms inlined).

@@ -286,6 +286,25 @@ def scene_textures(res=48, spp=8, depth=5, sampler="sobol", aamode="closedform",
     return b.build()
 
 
+def scene_sphere_lit_mixed(res=48, spp=8, depth=5):
+    """A sphere light over the room, with a textured Matte, a constant plastic and a constant mirror quad in it: every segment of the
+    material-sorted queue (Matte | constant lobe lists | textured) is non-empty and goes through the sphere-capable kernels."""
+    b = base(res=res, spp=spp, depth=depth)
+    T = scenes
+    b.area_light_source_diffuse(L=(30, 26, 20))
+    t = T.transform_translate(-1.0, 1.2, 0.2)
+    b.shape_sphere(radius=0.25, object_to_world=t[0], world_to_object=t[1])
+    b.no_area_light()
+    room(b, light_L=(4, 4, 4))
+    b.material_matte(b.texture_checkerboard((0.8, 0.2, 0.2), (0.2, 0.8, 0.2), uscale=4.0, vscale=4.0))
+    scenes._quad(b, (-1.5, -1.2, 1.0), (-0.3, -1.2, 1.0), (-0.3, -1.2, -0.4), (-1.5, -1.2, -0.4))
+    b.material_plastic(Kd=(0.3, 0.4, 0.5), Ks=(0.3, 0.3, 0.3), roughness=0.2)
+    scenes._quad(b, (0.2, -1.0, 1.0), (1.5, -1.0, 1.0), (1.5, -1.0, -0.4), (0.2, -1.0, -0.4))
+    b.material_mirror()
+    scenes._quad(b, (-0.8, -0.6, 1.8), (0.8, -0.6, 1.8), (0.8, 0.9, 1.8), (-0.8, 0.9, 1.8))
+    return b.build()
+
+
 def scene_roughness_textures(res=48, spp=8, depth=6, sampler="sobol"):
     """Float textures behind "roughness" / "uroughness" / "vroughness" / "eta" (ABI 6): evaluated at every hit, roughness through
     roughness_to_alpha's `ln` on the device (plastic.rs:57-62, glass.rs:57-81, metal.rs:58-69, uber.rs:66,96-104,

@@ -2,6 +2,7 @@
 need special builds or sizes: the HBM stack spill, the one-leaf scene, and BASELINE sizes."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -626,6 +627,58 @@ def test_far_traversal_kernel_changes_nothing(oracle, monkeypatch, name, make, m
         osc.close()
     finally:
         ctx.close()
+
+
+LOCAL_SORT_SCENES = {
+    "textures": lambda: fs.scene_textures(),
+    "sphere_lit_mixed": lambda: fs.scene_sphere_lit_mixed(),
+    # textured and WITHOUT an analytic shape: the scenes whose local sort had kernels of its own (a texture half and a shading half over the
+    # whole queue) before those were retired
+    "textured_triangles": lambda: _textured_triangles(),
+}
+
+
+def _textured_triangles():
+    b = fs.base()
+    fs.room(b)
+    b.material_matte(b.texture_checkerboard((0.8, 0.2, 0.2), (0.2, 0.8, 0.2), uscale=4.0, vscale=4.0))
+    scenes._quad(b, (-1.5, -1.2, 1.0), (-0.3, -1.2, 1.0), (-0.3, -1.2, -0.4), (-1.5, -1.2, -0.4))
+    b.material_plastic(Kd=(0.3, 0.4, 0.5), Ks=(0.3, 0.3, 0.3), roughness=0.2)
+    scenes._quad(b, (0.2, -1.0, 1.0), (1.5, -1.0, 1.0), (1.5, -1.0, -0.4), (0.2, -1.0, -0.4))
+    return b.build()
+
+
+def _radiance_samples(sd):
+    ctx = pkg.Context(0)
+    try:
+        info = ctx.upload(sd)
+        return ctx.radiance_samples(tuple(info.sample_bounds))
+    finally:
+        ctx.close()
+
+
+LOCAL_SORT_SCRIPT = r"""
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import test_gpu_features as t
+np.savez(sys.argv[2], **{name: t._radiance_samples(make()) for name, make in t.LOCAL_SORT_SCENES.items()})
+"""
+
+
+def test_local_sort_switch_keeps_textured_scenes_on_the_sorted_path(tmp_path):
+    """PBRTGPU_SHADE_LOCAL=1 asks for the local material sort wherever possible.  For a scene with textured materials it is not: the textured
+    segment needs a list of its own (k_tex_resolve, k_shade_general_res), so such a scene takes the global sort whatever the variable says --
+    with or without analytic shapes, with a sphere light, with constant lobe-list materials next to the textured ones.  Every camera sample
+    of a fresh process that runs under the variable is the default render's, bit for bit."""
+    out = str(tmp_path / "r.npz")
+    r = subprocess.run([sys.executable, "-c", LOCAL_SORT_SCRIPT, ROOT, out], env=dict(os.environ, PBRTGPU_SHADE_LOCAL="1"), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = np.load(out)
+    for name, make in LOCAL_SORT_SCENES.items():
+        base = _radiance_samples(make())
+        assert base.any(), name
+        assert np.array_equal(got[name], base), name
 
 
 def test_crown_class_3p5m_textured_tiles(gpu_ctx, oracle):

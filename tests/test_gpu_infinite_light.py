@@ -400,7 +400,7 @@ np.save(sys.argv[2], a)
 @pytest.mark.parametrize("family", ["textured", "general"])
 def test_switches_are_routed_around(tmp_path, family):
     base, _ = render_samples(equivalence_scene(True, family, "spatial", extra_light=True))
-    env = dict(os.environ, PBRTGPU_SHADE_LOCAL="1", PBRTGPU_TEX_SPLIT="0", PBRTGPU_NEE_SPLIT="15", PBRTGPU_TRACE_FAR="1", PBRTGPU_SHADE_UNSORTED="1")
+    env = dict(os.environ, PBRTGPU_SHADE_LOCAL="1", PBRTGPU_TRACE_FAR="1")
     out = str(tmp_path / "r.npy")
     r = subprocess.run([sys.executable, "-c", SWITCH_SCRIPT, ROOT, out, family], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]

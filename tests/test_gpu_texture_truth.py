@@ -11,7 +11,7 @@ Which kernels evaluate Kr, as the launch code reads (pt_kernels.hip, ptk_shade a
     `directlighting` do.  These rows never reach k_tex_resolve.
   * rows inside the closed box of emitters ("box"), in world space, under `path`: no infinite light and no instance, so the textured
     hits go through k_tex_resolve -- the instantiation with PT_TEXN(x) = x##_inl, __forceinline__, value buffer in LDS -- and
-    k_shade_general_res (k_tex_resolve_all and k_shade_all_res where the local sort is on).  Every texture has such a row (test_truth_rows_are_pairwise checks it).
+    k_shade_general_res.  Every texture has such a row (test_truth_rows_are_pairwise checks it).
   * box rows with the quad as an instance: k_shade_general_inst (__noinline__).
 The box rows run under `path` and `directlighting`: the reference's whitted integrator never adds the emission of a surface it hits.
 

@@ -189,25 +189,18 @@ def test_kernel_register_budgets():
         "k_shade_matte_sorted": (256, 0, 40960),
         "k_shade_general": (256, 0, 40960),
         "k_shade_general_inst_plain": (256, 0, 40960),   # scenes with instances and neither textures nor spheres: the lobe-list kernel + the instance-space reconstruction, nothing spilled
-        "k_shade_general_tex": (256, 140, 40960),    # the one-kernel form of the textured segment (PBRTGPU_TEX_SPLIT=0, scenes with instances)
+        "k_shade_all": (256, 0, 40960),              # the locally sorted queue's one kernel (the default for constant lobe-list materials): k_shade_general's figures
         "k_shade_general_res": (256, 0, 40960),      # the textured segment's shading half: nothing spilled
         "k_tex_resolve": (256, 32, 40960),           # ... and its texture half, the texture code inlined, the interpreter's node values in LDS: 28 registers spilled, 116 B of scratch
         "k_tex_resolve_sph": (256, 56, 40960),
         # The sphere-capable whole-vertex kernels (killeroo-class scenes) DO spill -- Sphere::sample_from and the EFloat quadratic are calls in the
-        # middle of next-event estimation.  Round 4 built the spill-free form (the vertex in two kernels, below) and measured it 6 % SLOWER on
-        # the killeroo-class line, so these stay the default; the budgets hold them where they are.
+        # middle of next-event estimation.  Round 4 built the spill-free form (the vertex in two kernels, since retired: tools/patches/README.md) and
+        # measured it 6 % SLOWER on the killeroo-class line, so these are the only form; the budgets hold them where they are.
         "k_shade_matte_sorted_sph": (256, 90, 40960),
         "k_shade_general_sph": (256, 64, 40960),
+        "k_shade_all_sph": (256, 64, 40960),         # k_shade_general_sph over the locally sorted queue
         "k_shade_general_res_sph": (256, 104, 40960),
         "k_shade_general_inst": (256, 150, 40960),   # scenes with object instances: one kernel shades everything (a breadth feature)
-        # the vertex in two kernels (PBRTGPU_NEE_SPLIT): no kernel of the family spills; the continuation halves of the triangle-only families fit three waves per SIMD
-        "k_shade_nee": (256, 0, 40960), "k_shade_cont": (168, 0, 16384),
-        "k_shade_matte_sorted_nee": (256, 0, 40960), "k_shade_matte_sorted_cont": (168, 0, 16384),
-        "k_shade_general_nee": (256, 0, 40960), "k_shade_general_cont": (168, 0, 16384),
-        "k_shade_general_res_nee": (256, 0, 40960), "k_shade_general_res_cont": (168, 0, 16384),
-        "k_shade_matte_sorted_sph_nee": (256, 0, 40960), "k_shade_matte_sorted_sph_cont": (256, 0, 16384),
-        "k_shade_general_sph_nee": (256, 0, 40960), "k_shade_general_sph_cont": (256, 0, 16384),
-        "k_shade_general_res_sph_nee": (256, 0, 40960), "k_shade_general_res_sph_cont": (256, 0, 16384),
         # the recursive integrators: the instantiation BASELINE's scenes run (no spheres, instances or textured materials) spills nothing;
         # the everything-compiled-in one keeps its per-hit lobe list in scratch
         "k_rec_enter_plain": (256, 0, 64), "k_rec_next_plain": (256, 0, 8192),

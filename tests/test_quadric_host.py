@@ -163,10 +163,7 @@ def test_second_kernel_set_register_budgets():
         "k_trace_sph_dist": (128, 0, 163840),
         "k_trace_sph": (168, 0, 32800), "k_trace_inst": (168, 48, 32800), "k_trace_batch_sph": (128, 0, 32800),
         "k_shade_matte_sorted_sph": (256, 70, 40960), "k_shade_general_sph": (256, 58, 40960), "k_shade_general_res_sph": (256, 89, 40960),
-        "k_shade_general_inst": (256, 176, 40960), "k_shade_general_tex": (256, 166, 40960), "k_tex_resolve_sph": (256, 23, 40960),
-        "k_shade_matte_sorted_sph_nee": (256, 0, 40960), "k_shade_matte_sorted_sph_cont": (256, 0, 16384),
-        "k_shade_general_sph_nee": (256, 0, 40960), "k_shade_general_sph_cont": (256, 0, 16384),
-        "k_shade_general_res_sph_nee": (256, 0, 40960), "k_shade_general_res_sph_cont": (256, 0, 16384),
+        "k_shade_general_inst": (256, 176, 40960), "k_tex_resolve_sph": (256, 23, 40960),
         "k_rec_enter": (256, 105, 64), "k_rec_next": (256, 118, 8192), "k_aov": (256, 0, 0), "k_ao_rays_sph": (256, 0, 0),
     }
     for name, (vgpr, spill, lds) in budgets.items():
