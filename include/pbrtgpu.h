@@ -130,13 +130,17 @@ typedef enum {
     PT_MATERIAL_SUBSTRATE = 7, /* materials/substrate.rs:34-68  Kd, Ks, uroughness, vroughness */
     PT_MATERIAL_TRANSLUCENT = 8,/* materials/translucent.rs:38-107  Kd, Ks, reflect (in kr / tex_kr), transmit (in kt / tex_kt), roughness,
                                  * remaproughness; eta is the constant 1.5 ("eta" / "index" are not read, translucent.rs:48) */
-    PT_MATERIAL_MIX = 9         /* materials/mix.rs:53-96: every BxDF of "namedmaterial1" scaled by s1 = clamp_zero(amount), then every BxDF of
+    PT_MATERIAL_MIX = 9,        /* materials/mix.rs:53-96: every BxDF of "namedmaterial1" scaled by s1 = clamp_zero(amount), then every BxDF of
                                  * "namedmaterial2" scaled by s2 = clamp_zero(1 - s1) (core/reflection/scaled.rs).  "amount" rides in kd / tex_kd
                                  * (default 0.5); the children ride as material index + 1 in tex_kr (namedmaterial1) and tex_kt (namedmaterial2),
                                  * which a mix does not otherwise read.  A child's index must be smaller than the mix's own (definition order: no
                                  * cycles, and a child may itself be a mix); anything else is PT_ERR_INVALID_ARGUMENT.  Every other field is
                                  * ignored: a mix has no bump map of its own, its shading frame and BSDF::eta are child 1's.  At most
                                  * PT_MIX_MAX_LEAVES leaves and PT_MIX_MAX_LOBES BxDFs per tree (PT_ERR_UNSUPPORTED beyond). */
+    PT_MATERIAL_DISNEY = 10     /* materials/disney.rs:644-841: "color" rides in kd / tex_kd, "eta" in eta / tex_eta, "roughness" in roughness /
+                                 * tex_roughness (never remapped), "bumpmap" in tex_bump; every other parameter rides in a pt_disney record
+                                 * (pt_scene_set_disney), and a material without one takes create_disney_material's defaults.  Up to eight
+                                 * BxDFs; usable as a child of a mix. */
 } pt_material_type;
 
 #define PT_MIX_MAX_LEAVES 4          /* leaf materials under one mix tree */
@@ -233,6 +237,33 @@ typedef struct {
     int32_t shadow_texture;
     uint32_t reserved[5];
 } pt_alpha_mask;
+
+/* Material "disney" (src/materials/disney.rs): the parameters of a PT_MATERIAL_DISNEY material that pt_material has no field for.
+ * value[k] / tex[k] are indexed by PT_DISNEY_*; tex[k] is index + 1 of the float texture that drives the parameter at each hit, 0 = the
+ * constant value[k].  Defaults (create_disney_material, disney.rs:806-841): metallic 0, speculartint 0, anisotropic 0, sheen 0,
+ * sheentint 0.5, clearcoat 0, clearcoatgloss 1, spectrans 0, flatness 0, difftrans 1, thin false, scatterdistance 0.  A non-black
+ * "scatterdistance" (or a texture behind it) on a material that is not thin is PT_ERR_UNSUPPORTED: the reference stops at a todo!()
+ * there (disney.rs:712); with thin set the parameter is never evaluated and is ignored.  Passed with pt_scene_set_disney, not in
+ * pt_scene_desc.  128 bytes. */
+#define PT_DISNEY_METALLIC        0
+#define PT_DISNEY_SPECULARTINT    1
+#define PT_DISNEY_ANISOTROPIC     2
+#define PT_DISNEY_SHEEN           3
+#define PT_DISNEY_SHEENTINT       4
+#define PT_DISNEY_CLEARCOAT       5
+#define PT_DISNEY_CLEARCOATGLOSS  6
+#define PT_DISNEY_SPECTRANS       7
+#define PT_DISNEY_FLATNESS        8
+#define PT_DISNEY_DIFFTRANS       9
+typedef struct {
+    uint32_t material;          /* index into pt_scene_desc.materials: a PT_MATERIAL_DISNEY material */
+    float value[10];            /* by PT_DISNEY_* */
+    uint32_t tex[10];           /* by PT_DISNEY_*: index + 1 of a float texture, 0 = constant */
+    int32_t thin;               /* "thin" */
+    float scatterdistance[3];   /* "scatterdistance" */
+    uint32_t tex_scatterdistance; /* index + 1 of its texture, 0 = constant */
+    uint32_t reserved[6];
+} pt_disney;
 
 /* TriangleMesh flags (src/shapes/triangle.rs:10-22). */
 #define PT_MESH_TWO_SIDED            1u  /* "twosided" shape param, default true (triangle.rs:707) */
@@ -452,6 +483,11 @@ pt_status pt_scene_set_delta_lights(pt_context* ctx, uint32_t n, const pt_delta_
  * per mesh.  A bad mesh or texture index, or a texture that is not a float texture, fails the upload with PT_ERR_INVALID_ARGUMENT.  A
  * scene with a mask traces every ray with k_trace_alpha (k_trace_batch_alpha for the trace hooks). */
 pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_mask* masks);
+/* The pt_disney records of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the infinite lights.  At most one
+ * record per material.  A bad material or texture index, a record for a material that is not PT_MATERIAL_DISNEY, or a colour texture
+ * where a float texture belongs fails the upload with PT_ERR_INVALID_ARGUMENT.  A scene that holds a Disney material runs the *_mix
+ * kernels of the build that knows Disney's BxDFs (pt_kernels_disney.hip); every other scene launches what it launched before. */
+pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* records);
 /* Integrator "aov": the target (a pt_aov_target) and the scale of the NEXT pt_scene_upload only, consumed like the infinite lights; read
  * when that upload's integrator is PT_INTEGRATOR_AOV.  Not called: target uv, scale 1 (create_aov_integrator's defaults, aov.rs:200-201).
  * A target outside the enum is PT_ERR_INVALID_ARGUMENT. */

@@ -62,11 +62,15 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
  * pth_options.delta_lights, for the same reason (a test pins the refusal of the plain entry points), and it goes away with it.
  * PTH_FEATURE_DELTA_LIGHTS: what pth_options.delta_lights != 0 does; the old field keeps working.
  * PTH_FEATURE_QUADRIC_SHAPES: Shape "cylinder" and Shape "disk" become pt_sphere records of kind PT_SHAPE_CYLINDER / PT_SHAPE_DISK (a
- * cylinder of radius 0 is skipped with a warning); without the bit they are refused as before, with the same message.  pbrt_gpu sets
- * all three. */
+ * cylinder of radius 0 is skipped with a warning); without the bit they are refused as before, with the same message.
+ * PTH_FEATURE_DISNEY_MATERIAL: Material "disney" and the MakeNamedMaterial type "disney" (also as a child of a mix) become
+ * PT_MATERIAL_DISNEY records with one pt_disney record each (pth_scene_get_disney); without the bit they are refused as before, with the
+ * same message.  Non-black "scatterdistance" without "thin", and a colour texture behind a float parameter, are refused.  pbrt_gpu sets
+ * all four. */
 #define PTH_FEATURE_MIX_MATERIAL 1u
 #define PTH_FEATURE_DELTA_LIGHTS 2u
 #define PTH_FEATURE_QUADRIC_SHAPES 4u
+#define PTH_FEATURE_DISNEY_MATERIAL 8u
 pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
@@ -82,6 +86,8 @@ const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint3
 const pt_delta_light* pth_scene_get_delta_lights(const pth_scene* s, uint32_t* n);
 /* The scene's alpha-masked meshes (for pt_scene_set_alpha_masks); *n receives their count.  Valid until pth_scene_free. */
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
+/* The scene's Material "disney" records (for pt_scene_set_disney); *n receives their count.  Valid until pth_scene_free. */
+const pt_disney* pth_scene_get_disney(const pth_scene* s, uint32_t* n);
 /* Integrator "aov": its "target" (a pt_aov_target, default uv) and "scale" (default 1), for pt_scene_set_aov.  Other integrators: the defaults. */
 void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale);
 /* Film "filename" parameter (default "pbrt.exr"). */

@@ -15,8 +15,11 @@ PT_MATERIAL_NONE, PT_MATERIAL_MATTE, PT_MATERIAL_PLASTIC, PT_MATERIAL_MIRROR = 0
 PT_MATERIAL_GLASS, PT_MATERIAL_METAL, PT_MATERIAL_UBER, PT_MATERIAL_SUBSTRATE = 4, 5, 6, 7
 PT_MATERIAL_TRANSLUCENT = 8
 PT_MATERIAL_MIX = 9
+PT_MATERIAL_DISNEY = 10
+(PT_DISNEY_METALLIC, PT_DISNEY_SPECULARTINT, PT_DISNEY_ANISOTROPIC, PT_DISNEY_SHEEN, PT_DISNEY_SHEENTINT, PT_DISNEY_CLEARCOAT,
+ PT_DISNEY_CLEARCOATGLOSS, PT_DISNEY_SPECTRANS, PT_DISNEY_FLATNESS, PT_DISNEY_DIFFTRANS) = range(10)
 PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
-PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES = 1, 2, 4
+PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES, PTH_FEATURE_DISNEY_MATERIAL = 1, 2, 4, 8
 PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER, PT_SHAPE_DISK = 0, 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
@@ -90,6 +93,12 @@ PT_ALPHA_NONE, PT_ALPHA_CONSTANT, PT_ALPHA_TEXTURE = range(3)
 class pt_alpha_mask(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("alpha_kind", C.c_int32), ("alpha_value", C.c_float), ("alpha_texture", C.c_int32),
                 ("shadow_kind", C.c_int32), ("shadow_value", C.c_float), ("shadow_texture", C.c_int32), ("reserved", C.c_uint32 * 5)]
+
+
+class pt_disney(C.Structure):
+    """Material "disney": what pt_material has no field for (value / tex by PT_DISNEY_*)."""
+    _fields_ = [("material", C.c_uint32), ("value", C.c_float * 10), ("tex", C.c_uint32 * 10), ("thin", C.c_int32),
+                ("scatterdistance", C.c_float * 3), ("tex_scatterdistance", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
 class pt_mesh(C.Structure):
@@ -183,7 +192,7 @@ SYMBOLS = [
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_pdf_from", "pt_light_le", "pt_scene_set_alpha_masks",
-    "pt_scene_set_aov", "pt_scene_set_delta_lights",
+    "pt_scene_set_aov", "pt_scene_set_delta_lights", "pt_scene_set_disney",
 ]
 
 _lib = None
@@ -249,7 +258,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_parse_string_opts", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_parse_file_features", "pth_parse_string_features",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_parse_file_features", "pth_parse_string_features",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
@@ -261,10 +270,12 @@ class ParsedScene:
     """A scene parsed from .pbrt text by the C++ front end (include/pbrtgpu_host.h).  Quacks like
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
-    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False):
+    def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False,
+                 disney_materials=False):
         """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
         mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before.
-        quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before."""
+        quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before.
+        disney_materials: take Material "disney" (PTH_FEATURE_DISNEY_MATERIAL, the same way); off, it is refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -284,11 +295,11 @@ class ParsedScene:
         opts = pth_options(0, 0, 0, 1)
         feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         features = (PTH_FEATURE_MIX_MATERIAL if mix_materials else 0) | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0) | \
-                   (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0)
-        if (mix_materials or quadric_shapes) and filename is not None:
+                   (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0) | (PTH_FEATURE_DISNEY_MATERIAL if disney_materials else 0)
+        if (mix_materials or quadric_shapes or disney_materials) and filename is not None:
             L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
             st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
-        elif mix_materials or quadric_shapes:
+        elif mix_materials or quadric_shapes or disney_materials:
             L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
             st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
         elif filename is not None and delta_lights:
@@ -320,6 +331,11 @@ class ParsedScene:
         n_am = C.c_uint32()
         am = L.pth_scene_get_alpha_masks(self.h, C.byref(n_am))
         self.alpha_masks = [pt_alpha_mask.from_buffer_copy(am[i]) for i in range(n_am.value)]      # "alpha" / "shadowalpha" of the meshes (copies)
+        L.pth_scene_get_disney.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.pth_scene_get_disney.restype = C.POINTER(pt_disney)
+        n_dis = C.c_uint32()
+        dis = L.pth_scene_get_disney(self.h, C.byref(n_dis))
+        self.disney = [pt_disney.from_buffer_copy(dis[i]) for i in range(n_dis.value)]      # Material "disney" records (copies)
         L.pth_scene_get_aov.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         L.pth_scene_get_aov.restype = None
         tgt, scl = C.c_int32(), C.c_float()
@@ -502,6 +518,11 @@ class Context:
         am = list(getattr(scene, "alpha_masks", None) or [])
         am_arr = (pt_alpha_mask * max(1, len(am)))(*am)
         self._check(self.lib.pt_scene_set_alpha_masks(self.h, C.c_uint32(len(am)), am_arr if am else None))
+        dis = list(getattr(scene, "disney", None) or [])
+        if dis:                      # Material "disney" records (an upload consumes them, so a scene without any has nothing to clear)
+            dis_arr = (pt_disney * len(dis))(*dis)
+            self.lib.pt_scene_set_disney.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_disney)]
+            self._check(self.lib.pt_scene_set_disney(self.h, C.c_uint32(len(dis)), dis_arr))
         aov = getattr(scene, "aov", None)
         if aov is not None:          # Integrator "aov": (target, scale); otherwise the upload takes the defaults (uv, 1)
             self._check(self.lib.pt_scene_set_aov(self.h, C.c_int32(int(aov[0])), C.c_float(float(aov[1]))))

@@ -143,11 +143,31 @@ PT_DEV V3 fr_conductor(float cos_theta_i, V3 eta_t, V3 k) {     // eta_i = 1 (me
     V3 rp = rgb_div(rs * (t3 - t4), t3 + t4);
     return (rp + rs) * 0.5f;
 }
+#if PT_DISNEY
+// ---- materials/disney.rs:17-39, :330-345.  Compiled into the kernels of pt_kernels_disney.hip only: every other build keeps the text below as it was.
+PT_DEV float schlick_weight(float cos_theta) {
+    float m = clampf(1.0f - cos_theta, 0.0f, 1.0f);
+    return m * m * m * m * m;
+}
+PT_DEV V3 fr_disney(V3 r0, float metallic, float eta, float cos_i) {           // DisneyFresnel::evaluate
+    float r0e = ((eta - 1.0f) * (eta - 1.0f)) / ((eta + 1.0f) * (eta + 1.0f));                 // schlick_r0_from_eta
+    float g = lerpf(metallic, r0e, lum_y(r0));
+    return r0 + (rgb1(g) - r0) * schlick_weight(cos_i);
+}
+PT_DEV V3 lobe_fresnel(const PtLobe& l, float cos_i) {
+    const uint32_t fr = l.fresnel & PT_FR_MASK;
+    if (fr == PT_FR_DIELECTRIC) return rgb1(fr_dielectric(cos_i, l.fr_eta_i, l.fr_eta_t));
+    if (fr == PT_FR_CONDUCTOR) return fr_conductor(fabsf(cos_i), ld3(l.t), ld3(l.k));
+    if (fr == PT_FR_DISNEY) return fr_disney(ld3(l.t), l.fr_eta_i, l.fr_eta_t, cos_i);
+    return rgb1(1.0f);
+}
+#else
 PT_DEV V3 lobe_fresnel(const PtLobe& l, float cos_i) {
     if (l.fresnel == PT_FR_DIELECTRIC) return rgb1(fr_dielectric(cos_i, l.fr_eta_i, l.fr_eta_t));
     if (l.fresnel == PT_FR_CONDUCTOR) return fr_conductor(fabsf(cos_i), ld3(l.t), ld3(l.k));
     return rgb1(1.0f);
 }
+#endif
 
 // ---- TrowbridgeReitzDistribution (trowbridge_reitz.rs:7-98, :145-221)
 PT_DEV float tr_d(float ax, float ay, V3 wh) {
@@ -215,6 +235,171 @@ PT_DEV V3 tr_sample_wh(float ax, float ay, V3 wo, V2 u) {
 // ---- the lobes
 PT_DEV bool lobe_matches(const PtLobe& l, uint32_t flags) { return (l.type & flags) == l.type; }
 
+// MicrofacetDistribution::g of a microfacet lobe: the height-correlated form, or for DisneyMicrofacetDistribution the separable one
+#if PT_DISNEY
+PT_DEV float lobe_g(const PtLobe& l, V3 wo, V3 wi) {
+    if (l.fresnel & PT_LOBE_G_SEPARABLE) return tr_g1(l.ax, l.ay, wo) * tr_g1(l.ax, l.ay, wi);
+    return tr_g(l.ax, l.ay, wo, wi);
+}
+#else
+#define lobe_g(l, wo, wi) tr_g((l).ax, (l).ay, wo, wi)
+#endif
+
+#if PT_DISNEY
+// ---- powf(x, y) as glibc computes it (sysdeps/ieee754/flt-32/e_powf.c, FMA build): pt_pow5 above with y as a variable -- the same log2
+// table and polynomial, y * log2(x) in double, the same exp2.  checkint: 0 y is no integer, 1 odd, 2 even.
+PT_DEV int pt_powf_checkint(uint32_t iy) {
+    int e = (int)((iy >> 23) & 0xffu);
+    if (e < 0x7f) return 0;
+    if (e > 0x7f + 23) return 2;
+    if (iy & ((1u << (0x7f + 23 - e)) - 1u)) return 0;
+    if (iy & (1u << (0x7f + 23 - e))) return 1;
+    return 2;
+}
+PT_DEV bool pt_powf_zeroinfnan(uint32_t ix) { return 2u * ix - 1u >= 2u * 0x7f800000u - 1u; }
+PT_DEV float pt_powf(float x, float y) {
+    uint32_t ix = __float_as_uint(x), iy = __float_as_uint(y), sign_bias = 0;
+    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u || pt_powf_zeroinfnan(iy)) {
+        if (pt_powf_zeroinfnan(iy)) {
+            if (2u * iy == 0u) return 1.0f;
+            if (ix == 0x3f800000u) return 1.0f;
+            if (2u * ix > 2u * 0x7f800000u || 2u * iy > 2u * 0x7f800000u) return x + y;
+            if (2u * ix == 2u * 0x3f800000u) return 1.0f;
+            if ((2u * ix < 2u * 0x3f800000u) == !(iy & 0x80000000u)) return 0.0f;
+            return y * y;
+        }
+        if (pt_powf_zeroinfnan(ix)) {
+            float x2 = x * x;
+            if ((ix & 0x80000000u) && pt_powf_checkint(iy) == 1) { x2 = -x2; sign_bias = 1; }
+            if (2u * ix == 0u && (iy & 0x80000000u)) return sign_bias ? -PT_INF : PT_INF;
+            return (iy & 0x80000000u) ? 1.0f / x2 : x2;
+        }
+        if (ix & 0x80000000u) {
+            int yint = pt_powf_checkint(iy);
+            if (yint == 0) return __uint_as_float(0x7fc00000u);
+            if (yint == 1) sign_bias = 1u << 16;
+            ix &= 0x7fffffffu;
+        }
+        if (ix < 0x00800000u) {
+            ix = __float_as_uint(x * 0x1p23f);
+            ix &= 0x7fffffffu;
+            ix -= 23u << 23;
+        }
+    }
+    uint32_t tmp = ix - 0x3f330000u;
+    uint32_t i = (tmp >> 19) & 15u;
+    uint32_t top = tmp & 0xff800000u;
+    int k = (int32_t)top >> 23;
+    double z = (double)__uint_as_float(ix - top);
+    double r = __builtin_fma(z, pt_powf_log2_tab[i][0], -1.0);
+    double y0 = pt_powf_log2_tab[i][1] + (double)k;
+    double r2 = r * r;
+    double yl = __builtin_fma(0x1.27616c9496e0bp-2, r, -0x1.71969a075c67ap-2);
+    double p = __builtin_fma(0x1.ec70a6ca7baddp-2, r, -0x1.7154748bef6c8p-1);
+    double r4 = r2 * r2;
+    double q = __builtin_fma(0x1.71547652ab82bp+0, r, y0);
+    q = __builtin_fma(p, r2, q);
+    yl = __builtin_fma(yl, r4, q);
+    double ylogx = (double)y * yl;
+    if ((((unsigned long long)__double_as_longlong(ylogx) >> 47) & 0xffffull) >= (0x405f800000000000ull >> 47)) {   // |y log2 x| >= 126
+        if (ylogx > 0x1.fffffffd1d571p+6) return sign_bias ? -PT_INF : PT_INF;
+        if (ylogx <= -150.0) return sign_bias ? -0.0f : 0.0f;
+    }
+    double kd = ylogx + 0x1.8p+47;
+    unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
+    kd -= 0x1.8p+47;
+    double rr = ylogx - kd;
+    unsigned long long t = pt_exp2f_tab[ki & 31u];
+    t += (ki + sign_bias) << 47;
+    double s = __longlong_as_double((long long)t);
+    double zz = __builtin_fma(0x1.c6af84b912394p-5, rr, 0x1.ebfce50fac4f3p-3);
+    double rr2 = rr * rr;
+    double yy = __builtin_fma(0x1.62e42ff0c52d6p-1, rr, 1.0);
+    yy = __builtin_fma(zz, rr2, yy);
+    yy = yy * s;
+    return (float)yy;
+}
+
+// ---- the BxDFs of Material "disney" (materials/disney.rs:44-323), as callees of globe_f / globe_pdf / globe_sample_f
+PT_DEV float disney_gtr1(float cos_theta, float alpha) {                       // :238-242
+    float alpha2 = alpha * alpha;
+    float cos_theta2 = cos_theta * cos_theta;
+    return (alpha2 - 1.0f) / (PT_PI * pt_logf(alpha2) * (1.0f + (alpha2 - 1.0f) * cos_theta2));
+}
+PT_DEV float disney_smith_g_ggx(float cos_theta, float alpha) {                // :246-250
+    float alpha2 = alpha * alpha;
+    float cos_theta2 = cos_theta * cos_theta;
+    return 1.0f / (cos_theta + sqrtf(alpha2 + cos_theta2 - alpha2 * cos_theta2));
+}
+__device__ __noinline__ V3 disney_f(const PtLobe& l, V3 wo, V3 wi) {
+    const V3 zero = mk3(0.0f, 0.0f, 0.0f);
+    if (l.kind == PT_LOBE_DISNEY_DIFFUSE) {                                     // :53-60
+        float fo = schlick_weight(fabsf(wo.z)), fi = schlick_weight(fabsf(wi.z));
+        return ld3(l.r) * PT_INV_PI * (1.0f - fo / 2.0f) * (1.0f - fi / 2.0f);
+    }
+    V3 wh = wo + wi;
+    if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return zero;
+    wh = normalize(wh);
+    switch (l.kind) {
+        case PT_LOBE_DISNEY_FAKE_SS: {                                          // :95-110
+            float cos_theta_d = dot(wi, wh);
+            float fss90 = cos_theta_d * cos_theta_d * l.oa;
+            float fo = schlick_weight(fabsf(wo.z)), fi = schlick_weight(fabsf(wi.z));
+            float fss = lerpf(fo, 1.0f, fss90) * lerpf(fi, 1.0f, fss90);
+            float ss = 1.25f * fss * (1.0f / (fabsf(wo.z) + fabsf(wi.z)) - 0.5f);
+            return ld3(l.r) * PT_INV_PI * ss;
+        }
+        case PT_LOBE_DISNEY_RETRO: {                                            // :145-159
+            float cos_theta_d = dot(wi, wh);
+            float fo = schlick_weight(fabsf(wo.z)), fi = schlick_weight(fabsf(wi.z));
+            float rr = 2.0f * l.oa * cos_theta_d * cos_theta_d;
+            return ld3(l.r) * PT_INV_PI * rr * (fo + fi + fo * fi * (rr - 1.0f));
+        }
+        case PT_LOBE_DISNEY_SHEEN: return ld3(l.r) * schlick_weight(dot(wi, wh));          // :193-202
+        case PT_LOBE_DISNEY_CLEARCOAT: {                                        // :253-268
+            float dr = disney_gtr1(fabsf(wh.z), l.ob);
+            float fr = lerpf(schlick_weight(dot(wo, wh)), 0.04f, 1.0f);         // fr_schlick(0.04, .)
+            float gr = disney_smith_g_ggx(fabsf(wo.z), 0.25f) * disney_smith_g_ggx(fabsf(wi.z), 0.25f);
+            return rgb1(l.oa * gr * fr * dr / 4.0f);
+        }
+        default: return zero;
+    }
+}
+__device__ __noinline__ float disney_pdf(const PtLobe& l, V3 wo, V3 wi) {
+    if (l.kind == PT_LOBE_DISNEY_DIFFUSE) return 0.0f;                          // :74-76: it adds nothing to the averaged pdf, and a pick of it samples nothing
+    if (!bx_same_hemisphere(wo, wi)) return 0.0f;
+    if (l.kind != PT_LOBE_DISNEY_CLEARCOAT) return fabsf(wi.z) * PT_INV_PI;     // pdf_default (bxdf.rs:88-94)
+    V3 wh = wo + wi;                                                            // :303-319
+    if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return 0.0f;
+    wh = normalize(wh);
+    float dr = disney_gtr1(fabsf(wh.z), l.ob);
+    return dr + fabsf(wh.z) / (4.0f * fabsf(wo.z));                             // a sum, as the text has it
+}
+__device__ __noinline__ bool disney_sample_f(const PtLobe& l, V3 wo, V2 u, V3* f, V3* wi_out, float* pdf) {
+    V3 wi;
+    if (l.kind != PT_LOBE_DISNEY_CLEARCOAT) {                                   // sample_f_default (bxdf.rs:74-86)
+        wi = cosine_sample_hemisphere(u);
+        if (wo.z < 0.0f) wi.z *= -1.0f;
+    } else {                                                                    // :269-300
+        if (wo.z == 0.0f) return false;
+        float alpha2 = l.ob * l.ob;
+        float cos_theta = sqrtf(fmaxf(0.0f, 1.0f - pt_powf(alpha2, 1.0f - u.x) / (1.0f - alpha2)));
+        float sin_theta = sqrtf(fmaxf(0.0f, 1.0f - cos_theta * cos_theta));
+        float phi = 2.0f * PT_PI * u.y;
+        float sin_p, cos_p;
+        pt_sincosf(phi, &sin_p, &cos_p);
+        V3 wh = mk3(sin_theta * cos_p, sin_theta * sin_p, cos_theta);
+        if (!bx_same_hemisphere(wo, wh)) wh = -wh;
+        wi = bx_reflect(wo, wh);
+        if (!bx_same_hemisphere(wo, wi)) return false;
+    }
+    *pdf = disney_pdf(l, wo, wi);
+    *f = disney_f(l, wo, wi);
+    *wi_out = wi;
+    return true;                        // (a pdf that is not positive is turned away by the caller, bsdf.rs:149-152)
+}
+#endif
+
 __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
     const V3 zero = mk3(0.0f, 0.0f, 0.0f);
     switch (l.kind) {
@@ -238,7 +423,7 @@ __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
             if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return zero;
             wh = normalize(wh);
             V3 f = lobe_fresnel(l, dot(wi, face_forward(wh, mk3(0.0f, 0.0f, 1.0f))));
-            return ld3(l.r) * f * (tr_d(l.ax, l.ay, wh) * tr_g(l.ax, l.ay, wo, wi) / (4.0f * cos_i * cos_o));
+            return ld3(l.r) * f * (tr_d(l.ax, l.ay, wh) * lobe_g(l, wo, wi) / (4.0f * cos_i * cos_o));
         }
         case PT_LOBE_MF_TRANS: {
             if (bx_same_hemisphere(wo, wi)) return zero;
@@ -252,7 +437,7 @@ __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
             V3 f = rgb1(fr_dielectric(dot(wo, wh), l.eta_a, l.eta_b));
             float sqrt_denom = wo_wh + eta * wi_wh;
             float factor = 1.0f / eta;
-            float d = fabsf(tr_d(l.ax, l.ay, wh) * tr_g(l.ax, l.ay, wo, wi) * eta * eta * abs_dot(wi, wh) * abs_dot(wo, wh) * factor * factor /
+            float d = fabsf(tr_d(l.ax, l.ay, wh) * lobe_g(l, wo, wi) * eta * eta * abs_dot(wi, wh) * abs_dot(wo, wh) * factor * factor /
                             (cos_i * cos_o * sqrt_denom * sqrt_denom));
             return ((rgb1(1.0f) - f) * ld3(l.r)) * d;
         }
@@ -267,7 +452,11 @@ __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
             V3 specular = schlick * (tr_d(l.ax, l.ay, wh) / (4.0f * abs_dot(wi, wh) * fmaxf(fabsf(wi.z), fabsf(wo.z))));
             return diffuse + specular;
         }
+#if PT_DISNEY
+        default: return disney_f(l, wo, wi);
+#else
         default: return zero;
+#endif
     }
 }
 
@@ -301,7 +490,11 @@ __device__ __noinline__ float globe_pdf(const PtLobe& l, V3 wo, V3 wi) {
             float pdf_wh = tr_pdf(l.ax, l.ay, wo, wh);
             return 0.5f * (fabsf(wi.z) * PT_INV_PI + pdf_wh / (4.0f * dot(wo, wh)));
         }
+#if PT_DISNEY
+        default: return disney_pdf(l, wo, wi);
+#else
         default: return 0.0f;
+#endif
     }
 }
 
@@ -405,7 +598,11 @@ __device__ __noinline__ bool globe_sample_f(const PtLobe& l, V3 wo, V2 u, V3* f,
             *wi_out = wi;
             return true;
         }
+#if PT_DISNEY
+        default: return disney_sample_f(l, wo, u, f, wi_out, pdf);
+#else
         default: return false;
+#endif
     }
 }
 

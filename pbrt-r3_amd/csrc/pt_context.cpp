@@ -69,11 +69,13 @@ struct pt_context {
     std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
     std::vector<pt_delta_light> delta_lights;       // pt_scene_set_delta_lights: the next upload's point / spot / distant lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
+    std::vector<pt_disney> disney_recs;             // pt_scene_set_disney: the next upload's Disney parameter records
     int32_t next_aov_target = PT_AOV_UV;            // pt_scene_set_aov: the next upload's AOV target and scale (create_aov_integrator's defaults)
     float next_aov_scale = 1.0f;
     int32_t aov_target = PT_AOV_UV;                 // of the uploaded scene (read when its integrator is PT_INTEGRATOR_AOV)
     float aov_scale = 1.0f;
     bool quadric_kernels = false;                   // the uploaded scene holds a cylinder or a disk: it runs the kernels of namespace ptq (pt_kernels_quadric.hip)
+    bool disney_kernels = false;                    // the uploaded scene holds a Material "disney": it runs the kernels of namespace ptd (pt_kernels_disney.hip)
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
@@ -81,7 +83,8 @@ struct pt_context {
     std::vector<uint64_t> sobol_vdc, sobol_inv;
     uint32_t sobol_n_vdc = 0, sobol_n_inv = 0, sobol_msize = 52;
     uint32_t n_materials = 0;
-    std::vector<uint8_t> mix_per_hit;               // per material: 1 for a "mix" whose lobes are built at every hit (the BSDF hooks refuse it)
+    std::vector<uint8_t> per_hit_lobes;             // per material, what the BSDF hooks refuse: PER_HIT_MIX a "mix", PER_HIT_DISNEY a "disney" whose lobes are built at every hit
+    enum { PER_HIT_NONE = 0, PER_HIT_MIX = 1, PER_HIT_DISNEY = 2 };
     uint32_t max_stack = 1;
     uint32_t film_w = 0, film_h = 0;
     int bvh_build_where = PT_BVH_BUILD_AUTO;
@@ -150,10 +153,12 @@ struct pt_context {
 };
 
 // The launchers whose kernels hold analytic-shape code (traversal, surface reconstruction, light sampling), by the scene: a cylinder or a disk asks for the second build of the kernels
-// (namespace ptq, pt_kernels_quadric.hip), every other scene runs the first.
+// (namespace ptq, pt_kernels_quadric.hip), every other scene runs the first.  A scene that holds a Material "disney" runs the third build (namespace ptd,
+// pt_kernels_disney.hip), which knows both the shapes and Disney's BxDFs.
 #define PTK_BY_SCENE(fn)                                                                                            \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->disney_kernels) return ptd::fn(std::forward<A>(a)...);                                             \
         return ctx->quadric_kernels ? ptq::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                 \
     }
 PTK_BY_SCENE(ptk_light_grid)
@@ -172,6 +177,15 @@ PTK_BY_SCENE(ptk_wavefront_results)
 PTK_BY_SCENE(ptk_light_hooks)
 PTK_BY_SCENE(ptk_light_pdf_from)
 #undef PTK_BY_SCENE
+// The BSDF hooks hold no analytic-shape code: the first build serves every scene but a Disney one
+#define PTK_BY_MATERIAL(fn)                                                                                         \
+    template <class... A>                                                                                           \
+    static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        return ctx->disney_kernels ? ptd::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                  \
+    }
+PTK_BY_MATERIAL(ptk_bsdf_eval)
+PTK_BY_MATERIAL(ptk_bsdf_sample)
+#undef PTK_BY_MATERIAL
 
 #define PT_HIP(call)                                             \
     do {                                                         \
@@ -599,6 +613,12 @@ pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_m
     return PT_OK;
 }
 
+pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* records) {
+    if (!ctx || (n && !records)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->disney_recs.assign(records, records + n);
+    return PT_OK;
+}
+
 pt_status pt_scene_set_aov(pt_context* ctx, int32_t target, float scale) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     if (target < PT_AOV_DISTANCE || target > PT_AOV_DPDVS) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown AOV target");
@@ -616,6 +636,7 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     ctx->inf_lights.clear();
     ctx->delta_lights.clear();
     ctx->alpha_masks.clear();
+    ctx->disney_recs.clear();
     ctx->next_aov_target = PT_AOV_UV;
     ctx->next_aov_scale = 1.0f;
     return st;
@@ -662,7 +683,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         if (d->meshes[m].area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "area light index out of range");
 
         int32_t mi = d->meshes[m].material;
-        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_MIX))
+        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_DISNEY))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
     }
     for (uint32_t i = 0; i < d->n_materials; i++) {
@@ -703,7 +724,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         const std::string shape = sp.kind == PT_SHAPE_CYLINDER ? "cylinder" : (sp.kind == PT_SHAPE_DISK ? "disk" : "sphere");
         if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " material index out of range");
         if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " area light index out of range");
-        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_MIX))
+        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_DISNEY))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
         if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " before_triangle exceeds n_triangles");
         if (sp.kind != PT_SHAPE_SPHERE) {
@@ -772,6 +793,28 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             mesh_alpha[am.mesh] = live ? 1 : 2;
         }
         for (uint8_t& m : mesh_alpha) if (m == 2) m = 0;
+        // Material "disney": one record per Disney material, float textures behind its float parameters ("eta" and "roughness" of pt_material included)
+        std::vector<uint8_t> seen(d->n_materials, 0);
+        for (const pt_disney& r : ctx->disney_recs) {
+            if (r.material >= d->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: material index out of range");
+            if (d->materials[r.material].type != PT_MATERIAL_DISNEY) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: a record for a material that is not a Disney material");
+            if (seen[r.material]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: two records for one material");
+            seen[r.material] = 1;
+            for (uint32_t t : r.tex) {
+                if (t > d->n_textures || (t && !d->textures)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: texture index out of range");
+                if (t && !is_float[t - 1]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: a colour texture behind a float parameter");
+            }
+            if (r.tex_scatterdistance > d->n_textures || (r.tex_scatterdistance && !d->textures)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: texture index out of range");
+            if (!r.thin && (r.tex_scatterdistance || r.scatterdistance[0] != 0.0f || r.scatterdistance[1] != 0.0f || r.scatterdistance[2] != 0.0f))
+                return ctx->fail(PT_ERR_UNSUPPORTED, "disney: non-black \"scatterdistance\" on a material that is not thin asks for the Disney BSSRDF, which the reference does not "
+                                                     "finish (todo!(), disney.rs:712); set \"thin\" or leave \"scatterdistance\" black");
+        }
+        for (uint32_t i = 0; i < d->n_materials; i++) {
+            const pt_material& m = d->materials[i];
+            if (m.type != PT_MATERIAL_DISNEY) continue;
+            for (uint32_t t : {m.tex_eta, m.tex_roughness, m.tex_bump})
+                if (t && !is_float[t - 1]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: a colour texture behind a float parameter");
+        }
     }
     bool any_alpha = false;
     for (uint8_t m : mesh_alpha) any_alpha |= m != 0;
@@ -1272,9 +1315,72 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
         return off;
     };
     std::vector<PtMix> mixes;
-    ctx->mix_per_hit.assign(mats.size(), 0);
+    ctx->per_hit_lobes.assign(mats.size(), 0);
+    std::vector<std::vector<PtLobe>> disney_lobes(mats.size());        // per constant Disney material: its list (a mix above it copies from here)
+    std::vector<const pt_disney*> disney_of(mats.size(), nullptr);
+    for (const pt_disney& r : ctx->disney_recs) disney_of[r.material] = &r;
+    ctx->disney_kernels = false;
     for (uint32_t i = 0; i < d->n_materials; i++) {
         build_lobes(d->materials[i], mats[i]);
+        if (d->materials[i].type == PT_MATERIAL_DISNEY) {
+            // Material "disney": its parameter block rides in the lobe slots of its PtMaterial record (PtDisneyParams), its up to eight lobes in a
+            // PtMix record of one leaf with no scale chain -- built here when every parameter is constant, at every hit otherwise
+            // (disney_hit_lobes, pt_kernels.hip).
+            const pt_material& in = d->materials[i];
+            PtMaterial& mm = mats[i];
+            PtDisneyParams dp;
+            std::memset(&dp, 0, sizeof(dp));
+            std::memcpy(dp.color, in.kd, 12);
+            const float defaults[10] = {0.0f, 0.0f, 0.0f, 0.0f, 0.5f, 0.0f, 1.0f, 0.0f, 0.0f, 1.0f};          // create_disney_material (disney.rs:806-841), by PT_DISNEY_*
+            const pt_disney* rec = disney_of[i];
+            const int slot[10] = {PT_DP_METALLIC, PT_DP_SPECULARTINT, PT_DP_ANISOTROPIC, PT_DP_SHEEN, PT_DP_SHEENTINT, PT_DP_CLEARCOAT, PT_DP_CLEARCOATGLOSS,
+                                  PT_DP_SPECTRANS, PT_DP_FLATNESS, PT_DP_DIFFTRANS};
+            uint32_t tex[PT_DP_COUNT] = {};
+            for (int k = 0; k < 10; k++) {
+                dp.f[slot[k]] = rec ? rec->value[k] : defaults[k];
+                tex[slot[k]] = rec ? rec->tex[k] : 0u;
+            }
+            dp.f[PT_DP_ETA] = in.eta; tex[PT_DP_ETA] = in.tex_eta;
+            dp.f[PT_DP_ROUGHNESS] = in.roughness; tex[PT_DP_ROUGHNESS] = in.tex_roughness;
+            dp.thin = rec && rec->thin ? 1u : 0u;
+            bool per_hit = false, too_big = false;
+            auto program = [&](uint32_t t) -> uint32_t {
+                if (!t) return 0u;
+                per_hit = true;
+                const uint32_t off = add_program(t - 1);
+                too_big |= off == 0;
+                return off;
+            };
+            dp.prog_color = program(in.tex_kd);
+            for (int k = 0; k < PT_DP_COUNT; k++) dp.prog[k] = program(tex[k]);
+            dp.prog_bump = program(in.tex_bump);
+            if (too_big) return ctx->fail(PT_ERR_UNSUPPORTED, "a material parameter's texture graph needs more than 12 nodes");
+            PtMix mx;
+            std::memset(&mx, 0, sizeof(mx));
+            mx.n_leaves = 1;
+            mx.leaf_material[0] = (int32_t)i;
+            if (!per_hit) {
+                mx.n_lobes = build_disney_lobes(dp, mx.lobes);
+                count_lobes(mx.lobes, mx.n_lobes, mm);
+                disney_lobes[i].assign(mx.lobes, mx.lobes + mx.n_lobes);
+            } else {
+                mx.per_hit = 1;
+                mm.textured = 1;
+                any_textured = true;
+                ctx->per_hit_lobes[i] = pt_context::PER_HIT_DISNEY;
+                mparams[i].m = in;
+                mparams[i].prog[8] = dp.prog_bump;          // where the aov kernel looks for a bump map
+            }
+            mm.n_lobes = 0; mm.has_bsdf = 1; mm.bsdf_eta = 1.0f;            // the BSDF is allocated with eta 1 (disney.rs:658)
+            static_assert(sizeof(dp) <= sizeof(mm.lobes), "PtDisneyParams in PtMaterial::lobes");
+            std::memcpy(mm.lobes, &dp, sizeof(dp));
+            mixes.push_back(mx);
+            mm.mix1 = (uint32_t)mixes.size();
+            general_materials = true;
+            ctx->disney_kernels = true;
+            mm.sort_bin = PT_SORT_GENERAL0 + std::min(n_general_bins++, PT_SORT_TEX0 - PT_SORT_GENERAL0 - 1u);
+            continue;
+        }
         if (d->materials[i].type == PT_MATERIAL_MIX) {
             // Flatten the tree under the mix (children precede it, so their PtMaterial records exist): leaves in lobe order, per leaf the
             // mix nodes above it innermost first.  Constant trees get their lobe list and scales here, once; a tree with a textured
@@ -1306,11 +1412,12 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
                     return;
                 }
                 const uint32_t j = n_leaves++;
-                if (in.type < PT_MATERIAL_NONE || in.type > PT_MATERIAL_TRANSLUCENT) {
+                if (in.type < PT_MATERIAL_NONE || (in.type > PT_MATERIAL_TRANSLUCENT && in.type != PT_MATERIAL_DISNEY)) {
                     if (refusal.empty()) refusal = "child material " + std::to_string(mi) + " has a material type that is not on the accelerated path";
                     return;
                 }
-                n_lobes += mats[mi].textured ? pt_lobes_most(in.type) : mats[mi].n_lobes;          // a texture-driven leaf: the most its type can add
+                n_lobes += mats[mi].textured ? pt_lobes_most(in.type)          // a texture-driven leaf: the most its type can add
+                                             : (in.type == PT_MATERIAL_DISNEY ? (uint32_t)disney_lobes[mi].size() : mats[mi].n_lobes);
                 if (in.type == PT_MATERIAL_NONE && refusal.empty())
                     refusal = "child material " + std::to_string(mi) + " is \"none\": it leaves no BSDF to scale (the reference asserts, mix.rs:78-79)";
                 else if (!mats[mi].textured && !mats[mi].has_bsdf && refusal.empty())
@@ -1343,6 +1450,9 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
                     }
                 for (uint32_t j = 0; j < mx.n_leaves; j++) {
                     const PtMaterial& lm = mats[mx.leaf_material[j]];
+                    const std::vector<PtLobe>& dl = disney_lobes[mx.leaf_material[j]];          // a Disney leaf's list lives beside its record
+                    if (lm.type == PT_MATERIAL_DISNEY) for (const PtLobe& l : dl) { mx.scales.lobe_leaf[mx.n_lobes] = j; mx.lobes[mx.n_lobes++] = l; }
+                    else
                     for (uint32_t l = 0; l < lm.n_lobes; l++) { mx.scales.lobe_leaf[mx.n_lobes] = j; mx.lobes[mx.n_lobes++] = lm.lobes[l]; }
                     for (uint32_t c = 0; c < mx.scales.n_chain[j]; c++)
                         std::memcpy(mx.scales.s[j][c], ns[mx.chain[j][c] & 0xffu][mx.chain[j][c] >> 8], 12);
@@ -1356,7 +1466,7 @@ static pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
             } else {
                 mm.textured = 1;                   // the per-hit route of the *_mix kernels
                 any_textured = true;
-                ctx->mix_per_hit[i] = 1;
+                ctx->per_hit_lobes[i] = pt_context::PER_HIT_MIX;
                 mparams[i].m = d->materials[i];
             }
             mixes.push_back(mx);
@@ -2415,7 +2525,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go
         unsigned long long sp[16];
-        if (ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
+        if (ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
             double tot = 0;
             for (int k = 0; k < 16; k++) if (k != 12) tot += (double)sp[k];
             static const char* names[16] = {"surface", "emit+bsdf setup", "grid+pick light", "u_light,u_scat", "light sample+f", "bsdf MIS+probe", "pend stores",
@@ -2688,7 +2798,9 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
     if (!ctx || !wo || !wi || !f_out || !pdf_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (material >= ctx->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material index out of range");
-    if (material < ctx->mix_per_hit.size() && ctx->mix_per_hit[material])
+    if (material < ctx->per_hit_lobes.size() && ctx->per_hit_lobes[material] == pt_context::PER_HIT_DISNEY)
+        return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this Disney material's lobes are built at every hit (a textured parameter or a bump map); the hooks take constant materials");
+    if (material < ctx->per_hit_lobes.size() && ctx->per_hit_lobes[material])
         return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this mix material's lobes are built at every hit (a textured amount or leaf); the hooks take constant trees");
     if (n == 0) return PT_OK;
     (void)hipSetDevice(ctx->device);
@@ -2696,7 +2808,7 @@ pt_status pt_bsdf_eval(pt_context* ctx, uint32_t material, uint32_t n, const flo
     PT_HIP(d_wo.alloc((size_t)n * 12)); PT_HIP(d_wi.alloc((size_t)n * 12)); PT_HIP(d_f.alloc((size_t)n * 12)); PT_HIP(d_pdf.alloc((size_t)n * 4));
     PT_HIP(hipMemcpy(d_wo.p, wo, (size_t)n * 12, hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(d_wi.p, wi, (size_t)n * 12, hipMemcpyHostToDevice));
-    PT_HIP(ptk_bsdf_eval(ctx->stream, ctx->sc, material, n, d_wo.as<float>(), d_wi.as<float>(), flags, d_f.as<float>(), d_pdf.as<float>()));
+    PT_HIP(ptk_bsdf_eval_any(ctx, ctx->stream, ctx->sc, material, n, d_wo.as<float>(), d_wi.as<float>(), flags, d_f.as<float>(), d_pdf.as<float>()));
     PT_HIP(hipStreamSynchronize(ctx->stream));
     PT_HIP(hipMemcpy(f_out, d_f.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     PT_HIP(hipMemcpy(pdf_out, d_pdf.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -2765,7 +2877,9 @@ pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const f
     if (!ctx || !wo || !u || !f_out || !wi_out || !pdf_out || !type_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (material >= ctx->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "material index out of range");
-    if (material < ctx->mix_per_hit.size() && ctx->mix_per_hit[material])
+    if (material < ctx->per_hit_lobes.size() && ctx->per_hit_lobes[material] == pt_context::PER_HIT_DISNEY)
+        return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this Disney material's lobes are built at every hit (a textured parameter or a bump map); the hooks take constant materials");
+    if (material < ctx->per_hit_lobes.size() && ctx->per_hit_lobes[material])
         return ctx->fail(PT_ERR_UNSUPPORTED, "BSDF hooks: this mix material's lobes are built at every hit (a textured amount or leaf); the hooks take constant trees");
     if (n == 0) return PT_OK;
     (void)hipSetDevice(ctx->device);
@@ -2774,7 +2888,7 @@ pt_status pt_bsdf_sample(pt_context* ctx, uint32_t material, uint32_t n, const f
     PT_HIP(d_pdf.alloc((size_t)n * 4)); PT_HIP(d_t.alloc((size_t)n * 4));
     PT_HIP(hipMemcpy(d_wo.p, wo, (size_t)n * 12, hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(d_u.p, u, (size_t)n * 8, hipMemcpyHostToDevice));
-    PT_HIP(ptk_bsdf_sample(ctx->stream, ctx->sc, material, n, d_wo.as<float>(), d_u.as<float>(), flags, d_f.as<float>(), d_wi.as<float>(), d_pdf.as<float>(),
+    PT_HIP(ptk_bsdf_sample_any(ctx, ctx->stream, ctx->sc, material, n, d_wo.as<float>(), d_u.as<float>(), flags, d_f.as<float>(), d_wi.as<float>(), d_pdf.as<float>(),
                            d_t.as<uint32_t>()));
     PT_HIP(hipStreamSynchronize(ctx->stream));
     PT_HIP(hipMemcpy(f_out, d_f.p, (size_t)n * 12, hipMemcpyDeviceToHost));

@@ -94,9 +94,15 @@ struct PtTriInfo {
 // One BxDF of a material's BSDF.  With constant textures Material::compute_scattering_functions adds
 // the same BxDFs at every hit, so the host evaluates it once per material (pt_context.cpp build_lobes).
 enum { PT_LOBE_LAMBERT = 0, PT_LOBE_OREN_NAYAR = 1, PT_LOBE_SPEC_REFL = 2, PT_LOBE_SPEC_TRANS = 3, PT_LOBE_FRESNEL_SPEC = 4,
-       PT_LOBE_MF_REFL = 5, PT_LOBE_MF_TRANS = 6, PT_LOBE_FRESNEL_BLEND = 7 };
+       PT_LOBE_MF_REFL = 5, PT_LOBE_MF_TRANS = 6, PT_LOBE_FRESNEL_BLEND = 7,
+       // Material "disney" (materials/disney.rs:44-323), known to the kernels of pt_kernels_disney.hip only: R in `r`; FakeSS / Retro keep their
+       // roughness in `oa`; Clearcoat keeps its weight in `oa` and its gloss in `ob`
+       PT_LOBE_DISNEY_DIFFUSE = 8, PT_LOBE_DISNEY_FAKE_SS = 9, PT_LOBE_DISNEY_RETRO = 10, PT_LOBE_DISNEY_SHEEN = 11, PT_LOBE_DISNEY_CLEARCOAT = 12 };
 // (LambertianTransmission, lambertian.rs:49-99, is PT_LOBE_LAMBERT whose `type` carries BSDF_TRANSMISSION instead of BSDF_REFLECTION: pt_bxdf.h)
-enum { PT_FR_NOOP = 0, PT_FR_DIELECTRIC = 1, PT_FR_CONDUCTOR = 2 };
+// PT_FR_DISNEY: DisneyFresnel (disney.rs:330-345): r0 in `t`, metallic in fr_eta_i, eta in fr_eta_t
+enum { PT_FR_NOOP = 0, PT_FR_DIELECTRIC = 1, PT_FR_CONDUCTOR = 2, PT_FR_DISNEY = 3 };
+#define PT_FR_MASK 0xffu
+#define PT_LOBE_G_SEPARABLE 0x100u    // in PtLobe::fresnel of a microfacet lobe: DisneyMicrofacetDistribution, whose g is g1(wo) * g1(wi) (disney.rs:368-371)
 struct PtLobe {                  // 80 bytes
     uint32_t kind;               // PT_LOBE_*
     uint32_t type;               // BxDFType bits (bxdf.rs:8-14)
@@ -127,7 +133,8 @@ struct PtMaterial {
                                  // specular_transmit ask BSDF::sample_f for: with the bit clear the call returns None before it looks at anything)
     uint32_t mix1;               // PT_MATERIAL_MIX: index + 1 of the material's PtMix record (0: not a mix); read by the *_mix kernels only
     uint32_t mix_base;           // ... and where the PtMix table starts: that many PtMaterial records into the materials buffer (material_mix below)
-    PtLobe lobes[PT_MAX_LOBES];
+    PtLobe lobes[PT_MAX_LOBES];  // n_lobes of them.  PT_MATERIAL_DISNEY: n_lobes is 0 (its list lives in a PtMix record or is built per hit) and these
+                                 // bytes hold the material's PtDisneyParams instead (material_disney below): read them as lobes only up to n_lobes
 };
 // Material "mix" (materials/mix.rs:53-96): the tree under one mix material, flattened at upload.  Its BSDF is the leaves' BxDFs in order
 // (child 1's, then child 2's, recursively), each wrapped in one ScaledBxDF (core/reflection/scaled.rs) per mix node above its leaf: the
@@ -171,6 +178,22 @@ struct PtMatParams {
     float a_r, a_u, a_v;
     uint32_t prog[13];           // [8] = the bump map's displacement texture, [9..12] = roughness, uroughness, vroughness, eta
 };
+// Material "disney": its thirteen parameters as create_disney_material reads them (disney.rs:806-841) and per parameter the offset of its
+// texture program (0 = constant).  f[]: metallic eta roughness speculartint anisotropic sheen sheentint clearcoat clearcoatgloss spectrans
+// flatness difftrans.  A Disney material's eight lobes do not fit PtMaterial::lobes (they live in a PtMix record of one leaf, or in the
+// per-hit list), so the block lives there: PtMaterial and PtScene keep their sizes.
+#define PT_DISNEY_MOST_LOBES 8
+enum { PT_DP_METALLIC = 0, PT_DP_ETA, PT_DP_ROUGHNESS, PT_DP_SPECULARTINT, PT_DP_ANISOTROPIC, PT_DP_SHEEN, PT_DP_SHEENTINT, PT_DP_CLEARCOAT,
+       PT_DP_CLEARCOATGLOSS, PT_DP_SPECTRANS, PT_DP_FLATNESS, PT_DP_DIFFTRANS, PT_DP_COUNT };
+struct PtDisneyParams {
+    float color[3];
+    float f[PT_DP_COUNT];
+    uint32_t thin;
+    uint32_t prog_color;
+    uint32_t prog[PT_DP_COUNT];
+    uint32_t prog_bump;
+};
+static_assert(sizeof(PtDisneyParams) <= sizeof(PtLobe) * PT_MAX_LOBES, "the Disney parameter block lives in PtMaterial::lobes");
 
 // One DiffuseAreaLight (one emissive triangle).
 struct PtLight {
@@ -354,6 +377,8 @@ PT_HOSTDEV_ENVS inline uint32_t scene_n_mix(const PtScene& sc) { return sc.gener
 PT_HOSTDEV_ENVS inline const PtMix& material_mix(const PtScene& sc, const PtMaterial& m) {
     return reinterpret_cast<const PtMix*>(sc.materials + m.mix_base)[m.mix1 - 1u];
 }
+// A Disney material's parameter block, in the lobe slots its PtMaterial record does not use (PtDisneyParams above).
+PT_HOSTDEV_ENVS inline const PtDisneyParams& material_disney(const PtMaterial& m) { return *reinterpret_cast<const PtDisneyParams*>(m.lobes); }
 static_assert(sizeof(PtMaterial) % 16 == 0 && sizeof(PtMix) % 4 == 0, "the PtMix table behind the materials");
 static_assert(sizeof(PtDeltaLight) == 80 && sizeof(PtEnvLight) % 8 == 0 && sizeof(PtLight) % 16 == 0, "side records of the light buffer");
 static_assert(__builtin_offsetof(PtScene, nodes) == 16, "n_deltas fills the hole in front of PtScene::nodes");

@@ -32,9 +32,14 @@
 // pt_kernels_quadric.hip includes it with PT_QUADRIC set: there the four places that touch an analytic shape branch on its kind
 // (pt_quadric.h), every kernel and launcher lives in namespace ptq, and pt_context.cpp runs that set for a scene that holds a cylinder
 // or a disk.  So a scene without them runs code that does not know them: no register, no branch, no spill of theirs.
+// pt_kernels_disney.hip includes it a third time, with PT_QUADRIC and PT_DISNEY set and PT_KERNEL_NS ptd: the BxDFs of Material "disney"
+// (pt_bxdf.h) on top of the second build, for the scenes that hold such a material.
 #if PT_QUADRIC
 #define PT_KERNEL __global__
-namespace ptq {
+#ifndef PT_KERNEL_NS
+#define PT_KERNEL_NS ptq
+#endif
+namespace PT_KERNEL_NS {
 #else
 #define PT_KERNEL extern "C" __global__
 #endif
@@ -2647,6 +2652,62 @@ struct PtMixHit {
     PtLobe lobes[PT_MIX_MAX_LOBES];
 };
 struct PtNoMix {};
+#if PT_DISNEY
+// Material "disney" with a textured parameter or a bump map: material_bump (core/material.rs:31-72) on the caller's frame, then the thirteen
+// parameters evaluated on the interaction (disney.rs:652-682), then the list written where the caller keeps it (build_disney_lobes, shared
+// with the host).  Returns the number of lobes, at most PT_DISNEY_MOST_LOBES.  One call site for every texture program of the hit, as in
+// textured_params_t: jobs 0-2 the bump map's displacement, job 3 "color", jobs 4.. the float parameters in PtDisneyParams order.
+__device__ __noinline__ uint32_t disney_hit_lobes(const PtScene& sc, int32_t material, const TexHit& th_in, PtLobe* out, V3 n, V2 uv, V3* sh_n, V3* sh_dpdu, V3 sh_dpdv,
+                                                  V3 sh_dndu, V3 sh_dndv) {
+    const TexHit th = th_in;          // (an object of this frame: see mix_hit_lobes)
+    PtDisneyParams dp = material_disney(sc.materials[material]);
+    float du = 0.0f, dv = 0.0f, disp0 = 0.0f, disp1 = 0.0f;
+    if (dp.prog_bump) {
+        du = 0.5f * (fabsf(th.dudx) + fabsf(th.dudy));
+        if (du == 0.0f) du = 0.0005f;
+        dv = 0.5f * (fabsf(th.dvdx) + fabsf(th.dvdy));
+        if (dv == 0.0f) dv = 0.0005f;
+    }
+    for (int j = 0; j < 4 + PT_DP_COUNT; j++) {
+        const uint32_t pr = j < 3 ? dp.prog_bump : (j == 3 ? dp.prog_color : dp.prog[j - 4]);
+        if (!pr) continue;
+        TexHit ev = th;
+        if (j == 0) { ev.p = th.p + du * *sh_dpdu; ev.uv = mk2(uv.x + du, uv.y + 0.0f); }
+        else if (j == 1) { ev.p = th.p + dv * sh_dpdv; ev.uv = mk2(uv.x + 0.0f, uv.y + dv); }
+        const V3 v = tex_eval(sc.textures, sc.tex_prog + pr, ev, sc.images);
+        if (j == 0) disp0 = v.x;
+        else if (j == 1) disp1 = v.x;
+        else if (j == 2) {
+            const float displace = v.x;
+            V3 dpdu = *sh_dpdu + (disp0 - displace) / du * *sh_n + displace * sh_dndu;
+            V3 dpdv = sh_dpdv + (disp1 - displace) / dv * *sh_n + displace * sh_dndv;
+            *sh_n = face_forward(normalize(cross(dpdu, dpdv)), n);
+            *sh_dpdu = dpdu;
+        } else if (j == 3) { dp.color[0] = v.x; dp.color[1] = v.y; dp.color[2] = v.z; }
+        else dp.f[j - 4] = v.x;
+    }
+    return build_disney_lobes(dp, out);
+}
+// Leaf j of a per-hit mix tree is a Disney material: its lobes into mh->lobes from slot nl on, tagged with their leaf; returns the new count.
+// leaf0_done == 2: mix_hit has written leaf 0's n0_lobes lobes to the head of the list already, on the caller's frame.  A textured leaf
+// builds its list on a clone of the frame (mix.rs:65); a constant one copies it from its own one-leaf record.  Every store is bounded by
+// PT_MIX_MAX_LOBES (the upload counts a textured Disney leaf at PT_DISNEY_MOST_LOBES, so the bound never bites).
+__device__ __noinline__ uint32_t disney_leaf_lobes(const PtScene& sc, int32_t mj, const PtMaterial& lm, const TexHit& th, uint32_t j, uint32_t leaf0_done, uint32_t n0_lobes,
+                                                   PtMixHit* mh, uint32_t nl, V3 n, V2 uv, V3 n0, V3 dpdu0, V3 sh_dpdv, V3 sh_dndu, V3 sh_dndv) {
+    uint32_t cnt = 0;
+    if (j == 0 && leaf0_done == 2) cnt = n0_lobes;
+    else if (lm.textured) {
+        V3 c_n = n0, c_dpdu = dpdu0;
+        if (nl + PT_DISNEY_MOST_LOBES <= PT_MIX_MAX_LOBES) cnt = disney_hit_lobes(sc, mj, th, mh->lobes + nl, n, uv, &c_n, &c_dpdu, sh_dpdv, sh_dndu, sh_dndv);
+    } else {
+        const PtMix& dm = material_mix(sc, lm);
+        cnt = dm.n_lobes;
+        for (uint32_t i = 0; i < cnt && nl + i < PT_MIX_MAX_LOBES; i++) mh->lobes[nl + i] = dm.lobes[i];
+    }
+    for (uint32_t i = 0; i < cnt && nl < PT_MIX_MAX_LOBES; i++) mh->scales.lobe_leaf[nl++] = j;
+    return nl;
+}
+#endif
 // leaf0_done: the caller has run the leftmost leaf through textured_lobes on its own interaction (mix_hit below) and *out holds that leaf's lobes;
 // n0 / dpdu0: the shading frame as the interaction arrived, which every later leaf's clone starts from.
 __device__ __noinline__ void mix_hit_lobes(const PtScene& sc, int32_t material, const TexHit& th_in, PtMaterial* out, uint32_t leaf0_done, PtMixHit* mh, V3 n, V2 uv, V3 n0,
@@ -2669,19 +2730,27 @@ __device__ __noinline__ void mix_hit_lobes(const PtScene& sc, int32_t material, 
         const int32_t mj = mx.leaf_material[j];
         const PtMaterial* lm = &sc.materials[mj];
         PtMaterial tm;
-        if (j == 0 && leaf0_done) lm = out;
-        else if (lm->textured) {
-            V3 c_n = n0, c_dpdu = dpdu0;          // the clone a later leaf works on is taken before any bump map (mix.rs:65) and thrown away
-            textured_lobes(sc, mj, th, &tm, n, uv, &c_n, &c_dpdu, sh_dpdv, sh_dndu, sh_dndv);
-            lm = &tm;
-        }
-        if (j == 0) eta0 = lm->bsdf_eta;
-        if (lm->has_bsdf)
-            for (uint32_t i = 0; i < lm->n_lobes && nl < PT_MIX_MAX_LOBES; i++) {          // (nl: a bound on a store; the upload counts a textured leaf at pt_lobes_most)
-                mh->lobes[nl] = lm->lobes[i];
-                mh->scales.lobe_leaf[nl] = j;
-                nl++;
+#if PT_DISNEY
+        if (lm->type == PT_MATERIAL_DISNEY) {          // its up to eight lobes go to mh->lobes without passing through a PtMaterial, which holds five
+            nl = disney_leaf_lobes(sc, mj, *lm, th, j, leaf0_done, out->n_lobes, mh, nl, n, uv, n0, dpdu0, sh_dpdv, sh_dndu, sh_dndv);
+            if (j == 0) eta0 = 1.0f;                   // DisneyMaterial allocates its BSDF with eta 1 (disney.rs:658)
+        } else
+#endif
+        {          // (one block, so that the branch above has a whole statement to fall to)
+            if (j == 0 && leaf0_done) lm = out;
+            else if (lm->textured) {
+                V3 c_n = n0, c_dpdu = dpdu0;          // the clone a later leaf works on is taken before any bump map (mix.rs:65) and thrown away
+                textured_lobes(sc, mj, th, &tm, n, uv, &c_n, &c_dpdu, sh_dpdv, sh_dndu, sh_dndv);
+                lm = &tm;
             }
+            if (j == 0) eta0 = lm->bsdf_eta;
+            if (lm->has_bsdf)
+                for (uint32_t i = 0; i < lm->n_lobes && nl < PT_MIX_MAX_LOBES; i++) {          // (nl: a bound on a store; the upload counts a textured leaf at pt_lobes_most)
+                    mh->lobes[nl] = lm->lobes[i];
+                    mh->scales.lobe_leaf[nl] = j;
+                    nl++;
+                }
+        }
         const uint32_t nc = mx.scales.n_chain[j];
         mh->scales.n_chain[j] = nc;
         for (uint32_t c = 0; c < nc; c++) {
@@ -2705,6 +2774,12 @@ PT_DEV void mix_hit(const PtScene& sc, int32_t material, const TexHit& th, PtMat
     const int32_t m0 = material_mix(sc, sc.materials[material]).leaf_material[0];
     const V3 n0 = s.sh_n, dpdu0 = s.sh_dpdu;
     uint32_t leaf0_done = 0;
+#if PT_DISNEY
+    if (sc.materials[m0].textured && sc.materials[m0].type == PT_MATERIAL_DISNEY) {          // a Disney material itself (a record of one leaf), or a mix's leftmost leaf
+        out->n_lobes = disney_hit_lobes(sc, m0, th, mh->lobes, s.n, s.uv, &s.sh_n, &s.sh_dpdu, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
+        leaf0_done = 2;
+    } else
+#endif
     if (sc.materials[m0].textured) {
         textured_lobes(sc, m0, th, out, s.n, s.uv, &s.sh_n, &s.sh_dpdu, s.sh_dpdv, s.sh_dndu, s.sh_dndv);
         leaf0_done = 1;
@@ -4838,5 +4913,5 @@ hipError_t ptk_sobol_samples(hipStream_t st, const PtScene& sc, uint32_t n, cons
     return PT_LAUNCH_CHECK();
 }
 #if PT_QUADRIC
-}  // namespace ptq
+}  // namespace PT_KERNEL_NS
 #endif

@@ -34,6 +34,7 @@ PT_HD inline uint32_t pt_lobes_most(int32_t type) {
         case PT_MATERIAL_PLASTIC: case PT_MATERIAL_GLASS: return 2;
         case PT_MATERIAL_TRANSLUCENT: return 4;
         case PT_MATERIAL_UBER: return 5;
+        case PT_MATERIAL_DISNEY: return PT_DISNEY_MOST_LOBES;      // build_disney_lobes below
         default: return 0;
     }
 }
@@ -191,3 +192,89 @@ PT_HD inline void build_lobes(const pt_material& in, float a_r, float a_u, float
     }
 }
 
+// ---- Material "disney" (materials/disney.rs:644-804): parameters in, BxDF list out, in the order the text adds them.  At most
+// PT_DISNEY_MOST_LOBES lobes, so the list is written to `out` directly (a PtMix record's lobes for a constant material, the per-hit
+// list for a textured one), not into a PtMaterial.  The conditions (diffuse_weight > 0, sheen_weight > 0, cc > 0, strans > 0, thin) are
+// taken on the evaluated values, per call.  Non-black "scatterdistance" without "thin" never gets here: the upload refuses it.
+PT_HD inline PtLobe* disney_lobe(PtLobe* l, uint32_t kind, uint32_t type, float r0, float r1, float r2) {
+    l->fresnel = 0;
+    l->t[0] = l->t[1] = l->t[2] = 0.0f; l->k[0] = l->k[1] = l->k[2] = 0.0f;
+    l->oa = l->ob = 0.0f;
+    l->kind = kind; l->type = type;
+    l->r[0] = r0; l->r[1] = r1; l->r[2] = r2;
+    l->eta_a = l->eta_b = l->fr_eta_i = l->fr_eta_t = 1.0f;
+    l->ax = l->ay = 0.001f;
+    return l;
+}
+PT_HD inline float disney_lerp(float t, float a, float b) { return (1.0f - t) * a + t * b; }           // core lerp
+PT_HD inline float disney_max(float a, float b) { return b != b ? a : (a > b ? a : b); }                // Float::max(a, b) for a number a: a NaN b gives a
+PT_HD inline uint32_t build_disney_lobes(const PtDisneyParams& p, PtLobe* out) {
+    uint32_t n = 0;
+    const float c[3] = {clamp_zero(p.color[0]), clamp_zero(p.color[1]), clamp_zero(p.color[2])};
+    const float metallic_weight = p.f[PT_DP_METALLIC], e = p.f[PT_DP_ETA], strans = p.f[PT_DP_SPECTRANS];
+    const float diffuse_weight = (1.0f - 0.5f * metallic_weight) * (1.0f - strans);
+    const float dt = p.f[PT_DP_DIFFTRANS] * (1.0f / 2.0f);
+    const float rough = p.f[PT_DP_ROUGHNESS];
+    const float lum = 0.212671f * c[0] + 0.715160f * c[1] + 0.072169f * c[2];                               // RGBSpectrum::y
+    const bool thin = p.thin != 0;
+    float c_tint[3], c_sheen[3];
+    for (int i = 0; i < 3; i++) c_tint[i] = lum > 0.0f ? c[i] / lum : 1.0f;
+    const float sheen_weight = p.f[PT_DP_SHEEN];
+    for (int i = 0; i < 3; i++) c_sheen[i] = sheen_weight > 0.0f ? disney_lerp(p.f[PT_DP_SHEENTINT], 1.0f, c_tint[i]) : 0.0f;
+    if (diffuse_weight > 0.0f) {
+        if (thin) {
+            const float flat = p.f[PT_DP_FLATNESS];
+            const float sd = diffuse_weight * (1.0f - flat) * (1.0f - dt);
+            disney_lobe(&out[n++], PT_LOBE_DISNEY_DIFFUSE, kRefl | kDiffuse, sd * c[0], sd * c[1], sd * c[2]);
+            const float ss = diffuse_weight * flat * (1.0f - dt);
+            disney_lobe(&out[n++], PT_LOBE_DISNEY_FAKE_SS, kRefl | kDiffuse, ss * c[0], ss * c[1], ss * c[2])->oa = rough;
+        } else {
+            disney_lobe(&out[n++], PT_LOBE_DISNEY_DIFFUSE, kRefl | kDiffuse, diffuse_weight * c[0], diffuse_weight * c[1], diffuse_weight * c[2]);
+        }
+        disney_lobe(&out[n++], PT_LOBE_DISNEY_RETRO, kRefl | kDiffuse, diffuse_weight * c[0], diffuse_weight * c[1], diffuse_weight * c[2])->oa = rough;
+        if (sheen_weight > 0.0f) {
+            const float sw = diffuse_weight * sheen_weight;
+            disney_lobe(&out[n++], PT_LOBE_DISNEY_SHEEN, kRefl | kDiffuse, sw * c_sheen[0], sw * c_sheen[1], sw * c_sheen[2]);
+        }
+    }
+    const float aspect = __builtin_sqrtf(1.0f - p.f[PT_DP_ANISOTROPIC] * 0.9f);
+    const float ax = disney_max(0.001f, rough * rough / aspect);
+    const float ay = disney_max(0.001f, rough * rough * aspect);
+    {
+        const float spec_tint = p.f[PT_DP_SPECULARTINT];
+        const float r0e = ((e - 1.0f) * (e - 1.0f)) / ((e + 1.0f) * (e + 1.0f));                              // schlick_r0_from_eta
+        PtLobe* l = disney_lobe(&out[n++], PT_LOBE_MF_REFL, kRefl | kGlossy, 1.0f, 1.0f, 1.0f);
+        for (int i = 0; i < 3; i++) l->t[i] = disney_lerp(metallic_weight, r0e * disney_lerp(spec_tint, 1.0f, c_tint[i]), c[i]);      // cspec0
+        set_distribution(l, ax, ay);
+        l->fresnel = PT_FR_DISNEY | PT_LOBE_G_SEPARABLE;
+        l->fr_eta_i = metallic_weight; l->fr_eta_t = e;
+    }
+    const float cc = p.f[PT_DP_CLEARCOAT];
+    if (cc > 0.0f) {
+        PtLobe* l = disney_lobe(&out[n++], PT_LOBE_DISNEY_CLEARCOAT, kRefl | kGlossy, 0.0f, 0.0f, 0.0f);
+        l->oa = cc;
+        l->ob = disney_lerp(p.f[PT_DP_CLEARCOATGLOSS], 0.1f, 0.001f);
+    }
+    if (strans > 0.0f) {
+        PtLobe* l = disney_lobe(&out[n++], PT_LOBE_MF_TRANS, kTrans | kGlossy, strans * __builtin_sqrtf(c[0]), strans * __builtin_sqrtf(c[1]), strans * __builtin_sqrtf(c[2]));
+        if (thin) {                                  // a plain TrowbridgeReitzDistribution on the roughness scaled by the IOR
+            const float rscaled = (0.65f * e - 0.35f) * rough;
+            set_distribution(l, disney_max(0.001f, (rscaled * rscaled) / aspect), disney_max(0.001f, (rscaled * rscaled) * aspect));
+        } else {
+            set_distribution(l, ax, ay);
+            l->fresnel = PT_LOBE_G_SEPARABLE;
+        }
+        l->eta_a = 1.0f; l->eta_b = e;
+    }
+    if (thin) disney_lobe(&out[n++], PT_LOBE_LAMBERT, kTrans | kDiffuse, dt * c[0], dt * c[1], dt * c[2]);      // LambertianTransmission, black or not
+    return n;
+}
+// what build_lobes leaves in a PtMaterial for the lobes of a list that lives elsewhere (a mix tree's, a Disney material's)
+PT_HD inline void count_lobes(const PtLobe* lobes, uint32_t n, PtMaterial& m) {
+    m.nonspecular = 0; m.spec_mask = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!(lobes[i].type & kSpecular)) m.nonspecular++;
+        if ((lobes[i].type & (kRefl | kSpecular)) == lobes[i].type) m.spec_mask |= 1u;
+        if ((lobes[i].type & (kTrans | kSpecular)) == lobes[i].type) m.spec_mask |= 2u;
+    }
+}

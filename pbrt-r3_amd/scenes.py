@@ -270,6 +270,7 @@ class SceneDesc:
         self.desc = capi.pt_scene_desc()
         self.buffers = {}
         self.alpha_masks = []       # capi.pt_alpha_mask, one per masked mesh (uploaded beside the descriptor, like infinite_lights)
+        self.disney = []            # capi.pt_disney, one per Material "disney" (uploaded beside the descriptor too)
         self.aov = (capi.PT_AOV_UV, 1.0)      # Integrator "aov": (pt_aov_target, scale), uploaded beside the descriptor too
 
     def _set(self, name, arr, ctype):
@@ -294,6 +295,7 @@ class SceneBuilder:
         self.infinite_lights = []   # capi.pt_infinite_light, in directive order
         self.delta_lights = []      # capi.pt_delta_light (point, spot, distant), in directive order
         self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
+        self.disney = []            # capi.pt_disney of the material_disney materials
         self.instances = []
         self.objects = {}           # name -> object index
         self.cur_object = 0         # 0 = world, k = inside ObjectBegin of object k - 1
@@ -617,6 +619,33 @@ class SceneBuilder:
         m.tex_kr, m.tex_kt = int(m1) + 1, int(m2) + 1
         if isinstance(amount, Tex):
             m.tex_kd = amount.index + 1
+
+    def material_disney(self, color=(0.5,) * 3, metallic=0.0, eta=1.5, roughness=0.5, speculartint=0.0, anisotropic=0.0, sheen=0.0, sheentint=0.5,
+                        clearcoat=0.0, clearcoatgloss=1.0, spectrans=0.0, flatness=0.0, difftrans=1.0, thin=False, scatterdistance=(0.0,) * 3,
+                        bumpmap=None):
+        """materials/disney.rs:806-841.  Every value but `thin` is a number (a colour for "color" and "scatterdistance") or a Tex handle.
+        "color", "eta", "roughness" and "bumpmap" travel in the pt_material; the rest in a pt_disney record beside the descriptor.  A
+        parameter behind a texture keeps the reference's default as its (unused) constant.  Usable as a child of material_mix."""
+        const = lambda v, d: d if isinstance(v, Tex) else v
+        self.cur_material = self._add_material(capi.PT_MATERIAL_DISNEY, const(color, (0.5,) * 3), eta=float(const(eta, 1.5)),
+                                               roughness=float(const(roughness, 0.5)), bump=bumpmap)
+        m = self.materials[self.cur_material]
+        for name, v in (("kd", color), ("eta", eta), ("roughness", roughness)):
+            if isinstance(v, Tex):
+                setattr(m, "tex_" + name, v.index + 1)
+        r = capi.pt_disney()
+        r.material = self.cur_material
+        given = ((capi.PT_DISNEY_METALLIC, metallic, 0.0), (capi.PT_DISNEY_SPECULARTINT, speculartint, 0.0), (capi.PT_DISNEY_ANISOTROPIC, anisotropic, 0.0),
+                 (capi.PT_DISNEY_SHEEN, sheen, 0.0), (capi.PT_DISNEY_SHEENTINT, sheentint, 0.5), (capi.PT_DISNEY_CLEARCOAT, clearcoat, 0.0),
+                 (capi.PT_DISNEY_CLEARCOATGLOSS, clearcoatgloss, 1.0), (capi.PT_DISNEY_SPECTRANS, spectrans, 0.0), (capi.PT_DISNEY_FLATNESS, flatness, 0.0),
+                 (capi.PT_DISNEY_DIFFTRANS, difftrans, 1.0))
+        for k, v, d in given:
+            r.value[k] = float(const(v, d))
+            r.tex[k] = v.index + 1 if isinstance(v, Tex) else 0
+        r.thin = 1 if thin else 0
+        r.scatterdistance[:] = [float(x) for x in const(scatterdistance, (0.0,) * 3)]
+        r.tex_scatterdistance = scatterdistance.index + 1 if isinstance(scatterdistance, Tex) else 0
+        self.disney.append(r)
 
     def material_none(self):
         self.cur_material = -1
@@ -945,6 +974,7 @@ class SceneBuilder:
         sd.infinite_lights = list(self.infinite_lights)
         sd.delta_lights = list(self.delta_lights)
         sd.alpha_masks = list(self.alpha_masks)
+        sd.disney = list(self.disney)
         sd.aov = tuple(self.aov)
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
         d.camera_to_world[:] = [float(v) for v in self.camera_to_world]
