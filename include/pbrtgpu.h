@@ -219,6 +219,27 @@ typedef struct {
     float direction[3];         /* distant: "from" - "to" as given (light space; not normalised): the w_light argument of DistantLight::new */
 } pt_delta_light;
 
+/* The two point-position lights that read an image: GonioPhotometricLight and ProjectionLight (src/lights/goniometric.rs, projection.rs).
+ * Delta lights like the three above (pdf 1, no MIS weight, no probe ray), in a record of their own so that pt_delta_light keeps its size.
+ * The record carries what the constructors are given and nothing derived: the upload computes p_light = light_to_world.transform_point(0)
+ * and, for a projection light, Transform::perspective(fov, 1e-3, 1e30), the screen bounds from resolution[0] / resolution[1] and
+ * cos_total_width from the inverse-projected corner, in f32 and in the constructors' operation order.  The map is images[image], three
+ * channels, a power-of-two pyramid as the infinite light's: read with s repeat and t clamp, no gamma, no y flip, negatives already
+ * clamped to 0, not multiplied by the intensity; "no mapname" is a 1 x 1 image of ones.  Passed with pt_scene_set_map_lights.
+ * Transforms must be affine (last row 0 0 0 1). */
+#define PT_DELTA_GONIOMETRIC 3
+#define PT_DELTA_PROJECTION  4
+typedef struct {
+    int32_t kind;               /* PT_DELTA_GONIOMETRIC / PT_DELTA_PROJECTION */
+    uint32_t light_index;       /* position in the scene's light list; counted together with the infinite and the delta lights */
+    float light_to_world[16];   /* row-major Transform.m: the CTM at the directive */
+    float world_to_light[16];   /* its stored inverse (Transform.minv) */
+    float spectrum[3];          /* "L" * "scale" (goniometric), "I" * "scale" (projection) */
+    int32_t image;              /* index into pt_scene_desc.images */
+    float fov;                  /* projection: "fov", degrees */
+    int32_t resolution[2];      /* projection: the map's width and height as read, before the pyramid's resize to powers of two */
+} pt_map_light;
+
 /* AlphaMaskShape (src/shapes/alphamask.rs) around every triangle of a mesh: "alpha" / "shadowalpha" of a trianglemesh or plymesh
  * (shapes/triangle.rs:654-694).  A candidate hit is rejected when the mask evaluated at its intersection-time interaction is <= 0;
  * the rejected hit does not shorten the ray.  Closest-hit rays test "alpha", shadow (any-hit) rays "alpha" and then "shadowalpha".
@@ -479,6 +500,11 @@ pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_inf
  * lights.  Their next-event estimate has no MIS weight and no probe ray (estimate_direct_surface, sample_lights.rs:380-397); a scene
  * with one runs the *_env kernels, as a scene with an infinite light does.  An unknown kind or a projective transform fails the upload. */
 pt_status pt_scene_set_delta_lights(pt_context* ctx, uint32_t n, const pt_delta_light* lights);
+/* The goniometric and projection lights of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the delta lights
+ * and estimated like them.  A scene with one runs a build of the kernels of its own (the one that knows the image lookup); every other
+ * scene runs the kernels it ran before.  An unknown kind, a projective transform, a bad image index, an image that is not three-channel
+ * or a projection light's resolution <= 0 fails the upload with PT_ERR_INVALID_ARGUMENT. */
+pt_status pt_scene_set_map_lights(pt_context* ctx, uint32_t n, const pt_map_light* lights);
 /* The alpha masks of the NEXT pt_scene_upload only (copied; n = 0 clears them), consumed like the infinite lights.  At most one record
  * per mesh.  A bad mesh or texture index, or a texture that is not a float texture, fails the upload with PT_ERR_INVALID_ARGUMENT.  A
  * scene with a mask traces every ray with k_trace_alpha (k_trace_batch_alpha for the trace hooks). */
@@ -592,6 +618,15 @@ pt_status pt_set_bvh_build(pt_context* ctx, int where);
 /* FNV-1a digests of the uploaded 4-wide node array and of the leaf record array (read back from the device): two uploads of one scene
  * agree exactly when their trees and leaf orders do. */
 pt_status pt_scene_bvh_digest(pt_context* ctx, uint64_t* nodes_digest, uint64_t* records_digest);
+/* Which build of the kernels renders the uploaded scene: PT_KERNELS_BASE for every scene without the features below (unmangled k_*
+ * symbols), PT_KERNELS_QUADRIC (namespace ptq) for one with a cylinder or a disk, PT_KERNELS_DISNEY (ptd) for one with a Material
+ * "disney", PT_KERNELS_MAP_LIGHT (ptm) for one with a goniometric or a projection light.  Each later build knows what the earlier ones
+ * know; a scene runs the first that knows everything it holds, so a new feature costs the scenes without it nothing. */
+#define PT_KERNELS_BASE 0
+#define PT_KERNELS_QUADRIC 1
+#define PT_KERNELS_DISNEY 2
+#define PT_KERNELS_MAP_LIGHT 3
+pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out);
 
 pt_status pt_get_counters(pt_context* ctx, pt_counters* out);
 pt_status pt_reset_counters(pt_context* ctx);

@@ -65,12 +65,16 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
  * cylinder of radius 0 is skipped with a warning); without the bit they are refused as before, with the same message.
  * PTH_FEATURE_DISNEY_MATERIAL: Material "disney" and the MakeNamedMaterial type "disney" (also as a child of a mix) become
  * PT_MATERIAL_DISNEY records with one pt_disney record each (pth_scene_get_disney); without the bit they are refused as before, with the
- * same message.  Non-black "scatterdistance" without "thin", and a colour texture behind a float parameter, are refused.  pbrt_gpu sets
- * all four. */
+ * same message.  Non-black "scatterdistance" without "thin", and a colour texture behind a float parameter, are refused.
+ * PTH_FEATURE_POINT_LIGHTS: LightSource "goniometric" and "projection" become pt_map_light records (pth_scene_get_map_lights; their
+ * "mapname" a three-channel pyramid among the descriptor's images, a 1 x 1 image of ones without it) and LightSource "point" a
+ * pt_delta_light of kind PT_DELTA_POINT; without the bit the three are refused as before, each with the same message.  pbrt_gpu sets
+ * all five. */
 #define PTH_FEATURE_MIX_MATERIAL 1u
 #define PTH_FEATURE_DELTA_LIGHTS 2u
 #define PTH_FEATURE_QUADRIC_SHAPES 4u
 #define PTH_FEATURE_DISNEY_MATERIAL 8u
+#define PTH_FEATURE_POINT_LIGHTS 16u
 pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
@@ -84,6 +88,9 @@ const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint3
 /* The scene's LightSource "spot" / "distant" lights, parsed with pth_options.delta_lights (for pt_scene_set_delta_lights); *n receives their count.
  * Valid until pth_scene_free. */
 const pt_delta_light* pth_scene_get_delta_lights(const pth_scene* s, uint32_t* n);
+/* The scene's LightSource "goniometric" / "projection" lights, parsed with PTH_FEATURE_POINT_LIGHTS (for pt_scene_set_map_lights); *n
+ * receives their count.  Their maps are entries of the descriptor's images[].  Valid until pth_scene_free. */
+const pt_map_light* pth_scene_get_map_lights(const pth_scene* s, uint32_t* n);
 /* The scene's alpha-masked meshes (for pt_scene_set_alpha_masks); *n receives their count.  Valid until pth_scene_free. */
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
 /* The scene's Material "disney" records (for pt_scene_set_disney); *n receives their count.  Valid until pth_scene_free. */

@@ -19,7 +19,7 @@ PT_MATERIAL_DISNEY = 10
 (PT_DISNEY_METALLIC, PT_DISNEY_SPECULARTINT, PT_DISNEY_ANISOTROPIC, PT_DISNEY_SHEEN, PT_DISNEY_SHEENTINT, PT_DISNEY_CLEARCOAT,
  PT_DISNEY_CLEARCOATGLOSS, PT_DISNEY_SPECTRANS, PT_DISNEY_FLATNESS, PT_DISNEY_DIFFTRANS) = range(10)
 PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
-PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES, PTH_FEATURE_DISNEY_MATERIAL = 1, 2, 4, 8
+PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES, PTH_FEATURE_DISNEY_MATERIAL, PTH_FEATURE_POINT_LIGHTS = 1, 2, 4, 8, 16
 PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER, PT_SHAPE_DISK = 0, 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
@@ -85,6 +85,15 @@ PT_DELTA_POINT, PT_DELTA_SPOT, PT_DELTA_DISTANT = range(3)
 class pt_delta_light(C.Structure):
     _fields_ = [("kind", C.c_int32), ("light_index", C.c_uint32), ("light_to_world", C.c_float * 16), ("world_to_light", C.c_float * 16),
                 ("spectrum", C.c_float * 3), ("cone_total_width", C.c_float), ("cone_falloff_start", C.c_float), ("direction", C.c_float * 3)]
+
+
+PT_DELTA_GONIOMETRIC, PT_DELTA_PROJECTION = 3, 4
+
+
+class pt_map_light(C.Structure):
+    """GonioPhotometricLight / ProjectionLight: the constructors' arguments (pt_scene_set_map_lights)."""
+    _fields_ = [("kind", C.c_int32), ("light_index", C.c_uint32), ("light_to_world", C.c_float * 16), ("world_to_light", C.c_float * 16),
+                ("spectrum", C.c_float * 3), ("image", C.c_int32), ("fov", C.c_float), ("resolution", C.c_int32 * 2)]
 
 
 PT_ALPHA_NONE, PT_ALPHA_CONSTANT, PT_ALPHA_TEXTURE = range(3)
@@ -192,7 +201,7 @@ SYMBOLS = [
     "pt_generate_camera_rays", "pt_sobol_samples", "pt_radiance_samples", "pt_get_counters", "pt_reset_counters",
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_pdf_from", "pt_light_le", "pt_scene_set_alpha_masks",
-    "pt_scene_set_aov", "pt_scene_set_delta_lights", "pt_scene_set_disney",
+    "pt_scene_set_aov", "pt_scene_set_delta_lights", "pt_scene_set_disney", "pt_scene_set_map_lights", "pt_scene_kernel_set",
 ]
 
 _lib = None
@@ -258,7 +267,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_parse_string_opts", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_parse_file_features", "pth_parse_string_features",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_scene_get_map_lights", "pth_parse_file_features", "pth_parse_string_features",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
@@ -271,11 +280,12 @@ class ParsedScene:
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
     def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False,
-                 disney_materials=False):
+                 disney_materials=False, point_lights=False):
         """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
         mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before.
         quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before.
-        disney_materials: take Material "disney" (PTH_FEATURE_DISNEY_MATERIAL, the same way); off, it is refused as before."""
+        disney_materials: take Material "disney" (PTH_FEATURE_DISNEY_MATERIAL, the same way); off, it is refused as before.
+        point_lights: take LightSource "goniometric", "projection" and "point" (PTH_FEATURE_POINT_LIGHTS, the same way); off, they are refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -295,11 +305,12 @@ class ParsedScene:
         opts = pth_options(0, 0, 0, 1)
         feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         features = (PTH_FEATURE_MIX_MATERIAL if mix_materials else 0) | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0) | \
-                   (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0) | (PTH_FEATURE_DISNEY_MATERIAL if disney_materials else 0)
-        if (mix_materials or quadric_shapes or disney_materials) and filename is not None:
+                   (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0) | (PTH_FEATURE_DISNEY_MATERIAL if disney_materials else 0) | \
+                   (PTH_FEATURE_POINT_LIGHTS if point_lights else 0)
+        if (mix_materials or quadric_shapes or disney_materials or point_lights) and filename is not None:
             L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
             st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
-        elif mix_materials or quadric_shapes or disney_materials:
+        elif mix_materials or quadric_shapes or disney_materials or point_lights:
             L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
             st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
         elif filename is not None and delta_lights:
@@ -326,6 +337,11 @@ class ParsedScene:
         n_dl = C.c_uint32()
         dl = L.pth_scene_get_delta_lights(self.h, C.byref(n_dl))
         self.delta_lights = [pt_delta_light.from_buffer_copy(dl[i]) for i in range(n_dl.value)]    # LightSource "spot" / "distant" (copies)
+        L.pth_scene_get_map_lights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.pth_scene_get_map_lights.restype = C.POINTER(pt_map_light)
+        n_ml = C.c_uint32()
+        ml = L.pth_scene_get_map_lights(self.h, C.byref(n_ml))
+        self.map_lights = [pt_map_light.from_buffer_copy(ml[i]) for i in range(n_ml.value)]       # LightSource "goniometric" / "projection" (copies)
         L.pth_scene_get_alpha_masks.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.pth_scene_get_alpha_masks.restype = C.POINTER(pt_alpha_mask)
         n_am = C.c_uint32()
@@ -515,6 +531,11 @@ class Context:
         dls = list(getattr(scene, "delta_lights", None) or [])
         dl_arr = (pt_delta_light * max(1, len(dls)))(*dls)
         self._check(self.lib.pt_scene_set_delta_lights(self.h, C.c_uint32(len(dls)), dl_arr if dls else None))
+        mls = list(getattr(scene, "map_lights", None) or [])
+        if mls:                      # goniometric / projection lights (an upload consumes them, so a scene without any has nothing to clear)
+            ml_arr = (pt_map_light * len(mls))(*mls)
+            self.lib.pt_scene_set_map_lights.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_map_light)]
+            self._check(self.lib.pt_scene_set_map_lights(self.h, C.c_uint32(len(mls)), ml_arr))
         am = list(getattr(scene, "alpha_masks", None) or [])
         am_arr = (pt_alpha_mask * max(1, len(am)))(*am)
         self._check(self.lib.pt_scene_set_alpha_masks(self.h, C.c_uint32(len(am)), am_arr if am else None))
@@ -535,6 +556,13 @@ class Context:
     def set_bvh_build(self, where):
         """BVH_BUILD_AUTO / _HOST / _DEVICE: where the lower half of an HLBVH build runs at the next upload."""
         self._check(self.lib.pt_set_bvh_build(self.h, int(where)))
+
+    def kernel_set(self):
+        """Which build of the kernels renders the uploaded scene: 0 base, 1 quadric (ptq), 2 disney (ptd), 3 map light (ptm)."""
+        k = C.c_int32()
+        self.lib.pt_scene_kernel_set.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        self._check(self.lib.pt_scene_kernel_set(self.h, C.byref(k)))
+        return k.value
 
     def bvh_digest(self):
         """(nodes, records) FNV-1a digests of the uploaded tree."""

@@ -147,10 +147,12 @@ public:
     std::vector<pt_area_light> area_lights;
     std::vector<pt_infinite_light> infinite_lights;
     std::vector<pt_delta_light> delta_lights;
+    std::vector<pt_map_light> map_lights;        // LightSource "goniometric" / "projection" (PTH_FEATURE_POINT_LIGHTS)
     bool accept_quadrics = false;                // PTH_FEATURE_QUADRIC_SHAPES: Shape "cylinder" and Shape "disk" are taken (off: refused, as before)
     bool accept_mix = false;                     // PTH_FEATURE_MIX_MATERIAL: Material "mix" is taken (off: refused, as before)
     bool accept_disney = false;                  // PTH_FEATURE_DISNEY_MATERIAL: Material "disney" is taken (off: refused, as before)
     std::vector<pt_disney> disney_records;                              // one per Material "disney" of `materials` (for pt_scene_set_disney)
+    bool accept_point_lights = false;            // PTH_FEATURE_POINT_LIGHTS: LightSource "goniometric", "projection" and "point" are taken (off: refused, as before)
     bool accept_delta_lights = false;            // pth_options.delta_lights: LightSource "spot" / "distant" are taken (off: refused, as before)
     int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
     float aov_scale = 1.0f;
@@ -472,7 +474,72 @@ public:
         dl.light_index = n_world_lights++;                          // appended to scene.lights as the directive is read
         delta_lights.push_back(dl);
     }
+    // create_point_light (lights/point.rs:113-124): Translate(from) * CTM, in that order; one pt_delta_light of kind PT_DELTA_POINT
+    void point_light_source(const ParamSet& p) {
+        float I[3] = {1.0f, 1.0f, 1.0f}, sc[3] = {1.0f, 1.0f, 1.0f};
+        spectrum_from(p, "I", I);
+        spectrum_from(p, "scale", sc);
+        if (!error.empty()) return;
+        const std::vector<float>* v = p.get_points("from");
+        const V3f from = (v && v->size() == 3) ? V3f{(*v)[0], (*v)[1], (*v)[2]} : V3f{0.0f, 0.0f, 0.0f};
+        const Xf l2w = pth::xf_mul(pth::xf_translate(from.x, from.y, from.z), transforms.back().t[0]);
+        for (int k = 0; k < 2; k++) {
+            const float* m = k ? l2w.inv.a : l2w.m.a;
+            if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f) { fail("LightSource \"point\" under a projective transform is not on the accelerated path"); return; }
+        }
+        pt_delta_light dl;
+        std::memset(&dl, 0, sizeof(dl));
+        dl.kind = PT_DELTA_POINT;
+        for (int k = 0; k < 3; k++) dl.spectrum[k] = I[k] * sc[k];
+        std::memcpy(dl.light_to_world, l2w.m.a, 64);
+        std::memcpy(dl.world_to_light, l2w.inv.a, 64);
+        dl.light_index = n_world_lights++;
+        delta_lights.push_back(dl);
+    }
+    // create_goniometric_light (lights/goniometric.rs:143-159) and create_projection_light (lights/projection.rs:176-195): one pt_map_light.
+    // make_mipmap (:123-141, :156-174): the map as the infinite light's with L = 1 (negatives clamped, no gamma, no flip), or a 1 x 1 map of ones.
+    void map_light_source(const std::string& name, const ParamSet& p) {
+        const bool gonio = name == "goniometric";
+        float I[3] = {1.0f, 1.0f, 1.0f}, sc[3] = {1.0f, 1.0f, 1.0f};
+        spectrum_from(p, gonio ? "L" : "I", I);
+        spectrum_from(p, "scale", sc);
+        if (!error.empty()) return;
+        const float fov = gonio ? 0.0f : p.find_one_float("fov", 45.0f);
+        std::string file = p.find_one_string("mapname", "");
+        const Xf& ctm = transforms.back().t[0];                    // light_to_world: the CTM at the directive
+        for (int k = 0; k < 2; k++) {
+            const float* m = k ? ctm.inv.a : ctm.m.a;
+            if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f) { fail("LightSource \"" + name + "\" under a projective transform is not on the accelerated path"); return; }
+        }
+        pt_map_light ml;
+        std::memset(&ml, 0, sizeof(ml));
+        const float one[3] = {1.0f, 1.0f, 1.0f};
+        int res[2] = {1, 1};
+        std::unique_ptr<Pyramid> pyr(new Pyramid());
+        if (!file.empty()) {
+            if (file[0] != '/' && !p.base_dir.empty()) file = p.base_dir + "/" + file;
+            RgbImage img;
+            std::string ierr;
+            if (!read_image_file(file, &img, &ierr)) { fail("LightSource \"" + name + "\": " + ierr); return; }
+            res[0] = img.width; res[1] = img.height;
+            if (res[0] <= 0 || res[1] <= 0) { fail("LightSource \"" + name + "\": the map's resolution must be positive"); return; }
+            build_env_pyramid(&img, one, pyr.get());
+        } else {
+            build_env_pyramid(nullptr, one, pyr.get());
+        }
+        pyramids.emplace_back(std::move(pyr));
+        ml.kind = gonio ? PT_DELTA_GONIOMETRIC : PT_DELTA_PROJECTION;
+        for (int k = 0; k < 3; k++) ml.spectrum[k] = I[k] * sc[k];
+        std::memcpy(ml.light_to_world, ctm.m.a, 64);
+        std::memcpy(ml.world_to_light, ctm.inv.a, 64);
+        ml.image = (int32_t)pyramids.size() - 1;
+        if (!gonio) { ml.fov = fov; ml.resolution[0] = res[0]; ml.resolution[1] = res[1]; }
+        ml.light_index = n_world_lights++;                          // appended to scene.lights as the directive is read
+        map_lights.push_back(ml);
+    }
     void pbrt_light_source(const std::string& name, const ParamSet& p) override {
+        if (accept_point_lights && (name == "goniometric" || name == "projection")) { map_light_source(name, p); return; }
+        if (accept_point_lights && name == "point") { point_light_source(p); return; }
         if ((name == "spot" || name == "distant") && accept_delta_lights) { delta_light_source(name, p); return; }
         if (name == "spot" || name == "distant") {
             fail("LightSource \"" + name + "\": taken only when the caller asks for delta lights (pth_options.delta_lights; pbrt_gpu does); "
@@ -1293,6 +1360,7 @@ pt_status pth_parse_file_features(const char* filename, const pth_options* opts,
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
+    s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_file(filename, s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);
@@ -1305,6 +1373,7 @@ pt_status pth_parse_string_features(const char* text, const char* work_dir, cons
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
+    s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_string(text, work_dir ? work_dir : ".", s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);
@@ -1335,6 +1404,10 @@ const pt_scene_desc* pth_scene_get_desc(const pth_scene* s) { return s ? &s->ctx
 const pt_delta_light* pth_scene_get_delta_lights(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.delta_lights.size() : 0u;
     return (s && !s->ctx.delta_lights.empty()) ? s->ctx.delta_lights.data() : nullptr;
+}
+const pt_map_light* pth_scene_get_map_lights(const pth_scene* s, uint32_t* n) {
+    if (n) *n = s ? (uint32_t)s->ctx.map_lights.size() : 0u;
+    return (s && !s->ctx.map_lights.empty()) ? s->ctx.map_lights.data() : nullptr;
 }
 const pt_infinite_light* pth_scene_get_infinite_lights(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.infinite_lights.size() : 0u;

@@ -653,7 +653,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go
         unsigned long long sp[16];
-        if (ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
+        if (ctx->maplight_kernels ? ptm::ptk_shade_prof_read(sp) : ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
             double tot = 0;
             for (int k = 0; k < 16; k++) if (k != 12) tot += (double)sp[k];
             static const char* names[16] = {"surface", "emit+bsdf setup", "grid+pick light", "u_light,u_scat", "light sample+f", "bsdf MIS+probe", "pend stores",
@@ -1070,6 +1070,13 @@ pt_status pt_set_bvh_build(pt_context* ctx, int where) {
     if (!ctx) return PT_ERR_INVALID_ARGUMENT;
     if (where != PT_BVH_BUILD_AUTO && where != PT_BVH_BUILD_HOST && where != PT_BVH_BUILD_DEVICE) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "unknown BVH build location");
     ctx->bvh_build_where = where;
+    return PT_OK;
+}
+
+pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out) {
+    if (!ctx || !set_out) return PT_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
+    *set_out = ctx->maplight_kernels ? PT_KERNELS_MAP_LIGHT : (ctx->disney_kernels ? PT_KERNELS_DISNEY : (ctx->quadric_kernels ? PT_KERNELS_QUADRIC : PT_KERNELS_BASE));
     return PT_OK;
 }
 

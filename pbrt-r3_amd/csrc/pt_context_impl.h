@@ -61,6 +61,7 @@ struct pt_context {
     pt_scene_info info;
     std::vector<pt_infinite_light> inf_lights;      // pt_scene_set_infinite_lights: the next upload's infinite lights
     std::vector<pt_delta_light> delta_lights;       // pt_scene_set_delta_lights: the next upload's point / spot / distant lights
+    std::vector<pt_map_light> map_lights;           // pt_scene_set_map_lights: the next upload's goniometric / projection lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
     std::vector<pt_disney> disney_recs;             // pt_scene_set_disney: the next upload's Disney parameter records
     int32_t next_aov_target = PT_AOV_UV;            // pt_scene_set_aov: the next upload's AOV target and scale (create_aov_integrator's defaults)
@@ -69,6 +70,7 @@ struct pt_context {
     float aov_scale = 1.0f;
     bool quadric_kernels = false;                   // the uploaded scene holds a cylinder or a disk: it runs the kernels of namespace ptq (pt_kernels_quadric.hip)
     bool disney_kernels = false;                    // the uploaded scene holds a Material "disney": it runs the kernels of namespace ptd (pt_kernels_disney.hip)
+    bool maplight_kernels = false;                  // the uploaded scene holds a goniometric or a projection light: it runs the kernels of namespace ptm (pt_kernels_maplight.hip)
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
@@ -147,10 +149,12 @@ struct pt_context {
 
 // The launchers whose kernels hold analytic-shape code (traversal, surface reconstruction, light sampling), by the scene: a cylinder or a disk asks for the second build of the kernels
 // (namespace ptq, pt_kernels_quadric.hip), every other scene runs the first.  A scene that holds a Material "disney" runs the third build (namespace ptd,
-// pt_kernels_disney.hip), which knows both the shapes and Disney's BxDFs.
+// pt_kernels_disney.hip), which knows both the shapes and Disney's BxDFs.  A scene that holds a goniometric or a projection light runs the fourth (namespace
+// ptm, pt_kernels_maplight.hip), which knows all of that and the two lights' image lookup.
 #define PTK_BY_SCENE(fn)                                                                                            \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         if (ctx->disney_kernels) return ptd::fn(std::forward<A>(a)...);                                             \
         return ctx->quadric_kernels ? ptq::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                 \
     }
@@ -174,6 +178,7 @@ PTK_BY_SCENE(ptk_light_pdf_from)
 #define PTK_BY_MATERIAL(fn)                                                                                         \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         return ctx->disney_kernels ? ptd::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                  \
     }
 PTK_BY_MATERIAL(ptk_bsdf_eval)

@@ -264,6 +264,16 @@ struct PtDeltaLight {            // 80 bytes
     float cos_falloff_start;     // spot: cos(radians(coneangle - conedelta))
     float radius;                // distant: the world bound's bounding-sphere radius (PtEnvLight::radius)
     float w2l[9];                // spot: rows 0..2 of world_to_light.m, the 3 x 3 part transform_vector reads (SpotLight::falloff)
+    uint32_t pad;                // goniometric, projection: index of the light's PtMapLight record (scene_map_lights)
+};
+// GonioPhotometricLight / ProjectionLight (lights/goniometric.rs, projection.rs): a PtDeltaLight of kind PT_DELTA_GONIOMETRIC /
+// PT_DELTA_PROJECTION (v = p_light, spectrum = intensity) plus this side record, so that PtDeltaLight keeps its 80 bytes for the kernels
+// that read it today.  Only the fourth build of the kernels (pt_kernels_maplight.hip) reads these records.
+struct PtMapLight {              // 136 bytes
+    float w2l[12];               // rows 0..2 of world_to_light.m: goniometric reads all twelve (transform_point on a direction, as written), projection the 3 x 3 part
+    uint32_t image;              // index into PtScene::images: the map (s repeat, t clamp)
+    float proj[16];              // projection: light_projection.m = (scale(1/tan(fov/2)) * perspective(1e-3, 1e30)).m, all sixteen for transform_point as written
+    float screen[4];             // projection: screen_bounds min.x min.y max.x max.y
     uint32_t pad;
 };
 
@@ -372,6 +382,8 @@ struct PtScene {
 PT_HOSTDEV_ENVS inline const PtEnvLight* scene_envs(const PtScene& sc) { return reinterpret_cast<const PtEnvLight*>(sc.lights + sc.n_lights); }
 // ... and the delta lights' PtDeltaLight records follow those.
 PT_HOSTDEV_ENVS inline const PtDeltaLight* scene_deltas(const PtScene& sc) { return reinterpret_cast<const PtDeltaLight*>(scene_envs(sc) + sc.n_envs); }
+// ... and the PtMapLight records of the goniometric / projection lights among them follow the last PtDeltaLight (n_deltas counts every delta record).
+PT_HOSTDEV_ENVS inline const PtMapLight* scene_map_lights(const PtScene& sc) { return reinterpret_cast<const PtMapLight*>(scene_deltas(sc) + sc.n_deltas); }
 // The mix materials' count rides above bit 0 of general_materials; their PtMix records follow the PtMaterial records in the materials buffer.
 PT_HOSTDEV_ENVS inline uint32_t scene_n_mix(const PtScene& sc) { return sc.general_materials >> 1; }
 PT_HOSTDEV_ENVS inline const PtMix& material_mix(const PtScene& sc, const PtMaterial& m) {

@@ -33,7 +33,9 @@
 // (pt_quadric.h), every kernel and launcher lives in namespace ptq, and pt_context.cpp runs that set for a scene that holds a cylinder
 // or a disk.  So a scene without them runs code that does not know them: no register, no branch, no spill of theirs.
 // pt_kernels_disney.hip includes it a third time, with PT_QUADRIC and PT_DISNEY set and PT_KERNEL_NS ptd: the BxDFs of Material "disney"
-// (pt_bxdf.h) on top of the second build, for the scenes that hold such a material.
+// (pt_bxdf.h) on top of the second build, for the scenes that hold such a material.  pt_kernels_maplight.hip includes it a fourth time, with
+// PT_MAPLIGHT set as well and PT_KERNEL_NS ptm: the image lookup of the goniometric and projection lights inside delta_sample_li, on top
+// of the third build, for the scenes that hold such a light.
 #if PT_QUADRIC
 #define PT_KERNEL __global__
 #ifndef PT_KERNEL_NS
@@ -2229,9 +2231,52 @@ PT_DEV float spot_falloff(const PtDeltaLight& dl, V3 w) {
     const float delta = (cos_theta - dl.cos_total_width) / (dl.cos_falloff_start - dl.cos_total_width);
     return (delta * delta) * (delta * delta);
 }
-PT_DEV void delta_sample_li(const PtDeltaLight& dl, V3 ref_p, V3* li, V3* wi, float* pdf, V3* lp) {
+#if PT_MAPLIGHT
+// ---- the two delta lights that read an image (lights/goniometric.rs:35-44, projection.rs:59-76); only the build with PT_MAPLIGHT set
+// (pt_kernels_maplight.hip) holds them.  Both look the map up as lookup(st, 0) does: the bilinear triangle filter on level 0, s repeat, t clamp.
+PT_DEV V3 map_light_lookup0(const PtScene& sc, const PtMapLight& ml, V2 st) {
+    MipRef m;
+    m.im = &sc.images[ml.image]; m.swrap = PT_WRAP_REPEAT; m.twrap = PT_WRAP_CLAMP;
+    return mip_triangle(m, 0u, st);
+}
+// GonioPhotometricLight::scale.  Q90: w goes through world_to_light.transform_point, so the translation is added to a direction, and the
+// result is not normalised; spherical_theta clamps its z.  (The y/z swap of pbrt-v3 is a comment there.)
+PT_DEV V3 gonio_scale(const PtScene& sc, const PtMapLight& ml, V3 w) {
+    const V3 wp = mk3(ml.w2l[0] * w.x + ml.w2l[1] * w.y + ml.w2l[2] * w.z + ml.w2l[3], ml.w2l[4] * w.x + ml.w2l[5] * w.y + ml.w2l[6] * w.z + ml.w2l[7],
+                      ml.w2l[8] * w.x + ml.w2l[9] * w.y + ml.w2l[10] * w.z + ml.w2l[11]);       // (the fourth row is 0 0 0 1: no divide)
+    const float theta = spherical_theta_dev(wp), phi = spherical_phi_dev(wp);
+    return map_light_lookup0(sc, ml, mk2(phi * PT_INV_2PI, theta * PT_INV_PI));
+}
+// ProjectionLight::projection.  Q91: black behind the near plane (wl.z < 1e-3), transform_point of the perspective matrix with its
+// homogeneous divide, Bounds2f::inside inclusive on both ends, offset for st.
+PT_DEV V3 projection_scale(const PtScene& sc, const PtMapLight& ml, V3 w) {
+    const V3 wl = mk3(ml.w2l[0] * w.x + ml.w2l[1] * w.y + ml.w2l[2] * w.z, ml.w2l[4] * w.x + ml.w2l[5] * w.y + ml.w2l[6] * w.z,
+                      ml.w2l[8] * w.x + ml.w2l[9] * w.y + ml.w2l[10] * w.z);
+    if (wl.z < 1e-3f) return mk3(0.0f, 0.0f, 0.0f);
+    const float* m = ml.proj;
+    float px = m[0] * wl.x + m[1] * wl.y + m[2] * wl.z + m[3], py = m[4] * wl.x + m[5] * wl.y + m[6] * wl.z + m[7];
+    const float pw = m[12] * wl.x + m[13] * wl.y + m[14] * wl.z + m[15];
+    if (pw != 1.0f) { px = px / pw; py = py / pw; }
+    if (!(px >= ml.screen[0] && px <= ml.screen[2] && py >= ml.screen[1] && py <= ml.screen[3])) return mk3(0.0f, 0.0f, 0.0f);
+    float ox = px - ml.screen[0], oy = py - ml.screen[1];
+    if (ml.screen[2] > ml.screen[0]) ox = ox / (ml.screen[2] - ml.screen[0]);
+    if (ml.screen[3] > ml.screen[1]) oy = oy / (ml.screen[3] - ml.screen[1]);
+    return map_light_lookup0(sc, ml, mk2(ox, oy));
+}
+#endif
+PT_DEV void delta_sample_li(const PtScene& sc, const PtDeltaLight& dl, V3 ref_p, V3* li, V3* wi, float* pdf, V3* lp) {
     const V3 v = ld3(dl.v), sp = ld3(dl.spectrum);
     *pdf = 1.0f;
+#if PT_MAPLIGHT
+    if (dl.kind >= PT_DELTA_GONIOMETRIC) {            // sample_li (goniometric.rs:48-64, projection.rs:80-97): intensity * scale(-wi) / distance_squared
+        const PtMapLight& ml = scene_map_lights(sc)[dl.pad];
+        *wi = normalize(v - ref_p);
+        const V3 s = dl.kind == PT_DELTA_GONIOMETRIC ? gonio_scale(sc, ml, -*wi) : projection_scale(sc, ml, -*wi);
+        *li = (sp * s) / distance_squared(v, ref_p);
+        *lp = v;
+        return;
+    }
+#endif
     if (dl.kind == PT_DELTA_DISTANT) {
         *wi = v;
         *li = sp;
@@ -2263,7 +2308,7 @@ PT_DEV bool light_sample_kind(const PtScene& sc, const PtLight& l, V3 ref_p, V3 
         }
         if constexpr (DELTA) {
             if (l.mesh_flags & PT_LIGHT_DELTA) {
-                delta_sample_li(scene_deltas(sc)[__float_as_uint(l.p0[0])], ref_p, li, wi, pdf, lp);
+                delta_sample_li(sc, scene_deltas(sc)[__float_as_uint(l.p0[0])], ref_p, li, wi, pdf, lp);
                 *lperr = mk3(0.0f, 0.0f, 0.0f); *ln = mk3(0.0f, 0.0f, 0.0f);
                 return true;
             }

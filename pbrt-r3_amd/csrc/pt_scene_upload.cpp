@@ -410,6 +410,19 @@ pt_status check_scene(pt_context* ctx, const pt_scene_desc* d, SceneChecks& chk)
         if (!affine(dl.light_to_world) || !affine(dl.world_to_light))
             return ctx->fail(PT_ERR_UNSUPPORTED, "delta light under a projective transform (last matrix row must be 0 0 0 1)");
     }
+    for (const pt_map_light& ml : ctx->map_lights) {
+        if (ml.kind != PT_DELTA_GONIOMETRIC && ml.kind != PT_DELTA_PROJECTION) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "map light: unknown kind (PT_DELTA_GONIOMETRIC and PT_DELTA_PROJECTION are known)");
+        const char* name = ml.kind == PT_DELTA_GONIOMETRIC ? "goniometric light" : "projection light";
+        if (!affine(ml.light_to_world) || !affine(ml.world_to_light))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, std::string(name) + " under a projective transform (last matrix row must be 0 0 0 1)");
+        if (ml.image < 0 || (uint32_t)ml.image >= d->n_images || !d->images) return ctx->fail(PT_ERR_INVALID_ARGUMENT, std::string(name) + ": image index out of range");
+        const pt_image& im = d->images[ml.image];
+        if (!im.texels || im.width == 0 || im.height == 0 || (im.width & (im.width - 1)) || (im.height & (im.height - 1)) || im.channels != 3 || im.n_levels == 0 ||
+            im.n_levels > PT_MAX_MIP_LEVELS || im.width > (1u << 14) || im.height > (1u << 14))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, std::string(name) + ": its image is not a power-of-two pyramid of 3 channels (at most 16384 wide)");
+        if (ml.kind == PT_DELTA_PROJECTION && (ml.resolution[0] <= 0 || ml.resolution[1] <= 0))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "projection light: resolution must be positive");
+    }
     // alpha masks: one record per mesh, float textures only (a texture whose channels are equal wherever it is evaluated)
     std::vector<uint8_t>& mesh_alpha = chk.mesh_alpha;
     mesh_alpha.assign(d->n_meshes, 0);
@@ -1212,8 +1225,11 @@ pt_status upload_materials_and_lights(pt_context* ctx, const pt_scene_desc* d, M
         if ((st = upload(ctx, ctx->d_materials, both.data(), both.size())) != PT_OK) return st;
     }
     {   // infinite and delta lights: their records at their places in the light list (scene_context.rs:1178-1188), in directive order
-        const uint32_t n_inf = (uint32_t)ctx->inf_lights.size(), n_all = n_inf + (uint32_t)ctx->delta_lights.size();
-        auto index_of = [&](uint32_t k) { return k < n_inf ? ctx->inf_lights[k].light_index : ctx->delta_lights[k - n_inf].light_index; };
+        // (the goniometric / projection lights are delta lights whose PtDeltaLight records follow those of pt_scene_set_delta_lights)
+        const uint32_t n_inf = (uint32_t)ctx->inf_lights.size(), n_dl = (uint32_t)ctx->delta_lights.size(), n_all = n_inf + n_dl + (uint32_t)ctx->map_lights.size();
+        auto index_of = [&](uint32_t k) {
+            return k < n_inf ? ctx->inf_lights[k].light_index : (k < n_inf + n_dl ? ctx->delta_lights[k - n_inf].light_index : ctx->map_lights[k - n_inf - n_dl].light_index);
+        };
         std::vector<uint32_t> order(n_all);
         for (uint32_t k = 0; k < n_all; k++) order[k] = k;
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return index_of(a) < index_of(b); });
@@ -1241,7 +1257,7 @@ pt_status upload_materials_and_lights(pt_context* ctx, const pt_scene_desc* d, M
 pt_status upload_images_and_textures(pt_context* ctx, const pt_scene_desc* d, const SceneChecks& chk, const MaterialTables& mt, bool& images_on_device) {
     pt_status st;
     std::vector<PtImage> dimages(d->n_images);
-    images_on_device =(mt.any_textured || !ctx->inf_lights.empty() || mt.any_alpha_tex) && d->n_images;
+    images_on_device =(mt.any_textured || !ctx->inf_lights.empty() || !ctx->map_lights.empty() || mt.any_alpha_tex) && d->n_images;
     if (images_on_device) {           // all pyramids in one buffer
         size_t total = 0;
         for (uint32_t i = 0; i < d->n_images; i++) {
@@ -1331,18 +1347,20 @@ pt_status build_delta_and_env_records(pt_context* ctx, const pt_scene_desc* d, c
     PtScene& sc = ctx->sc;
     pt_status st;
     env_power.assign(ctx->inf_lights.size(), 0.0f);
-    delta_power.assign(ctx->delta_lights.size(), 0.0f);
+    delta_power.assign(ctx->delta_lights.size() + ctx->map_lights.size(), 0.0f);
     sc.n_envs = 0;
     sc.n_deltas = 0;
     std::vector<PtEnvLight> envs(ctx->inf_lights.size());
-    std::vector<PtDeltaLight> deltas(ctx->delta_lights.size());
+    std::vector<PtDeltaLight> deltas(ctx->delta_lights.size() + ctx->map_lights.size());
+    std::vector<PtMapLight> maps(ctx->map_lights.size());
+    ctx->maplight_kernels = !ctx->map_lights.empty();
     // Light::preprocess: Bounds3::bounding_sphere of the world bound (bounds3.rs:173-177), half the diagonal
     const float dx = sc.wb_max[0] - sc.wb_min[0], dy = sc.wb_max[1] - sc.wb_min[1], dz = sc.wb_max[2] - sc.wb_min[2];
     const float radius = std::sqrt(dx * dx + dy * dy + dz * dz) * 0.5f;
     if (!ctx->delta_lights.empty()) {    // PtDeltaLight records: what PointLight::new / SpotLight::new / DistantLight::new + preprocess compute
         const float kPiF = 3.14159265358979323846f;
         auto lum = [](float r, float g, float b) { return 0.212671f * r + 0.715160f * g + 0.072169f * b; };
-        for (size_t k = 0; k < deltas.size(); k++) {
+        for (size_t k = 0; k < ctx->delta_lights.size(); k++) {
             const pt_delta_light& dl = ctx->delta_lights[k];
             PtDeltaLight& o = deltas[k];
             std::memset(&o, 0, sizeof(o));
@@ -1373,6 +1391,47 @@ pt_status build_delta_and_env_records(pt_context* ctx, const pt_scene_desc* d, c
             }
             delta_power[k] = lum(o.spectrum[0] * s, o.spectrum[1] * s, o.spectrum[2] * s);
         }
+    }
+    // GonioPhotometricLight::new / ProjectionLight::new (goniometric.rs:13-33, projection.rs:19-57) and their power() (:66-70, :99-103)
+    for (size_t k = 0; k < maps.size(); k++) {
+        const pt_map_light& ml = ctx->map_lights[k];
+        PtDeltaLight& o = deltas[ctx->delta_lights.size() + k];
+        PtMapLight& mo = maps[k];
+        std::memset(&o, 0, sizeof(o));
+        std::memset(&mo, 0, sizeof(mo));
+        o.kind = (uint32_t)ml.kind;
+        o.pad = (uint32_t)k;
+        std::memcpy(o.spectrum, ml.spectrum, 12);
+        const float* m = ml.light_to_world;
+        for (int a = 0; a < 3; a++) o.v[a] = m[4 * a] * 0.0f + m[4 * a + 1] * 0.0f + m[4 * a + 2] * 0.0f + m[4 * a + 3];       // p_light = light_to_world.transform_point(0)
+        std::memcpy(mo.w2l, ml.world_to_light, 48);
+        mo.image = (uint32_t)ml.image;
+        const EnvMap map(d->images[ml.image]);
+        float c[3];
+        map.lookup(0.5f, 0.5f, 0.5f, c);
+        const float kPiF = 3.14159265358979323846f;
+        float pw[3];
+        if (ml.kind == PT_DELTA_GONIOMETRIC) {
+            for (int a = 0; a < 3; a++) pw[a] = 4.0f * kPiF * o.spectrum[a] * c[a];
+        } else {
+            const float aspect = (float)ml.resolution[0] / (float)ml.resolution[1];
+            if (aspect > 1.0f) { mo.screen[0] = -aspect; mo.screen[1] = -1.0f; mo.screen[2] = aspect; mo.screen[3] = 1.0f; }
+            else { mo.screen[0] = -1.0f; mo.screen[1] = -1.0f / aspect; mo.screen[2] = 1.0f; mo.screen[3] = 1.0f / aspect; }
+            pth::Xf proj;
+            if (!pth::xf_perspective(ml.fov, 1e-3f, 1e30f, &proj)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "projection light: fov gives a singular projection");
+            std::memcpy(mo.proj, proj.m.a, 64);
+            // w_corner = screen_to_light.transform_point((max.x, max.y, 0)).normalize(); cos_total_width = w_corner.z
+            const float* q = proj.inv.a;
+            const float x = mo.screen[2], y = mo.screen[3], z = 0.0f;
+            float cx = q[0] * x + q[1] * y + q[2] * z + q[3], cy = q[4] * x + q[5] * y + q[6] * z + q[7], cz = q[8] * x + q[9] * y + q[10] * z + q[11];
+            const float cw = q[12] * x + q[13] * y + q[14] * z + q[15];
+            if (cw != 1.0f) { cx = cx / cw; cy = cy / cw; cz = cz / cw; }
+            const float len = std::sqrt(cx * cx + cy * cy + cz * cz);
+            o.cos_total_width = cz / len;
+            const float cone = 2.0f * kPiF * (1.0f - o.cos_total_width);
+            for (int a = 0; a < 3; a++) pw[a] = c[a] * o.spectrum[a] * cone;
+        }
+        delta_power[ctx->delta_lights.size() + k] = 0.212671f * pw[0] + 0.715160f * pw[1] + 0.072169f * pw[2];
     }
     if (!ctx->inf_lights.empty()) {      // PtEnvLight records + their Distribution2D tables (one buffer; its bytes are gone from what the path pool may take)
         const size_t ne = ctx->inf_lights.size();
@@ -1412,10 +1471,11 @@ pt_status build_delta_and_env_records(pt_context* ctx, const pt_scene_desc* d, c
     } else { ctx->d_env_tabs.release(); }
     if (!envs.empty() || !deltas.empty()) {
         const size_t ne = envs.size(), nd = deltas.size(), lb = lights.size() * sizeof(PtLight);
-        std::vector<uint8_t> lbuf(lb + ne * sizeof(PtEnvLight) + nd * sizeof(PtDeltaLight));       // the records behind the lights (scene_envs, scene_deltas)
+        std::vector<uint8_t> lbuf(lb + ne * sizeof(PtEnvLight) + nd * sizeof(PtDeltaLight) + maps.size() * sizeof(PtMapLight));       // the records behind the lights (scene_envs, scene_deltas, scene_map_lights)
         std::memcpy(lbuf.data(), lights.data(), lb);
         if (ne) std::memcpy(lbuf.data() + lb, envs.data(), ne * sizeof(PtEnvLight));
         if (nd) std::memcpy(lbuf.data() + lb + ne * sizeof(PtEnvLight), deltas.data(), nd * sizeof(PtDeltaLight));
+        if (!maps.empty()) std::memcpy(lbuf.data() + lb + ne * sizeof(PtEnvLight) + nd * sizeof(PtDeltaLight), maps.data(), maps.size() * sizeof(PtMapLight));
         if ((st = upload(ctx, ctx->d_lights, lbuf.data(), lbuf.size())) != PT_OK) return st;
         sc.lights = ctx->d_lights.as<PtLight>();
         sc.n_envs = (uint32_t)ne;
@@ -1711,6 +1771,7 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     const pt_status st = scene_upload(ctx, d);
     ctx->inf_lights.clear();
     ctx->delta_lights.clear();
+    ctx->map_lights.clear();
     ctx->alpha_masks.clear();
     ctx->disney_recs.clear();
     ctx->next_aov_target = PT_AOV_UV;
@@ -1727,6 +1788,12 @@ pt_status pt_scene_set_infinite_lights(pt_context* ctx, uint32_t n, const pt_inf
 pt_status pt_scene_set_delta_lights(pt_context* ctx, uint32_t n, const pt_delta_light* lights) {
     if (!ctx || (n && !lights)) return PT_ERR_INVALID_ARGUMENT;
     ctx->delta_lights.assign(lights, lights + n);
+    return PT_OK;
+}
+
+pt_status pt_scene_set_map_lights(pt_context* ctx, uint32_t n, const pt_map_light* lights) {
+    if (!ctx || (n && !lights)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->map_lights.assign(lights, lights + n);
     return PT_OK;
 }
 

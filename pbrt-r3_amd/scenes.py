@@ -294,6 +294,7 @@ class SceneBuilder:
         self.images = []            # (pt_image, texel buffer)
         self.infinite_lights = []   # capi.pt_infinite_light, in directive order
         self.delta_lights = []      # capi.pt_delta_light (point, spot, distant), in directive order
+        self.map_lights = []        # capi.pt_map_light (goniometric, projection), in directive order
         self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
         self.disney = []            # capi.pt_disney of the material_disney materials
         self.instances = []
@@ -684,7 +685,7 @@ class SceneBuilder:
                 mm = self.meshes[int(mid)]
                 n += 1 if (mm.area_light >= 0 and mm.object == 0) else 0
         n += sum(1 for sp in self.spheres if sp.area_light >= 0 and sp.object == 0)
-        return n + len(self.infinite_lights) + len(self.delta_lights)
+        return n + len(self.infinite_lights) + len(self.delta_lights) + len(self.map_lights)
 
     def _delta_light(self, kind, spectrum, scale, l2w, direction=(0.0, 0.0, 0.0), total_width=0.0, falloff_start=0.0):
         dl = capi.pt_delta_light()
@@ -724,6 +725,34 @@ class SceneBuilder:
         the opposite of pbrt-v3's."""
         frm = _v(*frm)
         return self._delta_light(capi.PT_DELTA_POINT, I, scale, transform_mul(transform_translate(frm[0], frm[1], frm[2]), self._ctm(ctm)))
+
+    def _map_light(self, kind, spectrum, scale, image, ctm, fov=0.0, resolution=(0, 0)):
+        ml = capi.pt_map_light()
+        ml.kind = kind
+        l2w = self._ctm(ctm)
+        ml.light_to_world[:] = [float(v) for v in l2w[0]]
+        ml.world_to_light[:] = [float(v) for v in l2w[1]]
+        ml.spectrum[:] = [float(f32(a) * f32(b)) for a, b in zip(spectrum, scale)]
+        # make_mipmap (goniometric.rs:123-141, projection.rs:156-174): negatives clamped to 0, not multiplied by the intensity; no map: 1 x 1 of ones
+        base = np.ones((1, 1, 3), np.float32) if image is None else np.maximum(np.asarray(image, np.float32), f32(0.0))
+        ml.image = self.image_pyramid(base)
+        ml.fov = float(f32(fov))
+        ml.resolution[:] = [int(resolution[0]), int(resolution[1])]
+        ml.light_index = self._next_light_index()
+        self.map_lights.append(ml)
+        return ml.light_index
+
+    def light_goniometric(self, L=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), image=None, ctm=None):
+        """LightSource "goniometric" (create_goniometric_light, lights/goniometric.rs:143-159) read at this point of the scene: light_to_world
+        is the CTM.  image: the map as read (H, W, 3), power of two, row 0 = t 0; None: the 1 x 1 map of ones.  Returns the light's index."""
+        return self._map_light(capi.PT_DELTA_GONIOMETRIC, L, scale, image, ctm)
+
+    def light_projection(self, I=(1.0, 1.0, 1.0), scale=(1.0, 1.0, 1.0), fov=45.0, image=None, resolution=None, ctm=None):
+        """LightSource "projection" (create_projection_light, lights/projection.rs:176-195).  image as light_goniometric takes it; resolution:
+        the map's (width, height) as read, before any resize to powers of two -- the aspect of the screen bounds --, default the array's shape."""
+        if resolution is None:
+            resolution = (1, 1) if image is None else (np.asarray(image).shape[1], np.asarray(image).shape[0])
+        return self._map_light(capi.PT_DELTA_PROJECTION, I, scale, image, ctm, fov=fov, resolution=resolution)
 
     def no_area_light(self):
         self.cur_area_light = -1
@@ -973,6 +1002,7 @@ class SceneBuilder:
             d.n_spheres, d.spheres = len(self.spheres), sph
         sd.infinite_lights = list(self.infinite_lights)
         sd.delta_lights = list(self.delta_lights)
+        sd.map_lights = list(self.map_lights)
         sd.alpha_masks = list(self.alpha_masks)
         sd.disney = list(self.disney)
         sd.aov = tuple(self.aov)
