@@ -340,7 +340,8 @@ typedef struct {
  * is wrapped directly).  Objects are the meshes / spheres tagged with `object`; their primitive order is their order in the
  * triangle array with their spheres spliced in by before_triangle, exactly as for the world list.  Rays are taken to instance
  * space with the stored inverse (Transform::inverse swaps m and m_inv) and hits brought back with
- * transform_surface_interaction.  Animated instance transforms are outside the accelerated path. */
+ * transform_surface_interaction.  These are the START-time transforms; an instance that moves gets a pt_motion_instance record as well
+ * (pt_scene_set_motion). */
 typedef struct {
     float instance_to_world[16];    /* CTM at the ObjectInstance directive */
     float world_to_instance[16];
@@ -349,6 +350,25 @@ typedef struct {
     uint32_t order;                 /* creation order among spheres and instances sharing a before_triangle value */
     uint32_t reserved;
 } pt_instance;
+
+/* Motion blur: AnimatedTransform (core/transform/animated_transform.rs) for the camera and for instances.  pt_scene_desc.camera_to_world
+ * and pt_instance.* are the transforms at transform_times[0]; this record adds the ones at transform_times[1].  Both ends are decomposed
+ * as the reference's decompose() does (translation, rotation quaternion, the diagonal of the scale: shear is dropped), and a ray at a
+ * time strictly between the two sees translate(lerp T) * slerp(R) * scale(lerp S), inverted by Gauss-Jordan elimination; at or outside
+ * the ends it sees the stored end transform and its stored inverse.  A record whose two ends are equal is static (actually_animated).
+ * Lights do not move.  Passed with pt_scene_set_motion, not in pt_scene_desc. */
+typedef struct {
+    uint32_t instance;                  /* index into pt_scene_desc.instances */
+    float instance_to_world_end[16];    /* row-major Transform.m at transform_times[1]; affine (last row 0 0 0 1) */
+    float world_to_instance_end[16];    /* its stored inverse */
+} pt_motion_instance;
+typedef struct {
+    float transform_times[2];           /* TransformTimes (render_options.rs:65-66: 0, 1) */
+    int32_t camera_animated;            /* != 0: camera_to_world_end is read */
+    float camera_to_world_end[16];      /* row-major Transform.m of the camera at transform_times[1]; affine */
+    uint32_t n_instances;
+    const pt_motion_instance* instances;    /* at most one record per instance */
+} pt_motion;
 
 typedef enum { PT_SPLIT_SAH = 0, PT_SPLIT_HLBVH = 1, PT_SPLIT_MIDDLE = 2, PT_SPLIT_EQUAL_COUNTS = 3 } pt_split_method;
 typedef enum {
@@ -518,6 +538,13 @@ pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* reco
  * when that upload's integrator is PT_INTEGRATOR_AOV.  Not called: target uv, scale 1 (create_aov_integrator's defaults, aov.rs:200-201).
  * A target outside the enum is PT_ERR_INVALID_ARGUMENT. */
 pt_status pt_scene_set_aov(pt_context* ctx, int32_t target, float scale);
+/* The motion of the NEXT pt_scene_upload only (copied; NULL clears it), consumed like the infinite lights.  An instance index out of
+ * range, two records for one instance, an end transform that is not affine or that decompose() fails on, or a pair whose decomposed
+ * scale changes sign in a component (its interpolation is singular on the way) fails the upload with PT_ERR_INVALID_ARGUMENT.  A scene whose camera or at least one instance actually moves runs the build of the kernels that knows
+ * AnimatedTransform::interpolate (PT_KERNELS_MOTION); not called, or with records whose ends are equal, the scene runs what it ran
+ * before.  The world tree takes AnimatedTransform::motion_bounds of a moving instance's object bound.  Every ray of a camera sample
+ * carries that sample's time: lerp(u, shutter_open, shutter_close) with the sampler's fifth dimension. */
+pt_status pt_scene_set_motion(pt_context* ctx, const pt_motion* motion);
 pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* desc);
 pt_status pt_scene_info_get(const pt_context* ctx, pt_scene_info* out);
 
@@ -573,6 +600,18 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
 pt_status pt_generate_camera_rays(pt_context* ctx, uint32_t n, const int32_t* pixel_xy,
                                   const uint32_t* sample_index, float* out_o, float* out_d,
                                   float* out_pfilm);
+/* The hooks above with a time per ray (n floats; Ray::time), and the camera hook returning each ray's time as well:
+ * lerp(u, shutter_open, shutter_close) with u the sampler's fifth dimension (perspective.rs:111-117).  On a scene without motion the
+ * times are ignored; the hooks without a time trace a moving scene at time 0 (Ray::default). */
+pt_status pt_trace_closest_time(pt_context* ctx, uint32_t n, const float* o, const float* d,
+                                const float* tmax, const float* time, pt_hit* out);
+pt_status pt_trace_any_time(pt_context* ctx, uint32_t n, const float* o, const float* d,
+                            const float* tmax, const float* time, uint8_t* occluded_out);
+pt_status pt_trace_wavefront_time(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time,
+                                  const uint8_t* kind, pt_hit* out, uint8_t* occluded_out);
+pt_status pt_generate_camera_rays_time(pt_context* ctx, uint32_t n, const int32_t* pixel_xy,
+                                       const uint32_t* sample_index, float* out_o, float* out_d,
+                                       float* out_pfilm, float* out_time);
 /* out[i] = sampler value for (pixel_xy[i], sample_index[i], dim[i]). */
 pt_status pt_sobol_samples(pt_context* ctx, uint32_t n, const int32_t* pixel_xy,
                            const uint32_t* sample_index, const uint32_t* dim, float* out);
@@ -626,7 +665,17 @@ pt_status pt_scene_bvh_digest(pt_context* ctx, uint64_t* nodes_digest, uint64_t*
 #define PT_KERNELS_QUADRIC 1
 #define PT_KERNELS_DISNEY 2
 #define PT_KERNELS_MAP_LIGHT 3
+/* PT_KERNELS_MOTION (namespace ptv): a scene with an animated camera or at least one actually-animated instance (pt_scene_set_motion). */
+#define PT_KERNELS_MOTION 4
 pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out);
+
+/* Host-only utilities (no device, no context) of the motion path.  pt_motion_decompose: decompose() of core/transform/decompose.rs in
+ * float32 for a row-major 4 x 4 -- translation T3, rotation quaternion R4 (x y z w, w >= 0) and the diagonal S3 of the scale;
+ * PT_ERR_INVALID_ARGUMENT where the reference returns None or fails its invertibility assertion.  pt_motion_bounds:
+ * AnimatedTransform::motion_bounds (animated_transform.rs:154-187) of box (min xyz, max xyz) under the pair (start, end) over
+ * times2: out6 = min xyz, max xyz.  The digit in a parameter's name is the number of floats behind it. */
+pt_status pt_motion_decompose(const float* m16, float* T3, float* R4, float* S3);
+pt_status pt_motion_bounds(const float* start16, const float* end16, const float* times2, const float* box6, float* out6);
 
 pt_status pt_get_counters(pt_context* ctx, pt_counters* out);
 pt_status pt_reset_counters(pt_context* ctx);

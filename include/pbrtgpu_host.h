@@ -68,13 +68,19 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
  * same message.  Non-black "scatterdistance" without "thin", and a colour texture behind a float parameter, are refused.
  * PTH_FEATURE_POINT_LIGHTS: LightSource "goniometric" and "projection" become pt_map_light records (pth_scene_get_map_lights; their
  * "mapname" a three-channel pyramid among the descriptor's images, a 1 x 1 image of ones without it) and LightSource "point" a
- * pt_delta_light of kind PT_DELTA_POINT; without the bit the three are refused as before, each with the same message.  pbrt_gpu sets
- * all five. */
+ * pt_delta_light of kind PT_DELTA_POINT; without the bit the three are refused as before, each with the same message.
+ * PTH_FEATURE_MOTION_BLUR: an ObjectInstance under a CTM whose two slots differ becomes an instance (the first slot) plus a
+ * pt_motion_instance record (the second); an animated Shape becomes an implicit object with one such instance at that place of the world
+ * list, built under the identity, with the warning "Ignoring currently set area light when creating animated shape" and no light; an
+ * animated camera gives pt_motion.camera_to_world_end; TransformTimes arrives in pt_motion.transform_times (pth_scene_get_motion).  An
+ * animated Shape inside ObjectBegin (two levels of transforms) and projective end transforms are refused by name.  Without the bit the
+ * three kinds are refused as before, each with the same message.  pbrt_gpu sets all six. */
 #define PTH_FEATURE_MIX_MATERIAL 1u
 #define PTH_FEATURE_DELTA_LIGHTS 2u
 #define PTH_FEATURE_QUADRIC_SHAPES 4u
 #define PTH_FEATURE_DISNEY_MATERIAL 8u
 #define PTH_FEATURE_POINT_LIGHTS 16u
+#define PTH_FEATURE_MOTION_BLUR 32u
 pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
@@ -95,6 +101,9 @@ const pt_map_light* pth_scene_get_map_lights(const pth_scene* s, uint32_t* n);
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
 /* The scene's Material "disney" records (for pt_scene_set_disney); *n receives their count.  Valid until pth_scene_free. */
 const pt_disney* pth_scene_get_disney(const pth_scene* s, uint32_t* n);
+/* The scene's motion, parsed with PTH_FEATURE_MOTION_BLUR (for pt_scene_set_motion): NULL when neither the camera nor an instance carries
+ * a second transform.  Valid until pth_scene_free. */
+const pt_motion* pth_scene_get_motion(pth_scene* s);
 /* Integrator "aov": its "target" (a pt_aov_target, default uv) and "scale" (default 1), for pt_scene_set_aov.  Other integrators: the defaults. */
 void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale);
 /* Film "filename" parameter (default "pbrt.exr"). */

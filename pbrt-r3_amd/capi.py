@@ -20,6 +20,7 @@ PT_MATERIAL_DISNEY = 10
  PT_DISNEY_CLEARCOATGLOSS, PT_DISNEY_SPECTRANS, PT_DISNEY_FLATNESS, PT_DISNEY_DIFFTRANS) = range(10)
 PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
 PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES, PTH_FEATURE_DISNEY_MATERIAL, PTH_FEATURE_POINT_LIGHTS = 1, 2, 4, 8, 16
+PTH_FEATURE_MOTION_BLUR = 32
 PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER, PT_SHAPE_DISK = 0, 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
@@ -126,6 +127,16 @@ class pt_instance(C.Structure):
                 ("before_triangle", C.c_uint32), ("order", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class pt_motion_instance(C.Structure):
+    _fields_ = [("instance", C.c_uint32), ("instance_to_world_end", C.c_float * 16), ("world_to_instance_end", C.c_float * 16)]
+
+
+class pt_motion(C.Structure):
+    """Motion blur (pt_scene_set_motion): the transforms at transform_times[1]; the descriptor's are those at transform_times[0]."""
+    _fields_ = [("transform_times", C.c_float * 2), ("camera_animated", C.c_int32), ("camera_to_world_end", C.c_float * 16),
+                ("n_instances", C.c_uint32), ("instances", C.POINTER(pt_motion_instance))]
+
+
 PT_SPHERE_REVERSE_ORIENTATION = 1
 
 
@@ -202,7 +213,10 @@ SYMBOLS = [
     "pt_bvh_leaf_order", "pt_bsdf_eval", "pt_bsdf_sample", "pt_set_bvh_build", "pt_scene_bvh_digest",
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_pdf_from", "pt_light_le", "pt_scene_set_alpha_masks",
     "pt_scene_set_aov", "pt_scene_set_delta_lights", "pt_scene_set_disney", "pt_scene_set_map_lights", "pt_scene_kernel_set",
+    "pt_scene_set_motion", "pt_trace_closest_time", "pt_trace_any_time", "pt_trace_wavefront_time", "pt_generate_camera_rays_time",
+    "pt_motion_decompose", "pt_motion_bounds",
 ]
+PT_KERNELS_BASE, PT_KERNELS_QUADRIC, PT_KERNELS_DISNEY, PT_KERNELS_MAP_LIGHT, PT_KERNELS_MOTION = 0, 1, 2, 3, 4
 
 _lib = None
 
@@ -267,7 +281,7 @@ def tiles_array(tiles):
 HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pth_parse_string_opts", "pth_scene_get_desc", "pth_scene_output_filename",
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
-                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_scene_get_map_lights", "pth_parse_file_features", "pth_parse_string_features",
+                "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_scene_get_map_lights", "pth_scene_get_motion", "pth_parse_file_features", "pth_parse_string_features",
                 "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
 
 
@@ -280,12 +294,14 @@ class ParsedScene:
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
     def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False,
-                 disney_materials=False, point_lights=False):
+                 disney_materials=False, point_lights=False, motion_blur=False):
         """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
         mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before.
         quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before.
         disney_materials: take Material "disney" (PTH_FEATURE_DISNEY_MATERIAL, the same way); off, it is refused as before.
-        point_lights: take LightSource "goniometric", "projection" and "point" (PTH_FEATURE_POINT_LIGHTS, the same way); off, they are refused as before."""
+        point_lights: take LightSource "goniometric", "projection" and "point" (PTH_FEATURE_POINT_LIGHTS, the same way); off, they are refused as before.
+        motion_blur: take animated ObjectInstance, Shape and Camera transforms (PTH_FEATURE_MOTION_BLUR, the same way; .motion is then the
+        pt_motion record, or None when nothing moves); off, they are refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -306,11 +322,11 @@ class ParsedScene:
         feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         features = (PTH_FEATURE_MIX_MATERIAL if mix_materials else 0) | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0) | \
                    (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0) | (PTH_FEATURE_DISNEY_MATERIAL if disney_materials else 0) | \
-                   (PTH_FEATURE_POINT_LIGHTS if point_lights else 0)
-        if (mix_materials or quadric_shapes or disney_materials or point_lights) and filename is not None:
+                   (PTH_FEATURE_POINT_LIGHTS if point_lights else 0) | (PTH_FEATURE_MOTION_BLUR if motion_blur else 0)
+        if (mix_materials or quadric_shapes or disney_materials or point_lights or motion_blur) and filename is not None:
             L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
             st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
-        elif mix_materials or quadric_shapes or disney_materials or point_lights:
+        elif mix_materials or quadric_shapes or disney_materials or point_lights or motion_blur:
             L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
             st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
         elif filename is not None and delta_lights:
@@ -357,6 +373,12 @@ class ParsedScene:
         tgt, scl = C.c_int32(), C.c_float()
         L.pth_scene_get_aov(self.h, C.byref(tgt), C.byref(scl))
         self.aov = (tgt.value, scl.value)         # Integrator "aov": (pt_aov_target, scale)
+        self.motion = None
+        if motion_blur:                           # the motion record (its instance records stay the parsed scene's, which this object keeps alive)
+            L.pth_scene_get_motion.argtypes = [C.c_void_p]
+            L.pth_scene_get_motion.restype = C.POINTER(pt_motion)
+            mo = L.pth_scene_get_motion(self.h)
+            self.motion = mo.contents if mo else None
 
     @property
     def output_filename(self):
@@ -547,6 +569,10 @@ class Context:
         aov = getattr(scene, "aov", None)
         if aov is not None:          # Integrator "aov": (target, scale); otherwise the upload takes the defaults (uv, 1)
             self._check(self.lib.pt_scene_set_aov(self.h, C.c_int32(int(aov[0])), C.c_float(float(aov[1]))))
+        mo = getattr(scene, "motion", None)
+        if mo is not None:           # motion blur: a pt_motion (an upload consumes it, so a scene without one has nothing to clear)
+            self.lib.pt_scene_set_motion.argtypes = [C.c_void_p, C.POINTER(pt_motion)]
+            self._check(self.lib.pt_scene_set_motion(self.h, C.byref(mo)))
         self._check(self.lib.pt_scene_upload(self.h, C.byref(scene.desc)))
         info = pt_scene_info()
         self._check(self.lib.pt_scene_info_get(self.h, C.byref(info)))
@@ -558,7 +584,7 @@ class Context:
         self._check(self.lib.pt_set_bvh_build(self.h, int(where)))
 
     def kernel_set(self):
-        """Which build of the kernels renders the uploaded scene: 0 base, 1 quadric (ptq), 2 disney (ptd), 3 map light (ptm)."""
+        """Which build of the kernels renders the uploaded scene: 0 base, 1 quadric (ptq), 2 disney (ptd), 3 map light (ptm), 4 motion (ptv)."""
         k = C.c_int32()
         self.lib.pt_scene_kernel_set.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         self._check(self.lib.pt_scene_kernel_set(self.h, C.byref(k)))
@@ -616,35 +642,60 @@ class Context:
         self._check(self.lib.pt_film_resolve_rgb(self.h, _ptr(out)))
         return out
 
-    def trace_closest(self, o, d, tmax):
+    def trace_closest(self, o, d, tmax, time=None):
+        """time: one Ray::time per ray (pt_trace_closest_time); None traces at time 0."""
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
         tmax = np.ascontiguousarray(tmax, np.float32)
         n = len(tmax)
         out = np.empty(n, HIT_DTYPE)
+        if time is not None:
+            time = np.ascontiguousarray(time, np.float32)
+            assert len(time) == n
+            self.lib.pt_trace_closest_time.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+            self._check(self.lib.pt_trace_closest_time(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(time), _ptr(out)))
+            return out
         self._check(self.lib.pt_trace_closest(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(out)))
         return out
 
-    def trace_any(self, o, d, tmax):
+    def trace_any(self, o, d, tmax, time=None):
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
         tmax = np.ascontiguousarray(tmax, np.float32)
         n = len(tmax)
         out = np.empty(n, np.uint8)
+        if time is not None:
+            time = np.ascontiguousarray(time, np.float32)
+            assert len(time) == n
+            self.lib.pt_trace_any_time.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+            self._check(self.lib.pt_trace_any_time(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(time), _ptr(out)))
+            return out
         self._check(self.lib.pt_trace_any(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(out)))
         return out
 
-    def trace_wavefront(self, o, d, tmax, kind):
+    def trace_wavefront(self, o, d, tmax, kind, time=None):
         """Rays through the renderer's own traversal kernel; kind: 1 continuation, 2 shadow, 3 probe.  Returns (hits, occluded)."""
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
         tmax = np.ascontiguousarray(tmax, np.float32); kind = np.ascontiguousarray(kind, np.uint8)
         n = len(tmax)
         out = np.empty(n, HIT_DTYPE); occ = np.empty(n, np.uint8)
+        if time is not None:
+            time = np.ascontiguousarray(time, np.float32)
+            assert len(time) == n
+            self.lib.pt_trace_wavefront_time.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7
+            self._check(self.lib.pt_trace_wavefront_time(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(time), _ptr(kind), _ptr(out), _ptr(occ)))
+            return out, occ
         self._check(self.lib.pt_trace_wavefront(self.h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(kind), _ptr(out), _ptr(occ)))
         return out, occ
 
-    def generate_camera_rays(self, pixel_xy, sample_index):
+    def generate_camera_rays(self, pixel_xy, sample_index, with_time=False):
+        """(o, d, p_film), and with with_time the rays' times as a fourth array (pt_generate_camera_rays_time)."""
         pixel_xy = np.ascontiguousarray(pixel_xy, np.int32); sample_index = np.ascontiguousarray(sample_index, np.uint32)
         n = len(sample_index)
         o = np.empty((n, 3), np.float32); d = np.empty((n, 3), np.float32); pf = np.empty((n, 2), np.float32)
+        if with_time:
+            tm = np.empty(n, np.float32)
+            self.lib.pt_generate_camera_rays_time.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+            self._check(self.lib.pt_generate_camera_rays_time(self.h, n, _ptr(pixel_xy), _ptr(sample_index), _ptr(o), _ptr(d), _ptr(pf), _ptr(tm)))
+            return o, d, pf, tm
         self._check(self.lib.pt_generate_camera_rays(self.h, n, _ptr(pixel_xy), _ptr(sample_index), _ptr(o), _ptr(d), _ptr(pf)))
         return o, d, pf
 
@@ -722,3 +773,28 @@ class Context:
 
     def reset_counters(self):
         self._check(self.lib.pt_reset_counters(self.h))
+
+
+def motion_decompose(m, lib=None):
+    """pt_motion_decompose of a 4 x 4 (row-major): (T[3], R[4] as x y z w, S[3]) in float32; raises PtError where the reference's decompose fails."""
+    L = lib or load_library()
+    a = np.ascontiguousarray(m, np.float32).reshape(16)
+    T = np.empty(3, np.float32); R = np.empty(4, np.float32); S = np.empty(3, np.float32)
+    L.pt_motion_decompose.argtypes = [C.c_void_p] * 4
+    st = L.pt_motion_decompose(_ptr(a), _ptr(T), _ptr(R), _ptr(S))
+    if st != 0:
+        raise PtError(st, "pt_motion_decompose failed")
+    return T, R, S
+
+
+def motion_bounds(start, end, times, box, lib=None):
+    """pt_motion_bounds: AnimatedTransform::motion_bounds of box (min xyz, max xyz) under (start, end) over times; 6 floats."""
+    L = lib or load_library()
+    a = np.ascontiguousarray(start, np.float32).reshape(16); b = np.ascontiguousarray(end, np.float32).reshape(16)
+    t = np.ascontiguousarray(times, np.float32).reshape(2); bx = np.ascontiguousarray(box, np.float32).reshape(6)
+    out = np.empty(6, np.float32)
+    L.pt_motion_bounds.argtypes = [C.c_void_p] * 5
+    st = L.pt_motion_bounds(_ptr(a), _ptr(b), _ptr(t), _ptr(bx), _ptr(out))
+    if st != 0:
+        raise PtError(st, "pt_motion_bounds failed")
+    return out

@@ -75,6 +75,7 @@ static const pt_disney* g_disney = nullptr;   // Material "disney" records of th
 static uint32_t g_n_disney = 0;
 static const pt_map_light* g_map_lights = nullptr;   // LightSource "goniometric" / "projection" of the parsed scene (pth_scene_get_map_lights), handed to every upload
 static uint32_t g_n_map_lights = 0;
+static const pt_motion* g_motion = nullptr;   // the parsed scene's motion (pth_scene_get_motion; NULL: nothing moves), handed to every upload
 static int32_t g_aov_target = PT_AOV_UV;      // Integrator "aov" of the parsed scene (pth_scene_get_aov), handed to every upload
 static float g_aov_scale = 1.0f;
 static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* inf, uint32_t n_inf, const pt_delta_light* dl, uint32_t n_dl, const pt_alpha_mask* am, uint32_t n_am, const std::vector<int>& devs, std::vector<float>& rgb, pt_scene_info* info_out, pt_counters* total,
@@ -116,6 +117,7 @@ static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* i
         if (!check(r, pt_scene_set_alpha_masks(ctxs[(size_t)r], n_am, am), "alpha masks")) return;
         if (!check(r, pt_scene_set_disney(ctxs[(size_t)r], g_n_disney, g_disney), "disney records")) return;
         if (!check(r, pt_scene_set_aov(ctxs[(size_t)r], g_aov_target, g_aov_scale), "aov target")) return;
+        if (!check(r, pt_scene_set_motion(ctxs[(size_t)r], g_motion), "motion")) return;
         check(r, pt_scene_upload(ctxs[(size_t)r], dsc), "scene upload");
     });
     double secs = 0;
@@ -222,7 +224,7 @@ int main(int argc, char** argv) {
     opts.delta_lights = 1;           // LightSource "spot" / "distant" render here (pt_scene_set_delta_lights below)
     char err[1024] = {0};
     pth_scene* scene = nullptr;
-    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS | PTH_FEATURE_QUADRIC_SHAPES | PTH_FEATURE_DISNEY_MATERIAL | PTH_FEATURE_POINT_LIGHTS, &scene, err, sizeof(err));      // Material "mix" renders here
+    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS | PTH_FEATURE_QUADRIC_SHAPES | PTH_FEATURE_DISNEY_MATERIAL | PTH_FEATURE_POINT_LIGHTS | PTH_FEATURE_MOTION_BLUR, &scene, err, sizeof(err));      // Material "mix" renders here
     if (st != PT_OK) { std::fprintf(stderr, "pbrt_gpu: %s\n", err); return 1; }
     if (!quiet && pth_scene_warnings(scene)[0]) std::fprintf(stderr, "%s", pth_scene_warnings(scene));
     uint32_t n_inf_lights = 0;
@@ -234,6 +236,7 @@ int main(int argc, char** argv) {
     pth_scene_get_aov(scene, &g_aov_target, &g_aov_scale);
     g_disney = pth_scene_get_disney(scene, &g_n_disney);
     g_map_lights = pth_scene_get_map_lights(scene, &g_n_map_lights);
+    g_motion = pth_scene_get_motion(scene);
     if (outfile.empty()) {
         outfile = pth_scene_output_filename(scene);
         size_t dot = outfile.find_last_of('.');
@@ -278,6 +281,7 @@ int main(int argc, char** argv) {
     if (pt_scene_set_disney(ctx, g_n_disney, g_disney) != PT_OK) return fail("disney records");
     if (pt_scene_set_map_lights(ctx, g_n_map_lights, g_map_lights) != PT_OK) return fail("goniometric / projection lights");
     if (pt_scene_set_aov(ctx, g_aov_target, g_aov_scale) != PT_OK) return fail("aov target");
+    if (pt_scene_set_motion(ctx, g_motion) != PT_OK) return fail("motion");
     if (pt_scene_upload(ctx, pth_scene_get_desc(scene)) != PT_OK) return fail("scene upload");
     pt_scene_info info;
     pt_scene_info_get(ctx, &info);

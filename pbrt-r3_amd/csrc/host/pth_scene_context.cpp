@@ -148,6 +148,10 @@ public:
     std::vector<pt_infinite_light> infinite_lights;
     std::vector<pt_delta_light> delta_lights;
     std::vector<pt_map_light> map_lights;        // LightSource "goniometric" / "projection" (PTH_FEATURE_POINT_LIGHTS)
+    bool accept_motion = false;                  // PTH_FEATURE_MOTION_BLUR: animated instances, shapes and camera become pt_motion records (off: refused, as before)
+    pt_motion motion{{0.0f, 1.0f}, 0, {0.0f}, 0, nullptr};                          // TransformTimes (kept whatever the flag says), the camera's end transform, the records below (pth_scene_get_motion)
+    std::vector<pt_motion_instance> motion_instances;
+    uint32_t n_animated_shapes = 0;
     bool accept_quadrics = false;                // PTH_FEATURE_QUADRIC_SHAPES: Shape "cylinder" and Shape "disk" are taken (off: refused, as before)
     bool accept_mix = false;                     // PTH_FEATURE_MIX_MATERIAL: Material "mix" is taken (off: refused, as before)
     bool accept_disney = false;                  // PTH_FEATURE_DISNEY_MATERIAL: Material "disney" is taken (off: refused, as before)
@@ -208,7 +212,7 @@ public:
     void pbrt_active_transform_all() override { bits.back() = kAllBits; }
     void pbrt_active_transform_end_time() override { bits.back() = kEndBit; }
     void pbrt_active_transform_start_time() override { bits.back() = kStartBit; }
-    void pbrt_transform_times(float, float) override {}
+    void pbrt_transform_times(float start, float end) override { motion.transform_times[0] = start; motion.transform_times[1] = end; }      // scene_context.rs:945-951
 
     // ---- options
     void pbrt_pixel_filter(const std::string& name, const ParamSet& p) override { filter_name = name; filter_params = p; }
@@ -614,14 +618,30 @@ public:
         auto it = object_ids.find(name);
         if (it == object_ids.end()) return;                          // unknown name: nothing happens (:1365)
         const TransformSet& ts = transforms.back();
-        if (std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) != 0) { fail("animated instance transforms are outside the accelerated path"); return; }
+        push_instance(it->second, ts);
+    }
+    // The TransformedPrimitive of an ObjectInstance (scene_context.rs:1349-1391) or of an animated Shape (:1233-1293) under the CTM pair `ts`:
+    // the instance at the first slot, and with PTH_FEATURE_MOTION_BLUR a motion record for a pair whose slots differ.
+    void push_instance(uint32_t object, const TransformSet& ts) {
+        const bool animated = std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) != 0;
+        if (animated && !accept_motion) { fail("animated instance transforms are outside the accelerated path"); return; }
         const Xf& c = ts.t[0];
         if (c.m.a[12] != 0.0f || c.m.a[13] != 0.0f || c.m.a[14] != 0.0f || c.m.a[15] != 1.0f) { fail("ObjectInstance under a projective transform is outside the accelerated path"); return; }
+        if (animated) {
+            const Xf& e = ts.t[1];
+            if (e.m.a[12] != 0.0f || e.m.a[13] != 0.0f || e.m.a[14] != 0.0f || e.m.a[15] != 1.0f) { fail("animated transform whose end is projective is outside the accelerated path"); return; }
+            pt_motion_instance mi;
+            std::memset(&mi, 0, sizeof(mi));
+            mi.instance = (uint32_t)instances.size();
+            std::memcpy(mi.instance_to_world_end, e.m.a, 64);
+            std::memcpy(mi.world_to_instance_end, e.inv.a, 64);
+            motion_instances.push_back(mi);
+        }
         pt_instance in;
         std::memset(&in, 0, sizeof(in));
         std::memcpy(in.instance_to_world, c.m.a, 64);
         std::memcpy(in.world_to_instance, c.inv.a, 64);
-        in.object = it->second;
+        in.object = object;
         in.before_triangle = (uint32_t)tri_mesh.size();
         in.order = n_extra++;
         instances.push_back(in);
@@ -923,7 +943,31 @@ public:
         return true;
     }
 
+    // An animated Shape (scene_context.rs:1233-1293): the area light is ignored with a warning, the shape is built under the identity,
+    // and one TransformedPrimitive with the CTM pair wraps it -- here an implicit object with one instance at this place of the world list.
     void pbrt_shape(const std::string& name, const ParamSet& p) override {
+        if (!error.empty()) return;
+        const TransformSet ts = transforms.back();
+        if (!accept_motion || std::memcmp(&ts.t[0].m, &ts.t[1].m, sizeof(M44)) == 0) { shape_under_ctm(name, p); return; }
+        if (cur_object) { fail("animated Shape inside ObjectBegin (a TransformedPrimitive inside an instance: two levels of transforms) is outside the accelerated path"); return; }
+        const std::string saved_light = gstates.back().area_light_name;
+        gstates.back().area_light_name.clear();
+        const uint32_t object = (uint32_t)object_ids.size();          // the id the implicit object gets if the shape yields a primitive
+        const size_t n_tris = tri_mesh.size(), n_sph = spheres.size();
+        TransformSet ident;
+        ident.t[0].m = ident.t[0].inv = ident.t[1].m = ident.t[1].inv = m_identity();
+        transforms.back() = ident;
+        cur_object = object + 1;
+        shape_under_ctm(name, p);
+        cur_object = 0;
+        transforms.back() = ts;
+        gstates.back().area_light_name = saved_light;
+        if (!error.empty() || (tri_mesh.size() == n_tris && spheres.size() == n_sph)) return;      // (a shape that made no primitive has nothing to wrap: no object, no warning)
+        if (!saved_light.empty()) warn("Ignoring currently set area light when creating animated shape");
+        object_ids[std::string("\x01 animated shape ") + std::to_string(n_animated_shapes++)] = object;      // (a name no ObjectBegin can give)
+        push_instance(object, ts);
+    }
+    void shape_under_ctm(const std::string& name, const ParamSet& p) {
         if (!error.empty()) return;
         const bool quadric = accept_quadrics && (name == "cylinder" || name == "disk");
         if (!quadric && name != "trianglemesh" && name != "plymesh" && name != "sphere" && name != "loopsubdiv" && name != "nurbs" && name != "heightfield") {
@@ -1206,7 +1250,13 @@ public:
         TransformSet c2w;
         if (have_camera) c2w = named_cs["camera"];
         else { c2w.t[0].m = c2w.t[0].inv = c2w.t[1].m = c2w.t[1].inv = m_identity(); }
-        if (std::memcmp(&c2w.t[0].m, &c2w.t[1].m, sizeof(M44)) != 0) { fail("animated camera transforms are outside the accelerated path"); return; }
+        if (std::memcmp(&c2w.t[0].m, &c2w.t[1].m, sizeof(M44)) != 0) {
+            if (!accept_motion) { fail("animated camera transforms are outside the accelerated path"); return; }
+            const float* e = c2w.t[1].m.a;          // AnimatedTransform of the CTM pair (scene_context.rs:643-655)
+            if (e[12] != 0.0f || e[13] != 0.0f || e[14] != 0.0f || e[15] != 1.0f) { fail("animated camera whose end transform is projective is outside the accelerated path"); return; }
+            motion.camera_animated = 1;
+            std::memcpy(motion.camera_to_world_end, e, 64);
+        }
         std::memcpy(desc.camera_to_world, c2w.t[0].m.a, 64);
         float so = camera_params.find_one_float("shutteropen", 0.0f), sc = camera_params.find_one_float("shutterclose", 1.0f);
         if (sc < so) std::swap(so, sc);
@@ -1361,6 +1411,7 @@ pt_status pth_parse_file_features(const char* filename, const pth_options* opts,
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
     s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
+    s->ctx.accept_motion = (features & PTH_FEATURE_MOTION_BLUR) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_file(filename, s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);
@@ -1374,6 +1425,7 @@ pt_status pth_parse_string_features(const char* text, const char* work_dir, cons
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
     s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
+    s->ctx.accept_motion = (features & PTH_FEATURE_MOTION_BLUR) != 0;
     std::string perr;
     bool ok = pth::pbrt_parse_string(text, work_dir ? work_dir : ".", s->ctx, &perr);
     return finish_with_options(s, ok, perr, opts, out, err, err_cap);
@@ -1420,6 +1472,12 @@ const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n) 
 const pt_disney* pth_scene_get_disney(const pth_scene* s, uint32_t* n) {
     if (n) *n = s ? (uint32_t)s->ctx.disney_records.size() : 0u;
     return (s && !s->ctx.disney_records.empty()) ? s->ctx.disney_records.data() : nullptr;
+}
+const pt_motion* pth_scene_get_motion(pth_scene* s) {
+    if (!s || (!s->ctx.motion.camera_animated && s->ctx.motion_instances.empty())) return nullptr;
+    s->ctx.motion.n_instances = (uint32_t)s->ctx.motion_instances.size();
+    s->ctx.motion.instances = s->ctx.motion_instances.empty() ? nullptr : s->ctx.motion_instances.data();
+    return &s->ctx.motion;
 }
 void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale) {
     if (target) *target = s ? s->ctx.aov_target : (int32_t)PT_AOV_UV;

@@ -354,7 +354,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
             uint32_t* qa = ctx->d_qa.as<uint32_t>();
             uint32_t* qb = ctx->d_qb.as<uint32_t>();
             Q.cur = qa; Q.next = qb;
-            PT_HIP(ptk_gen(ctx->stream, ctx->grid_wide, sc, ctx->paths, Q, d_pix, n_pix, s0, ns, cnt));
+            PT_HIP(ptk_gen_any(ctx, ctx->stream, ctx->grid_wide, sc, ctx->paths, Q, d_pix, n_pix, s0, ns, cnt));
             if (ao) {
                 // camera rays -> closest hits -> ao_samples occlusion rays per hit (compacted) -> any-hit -> ordered sum
                 const uint32_t n_paths = n_pix * ns;
@@ -653,7 +653,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go
         unsigned long long sp[16];
-        if (ctx->maplight_kernels ? ptm::ptk_shade_prof_read(sp) : ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
+        if (ctx->motion_kernels ? ptv::ptk_shade_prof_read(sp) : ctx->maplight_kernels ? ptm::ptk_shade_prof_read(sp) : ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
             double tot = 0;
             for (int k = 0; k < 16; k++) if (k != 12) tot += (double)sp[k];
             static const char* names[16] = {"surface", "emit+bsdf setup", "grid+pick light", "u_light,u_scat", "light sample+f", "bsdf MIS+probe", "pend stores",
@@ -806,7 +806,8 @@ pt_status pt_film_resolve_rgb(pt_context* ctx, float* rgb_out) {
     return PT_OK;
 }
 
-static pt_status trace_batch(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out, uint8_t* occ, int any_hit) {
+// time: a time per ray (pt_trace_closest_time / pt_trace_any_time), read by a scene with a moving instance; nullptr: every ray at time 0
+static pt_status trace_batch(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out, uint8_t* occ, int any_hit, const float* time = nullptr) {
     if (!ctx || !o || !d || !tmax || (!any_hit && !out) || (any_hit && !occ)) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (n == 0) return PT_OK;
@@ -819,7 +820,18 @@ static pt_status trace_batch(pt_context* ctx, uint32_t n, const float* o, const 
     PT_HIP(hipMemcpy(d_t.p, tmax, (size_t)n * 4, hipMemcpyHostToDevice));
     PT_HIP(hipMemsetAsync(ctx->d_ticket.p, 0, 16, ctx->stream));
     hipEvent_t a = get_event(ctx, 0), b = get_event(ctx, 1);
+    DevBuf d_time;
+    const bool timed = time && ctx->motion_instances;
+    if (timed) {
+        PT_HIP(d_time.alloc((size_t)n * 4));
+        PT_HIP(hipMemcpy(d_time.p, time, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
     PT_HIP(hipEventRecord(a, ctx->stream));
+    if (timed)
+        PT_HIP(ptv::ptk_trace_batch_time(ctx->stream, ctx->grid_trace, ctx->sc, n, d_o.as<float>(), d_d.as<float>(), d_t.as<float>(), d_time.as<float>(),
+                                         any_hit ? nullptr : d_out.as<pt_hit>(), any_hit ? d_out.as<uint8_t>() : nullptr, any_hit, ctx->d_ticket.as<uint32_t>(),
+                                         ctx->d_counters.as<PtCounters>(), ctx->d_spill.as<uint32_t>(), ctx->spill_depth, ctx->d_err.as<uint32_t>(), ctx->scene_alpha ? 1 : 0));
+    else
     PT_HIP(ptk_trace_batch_any(ctx, ctx->stream, ctx->grid_trace, ctx->sc, n, d_o.as<float>(), d_d.as<float>(), d_t.as<float>(), any_hit ? nullptr : d_out.as<pt_hit>(),
                            any_hit ? d_out.as<uint8_t>() : nullptr, any_hit, ctx->d_ticket.as<uint32_t>(), ctx->d_counters.as<PtCounters>(),
                            ctx->d_spill.as<uint32_t>(), ctx->spill_depth, ctx->d_err.as<uint32_t>(), ctx->scene_alpha ? 1 : 0));
@@ -843,11 +855,31 @@ pt_status pt_trace_closest(pt_context* ctx, uint32_t n, const float* o, const fl
 pt_status pt_trace_any(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, uint8_t* occluded_out) {
     return trace_batch(ctx, n, o, d, tmax, nullptr, occluded_out, 1);
 }
+pt_status pt_trace_closest_time(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time, pt_hit* out) {
+    if (!time) return PT_ERR_INVALID_ARGUMENT;
+    return trace_batch(ctx, n, o, d, tmax, out, nullptr, 0, time);
+}
+pt_status pt_trace_any_time(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time, uint8_t* occluded_out) {
+    if (!time) return PT_ERR_INVALID_ARGUMENT;
+    return trace_batch(ctx, n, o, d, tmax, nullptr, occluded_out, 1, time);
+}
 
 // Caller rays through the kernel the renderer itself traces with (see k_wavefront_results): ray i becomes path slot i; the
 // continuation / shadow / probe queues list the rays of each kind in caller order, exactly the mix one bounce launches.
+static pt_status trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time, const uint8_t* kind, pt_hit* out,
+                                 uint8_t* occluded_out);
 pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const uint8_t* kind, pt_hit* out,
                              uint8_t* occluded_out) {
+    return trace_wavefront(ctx, n, o, d, tmax, nullptr, kind, out, occluded_out);
+}
+pt_status pt_trace_wavefront_time(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time, const uint8_t* kind,
+                                  pt_hit* out, uint8_t* occluded_out) {
+    if (!time) return PT_ERR_INVALID_ARGUMENT;
+    return trace_wavefront(ctx, n, o, d, tmax, time, kind, out, occluded_out);
+}
+// (time: the w lane of a ray's direction, which only the motion build reads; nullptr: time 0)
+static pt_status trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const float* time, const uint8_t* kind, pt_hit* out,
+                                 uint8_t* occluded_out) {
     if (!ctx || !o || !d || !tmax || !kind || !out || !occluded_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (n == 0) return PT_OK;
@@ -859,7 +891,7 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
         ids[kind[i] - 1].push_back(i);
         for (int k = 0; k < 3; k++) { o4[4 * (size_t)i + k] = o[3 * (size_t)i + k]; d4[4 * (size_t)i + k] = d[3 * (size_t)i + k]; }
         o4[4 * (size_t)i + 3] = tmax[i];
-        d4[4 * (size_t)i + 3] = 0.0f;
+        d4[4 * (size_t)i + 3] = time ? time[i] : 0.0f;
     }
     pt_status st;
     if ((st = ensure_pool(ctx, std::max<size_t>(n, 65536))) != PT_OK) return st;
@@ -903,8 +935,21 @@ pt_status pt_trace_wavefront(pt_context* ctx, uint32_t n, const float* o, const 
     return PT_OK;
 }
 
+static pt_status camera_rays(pt_context* ctx, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
+                             float* out_pfilm, float* out_time);
 pt_status pt_generate_camera_rays(pt_context* ctx, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
                                   float* out_pfilm) {
+    return camera_rays(ctx, n, pixel_xy, sample_index, out_o, out_d, out_pfilm, nullptr);
+}
+pt_status pt_generate_camera_rays_time(pt_context* ctx, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
+                                       float* out_pfilm, float* out_time) {
+    if (!out_time) return PT_ERR_INVALID_ARGUMENT;
+    return camera_rays(ctx, n, pixel_xy, sample_index, out_o, out_d, out_pfilm, out_time);
+}
+// out_time: the rays' times as well.  A scene that moves asks its own k_gen twin (the ray depends on the time); every other scene gets the
+// time from the sampler's fifth dimension, lerp(u, shutter_open, shutter_close) in float32 as perspective.rs:111-117 has it.
+static pt_status camera_rays(pt_context* ctx, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
+                             float* out_pfilm, float* out_time) {
     if (!ctx || !pixel_xy || !sample_index || !out_o || !out_d || !out_pfilm) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
     if (n == 0) return PT_OK;
@@ -914,8 +959,25 @@ pt_status pt_generate_camera_rays(pt_context* ctx, uint32_t n, const int32_t* pi
     PT_HIP(d_o.alloc((size_t)n * 12)); PT_HIP(d_d.alloc((size_t)n * 12)); PT_HIP(d_pf.alloc((size_t)n * 8));
     PT_HIP(hipMemcpy(d_px.p, pixel_xy, (size_t)n * 8, hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(d_si.p, sample_index, (size_t)n * 4, hipMemcpyHostToDevice));
-    PT_HIP(ptk_camera_rays(ctx->stream, ctx->sc, n, d_px.as<int32_t>(), d_si.as<uint32_t>(), d_o.as<float>(), d_d.as<float>(), d_pf.as<float>()));
+    DevBuf d_tm, d_dim;
+    if (out_time) PT_HIP(d_tm.alloc((size_t)n * 4));
+    if (out_time && ctx->motion_kernels)
+        PT_HIP(ptv::ptk_camera_rays_time(ctx->stream, ctx->sc, n, d_px.as<int32_t>(), d_si.as<uint32_t>(), d_o.as<float>(), d_d.as<float>(), d_pf.as<float>(), d_tm.as<float>()));
+    else {
+        PT_HIP(ptk_camera_rays_any(ctx, ctx->stream, ctx->sc, n, d_px.as<int32_t>(), d_si.as<uint32_t>(), d_o.as<float>(), d_d.as<float>(), d_pf.as<float>()));
+        if (out_time) {
+            const std::vector<uint32_t> dims(n, 4u);
+            PT_HIP(d_dim.alloc((size_t)n * 4));
+            PT_HIP(hipMemcpy(d_dim.p, dims.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+            PT_HIP(ptk_sobol_samples(ctx->stream, ctx->sc, n, d_px.as<int32_t>(), d_si.as<uint32_t>(), d_dim.as<uint32_t>(), d_tm.as<float>()));
+        }
+    }
     PT_HIP(hipStreamSynchronize(ctx->stream));
+    if (out_time) {
+        PT_HIP(hipMemcpy(out_time, d_tm.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (!ctx->motion_kernels)
+            for (uint32_t i = 0; i < n; i++) out_time[i] = (1.0f - out_time[i]) * ctx->sc.cam.shutter_open + out_time[i] * ctx->sc.cam.shutter_close;
+    }
     PT_HIP(hipMemcpy(out_o, d_o.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     PT_HIP(hipMemcpy(out_d, d_d.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     PT_HIP(hipMemcpy(out_pfilm, d_pf.p, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -1076,7 +1138,7 @@ pt_status pt_set_bvh_build(pt_context* ctx, int where) {
 pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out) {
     if (!ctx || !set_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    *set_out = ctx->maplight_kernels ? PT_KERNELS_MAP_LIGHT : (ctx->disney_kernels ? PT_KERNELS_DISNEY : (ctx->quadric_kernels ? PT_KERNELS_QUADRIC : PT_KERNELS_BASE));
+    *set_out = ctx->motion_kernels ? PT_KERNELS_MOTION : ctx->maplight_kernels ? PT_KERNELS_MAP_LIGHT : (ctx->disney_kernels ? PT_KERNELS_DISNEY : (ctx->quadric_kernels ? PT_KERNELS_QUADRIC : PT_KERNELS_BASE));
     return PT_OK;
 }
 

@@ -64,6 +64,9 @@ struct pt_context {
     std::vector<pt_map_light> map_lights;           // pt_scene_set_map_lights: the next upload's goniometric / projection lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
     std::vector<pt_disney> disney_recs;             // pt_scene_set_disney: the next upload's Disney parameter records
+    bool next_has_motion = false;                   // pt_scene_set_motion: the next upload's motion (the instance records copied)
+    pt_motion next_motion{};
+    std::vector<pt_motion_instance> next_motion_inst;
     int32_t next_aov_target = PT_AOV_UV;            // pt_scene_set_aov: the next upload's AOV target and scale (create_aov_integrator's defaults)
     float next_aov_scale = 1.0f;
     int32_t aov_target = PT_AOV_UV;                 // of the uploaded scene (read when its integrator is PT_INTEGRATOR_AOV)
@@ -71,6 +74,8 @@ struct pt_context {
     bool quadric_kernels = false;                   // the uploaded scene holds a cylinder or a disk: it runs the kernels of namespace ptq (pt_kernels_quadric.hip)
     bool disney_kernels = false;                    // the uploaded scene holds a Material "disney": it runs the kernels of namespace ptd (pt_kernels_disney.hip)
     bool maplight_kernels = false;                  // the uploaded scene holds a goniometric or a projection light: it runs the kernels of namespace ptm (pt_kernels_maplight.hip)
+    bool motion_kernels = false;                    // the uploaded scene's camera or one of its instances moves: it runs the kernels of namespace ptv (pt_kernels_motion.hip)
+    bool motion_instances = false;                  // ... an instance does (the trace hooks with a time need their own batch kernel then)
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
@@ -150,10 +155,12 @@ struct pt_context {
 // The launchers whose kernels hold analytic-shape code (traversal, surface reconstruction, light sampling), by the scene: a cylinder or a disk asks for the second build of the kernels
 // (namespace ptq, pt_kernels_quadric.hip), every other scene runs the first.  A scene that holds a Material "disney" runs the third build (namespace ptd,
 // pt_kernels_disney.hip), which knows both the shapes and Disney's BxDFs.  A scene that holds a goniometric or a projection light runs the fourth (namespace
-// ptm, pt_kernels_maplight.hip), which knows all of that and the two lights' image lookup.
+// ptm, pt_kernels_maplight.hip), which knows all of that and the two lights' image lookup.  A scene whose camera or instances move runs the fifth (namespace ptv,
+// pt_kernels_motion.hip), which knows all of that and AnimatedTransform::interpolate; its k_gen keeps the time sample, so ray generation is dispatched as well.
 #define PTK_BY_SCENE(fn)                                                                                            \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->motion_kernels) return ptv::fn(std::forward<A>(a)...);                                             \
         if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         if (ctx->disney_kernels) return ptd::fn(std::forward<A>(a)...);                                             \
         return ctx->quadric_kernels ? ptq::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                 \
@@ -173,11 +180,14 @@ PTK_BY_SCENE(ptk_trace_batch)
 PTK_BY_SCENE(ptk_wavefront_results)
 PTK_BY_SCENE(ptk_light_hooks)
 PTK_BY_SCENE(ptk_light_pdf_from)
+PTK_BY_SCENE(ptk_gen)
+PTK_BY_SCENE(ptk_camera_rays)
 #undef PTK_BY_SCENE
 // The BSDF hooks hold no analytic-shape code: the first build serves every scene but a Disney one
 #define PTK_BY_MATERIAL(fn)                                                                                         \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->motion_kernels) return ptv::fn(std::forward<A>(a)...);                                             \
         if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         return ctx->disney_kernels ? ptd::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                  \
     }

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/pbrtgpu.h"
+#include "pt_motion.h"
 
 #define PT_WAVE 64
 #define PT_BLOCK 256
@@ -229,7 +230,9 @@ struct PtInstance {              // 144 bytes
     uint32_t direct;             // 1: one primitive, wrapped without an accelerator (no root box test)
     float root_lo[3], root_hi[3];// the accelerator's bound (QBVHAccel::intersect starts with it)
     uint32_t world_prim;         // the instance's index in the world primitive list (pt_hit.prim)
-    uint32_t pad[3];
+    uint32_t motion1;            // index of the instance's PtMotion record (scene_motions; >= 1, entry 0 is the camera's), 0 = static.  Only the
+                                 // fifth build of the kernels (pt_kernels_motion.hip) reads it
+    uint32_t pad[2];
 };
 #define PT_LIGHT_SPHERE 0x80000000u   // PtLight::mesh_flags: the light's shape is entry number bits(p0[0]) of PtScene::spheres (any kind)
 #ifdef __HIPCC__
@@ -281,7 +284,7 @@ struct PtCamera {
     float raster_to_camera[16];
     float camera_to_world[16];
     float lens_radius, focal_distance;
-    float pad[2];
+    float shutter_open, shutter_close;      // read by the motion build's k_gen only (the two words were padding)
 };
 
 struct PtFilm {
@@ -389,6 +392,10 @@ PT_HOSTDEV_ENVS inline uint32_t scene_n_mix(const PtScene& sc) { return sc.gener
 PT_HOSTDEV_ENVS inline const PtMix& material_mix(const PtScene& sc, const PtMaterial& m) {
     return reinterpret_cast<const PtMix*>(sc.materials + m.mix_base)[m.mix1 - 1u];
 }
+// The PtMotion records of a scene that moves (pt_motion.h) follow the n_instances PtInstance records in the instances buffer: entry 0 is the
+// camera's (its start transform is PtCamera::camera_to_world), entry PtInstance::motion1 an instance's.  Only pt_kernels_motion.hip reads them.
+static_assert(sizeof(PtInstance) == 144 && sizeof(PtInstance) % 16 == 0, "PtMotion records behind the instances");
+PT_HOSTDEV_ENVS inline const PtMotion* scene_motions(const PtScene& sc) { return reinterpret_cast<const PtMotion*>(sc.instances + sc.n_instances); }
 // A Disney material's parameter block, in the lobe slots its PtMaterial record does not use (PtDisneyParams above).
 PT_HOSTDEV_ENVS inline const PtDisneyParams& material_disney(const PtMaterial& m) { return *reinterpret_cast<const PtDisneyParams*>(m.lobes); }
 static_assert(sizeof(PtMaterial) % 16 == 0 && sizeof(PtMix) % 4 == 0, "the PtMix table behind the materials");

@@ -17,3 +17,11 @@ namespace ptd {
 namespace ptm {
 #include "pt_kernels_decl.inc"
 }
+// the fifth build (pt_kernels_motion.hip: scenes whose camera or instances move), and what only it has: the hooks that take a time per ray
+namespace ptv {
+#include "pt_kernels_decl.inc"
+hipError_t ptk_trace_batch_time(hipStream_t st, int grid, const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, const float* time,
+                                pt_hit* out, uint8_t* occ, int any_hit, uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err, int alpha);
+hipError_t ptk_camera_rays_time(hipStream_t st, const PtScene& sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* o, float* d,
+                                float* pf, float* time);
+}

@@ -35,7 +35,9 @@
 // pt_kernels_disney.hip includes it a third time, with PT_QUADRIC and PT_DISNEY set and PT_KERNEL_NS ptd: the BxDFs of Material "disney"
 // (pt_bxdf.h) on top of the second build, for the scenes that hold such a material.  pt_kernels_maplight.hip includes it a fourth time, with
 // PT_MAPLIGHT set as well and PT_KERNEL_NS ptm: the image lookup of the goniometric and projection lights inside delta_sample_li, on top
-// of the third build, for the scenes that hold such a light.
+// of the third build, for the scenes that hold such a light.  pt_kernels_motion.hip includes it a fifth time, with PT_MOTION set as well and
+// PT_KERNEL_NS ptv: a time per camera sample and AnimatedTransform::interpolate where a transform that moves is read (animated_at), on top
+// of the fourth build, for the scenes whose camera or instances move.
 #if PT_QUADRIC
 #define PT_KERNEL __global__
 #ifndef PT_KERNEL_NS
@@ -46,6 +48,14 @@ namespace PT_KERNEL_NS {
 #define PT_KERNEL extern "C" __global__
 #endif
 
+// The motion build (pt_kernels_motion.hip, PT_MOTION): Ray::time rides in the w lane of every ray direction the wavefront stores -- the camera
+// ray's (k_gen), and from there every continuation, shadow, probe and occlusion ray of the sample (spawn_ray / spawn_ray_to inherit the
+// interaction's time) -- so that the traversal and the surface reconstruction find it with the ray.  The other builds keep their 0.
+#if PT_MOTION
+#define PT_TIME_LANE(t) (t)
+#else
+#define PT_TIME_LANE(t) 0.0f
+#endif
 #ifndef PT_LIGHTS_IN_LDS
 #define PT_LIGHTS_IN_LDS 8       // the shading kernels keep the light records of scenes with at most this many lights in LDS (0: never); RT1M 1 075 -> 1 081 Mrays/s
 #endif
@@ -265,7 +275,23 @@ PT_DEV V3 xform_point(const float* m, V3 p) {
 PT_DEV V3 xform_vector(const float* m, V3 v) {
     return mk3(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z);
 }
-PT_DEV void generate_camera_ray(const PtScene& sc, V2 p_film, V2 u_lens, V3* o_out, V3* d_out) {
+#if PT_MOTION
+// The camera's AnimatedTransform (scene_context.rs:643-655) at the ray's time: entry 0 of the scene's motion records through animated_at,
+// the function the instances go through (defined with them below); a camera that does not move keeps its matrix.
+__device__ __noinline__ void animated_at(const PtMotion* rec, const float* m0, const float* minv0, float time, float* m, float* minv);
+PT_DEV void camera_matrix_at(const PtScene& sc, float time, float* m16) {
+    const PtMotion* mo = scene_motions(sc);
+    for (int i = 0; i < 16; i++) m16[i] = sc.cam.camera_to_world[i];
+    if (mo->animated) {
+        float inv[12];
+        animated_at(mo, sc.cam.camera_to_world, sc.cam.camera_to_world, time, m16, inv);          // (the camera keeps no inverse: that half is not read)
+    }
+}
+#define PT_CAMERA_MATRIX(time) float cam_m_[16]; camera_matrix_at(sc, time, cam_m_); const float* m = cam_m_
+#else
+#define PT_CAMERA_MATRIX(time) const float* m = sc.cam.camera_to_world
+#endif
+PT_DEV void generate_camera_ray(const PtScene& sc, V2 p_film, V2 u_lens, V3* o_out, V3* d_out, float time = 0.0f) {
     V3 p_camera = xform_point(sc.cam.raster_to_camera, mk3(p_film.x, p_film.y, 0.0f));
     V3 o = mk3(0.0f, 0.0f, 0.0f);
     V3 d = normalize(p_camera);
@@ -278,7 +304,7 @@ PT_DEV void generate_camera_ray(const PtScene& sc, V2 p_film, V2 u_lens, V3* o_o
         d = normalize(p_focus - o);
     }
     // Transform::transform_ray: nudge the origin along d by the transform's rounding error bound
-    const float* m = sc.cam.camera_to_world;
+    PT_CAMERA_MATRIX(time);
     V3 op = xform_point(m, o);
     float xa = fabsf(m[0] * o.x) + fabsf(m[1] * o.y) + fabsf(m[2] * o.z) + fabsf(m[3]);
     float ya = fabsf(m[4] * o.x) + fabsf(m[5] * o.y) + fabsf(m[6] * o.z) + fabsf(m[7]);
@@ -297,7 +323,7 @@ PT_DEV void generate_camera_ray(const PtScene& sc, V2 p_film, V2 u_lens, V3* o_o
 // The camera ray's offset rays (PerspectiveCamera::generate_ray_differential, perspective.rs:146-171, transformed as
 // transform_ray_differential does, transform.rs:284-297) after render_tile's scale_differentials(1 / sqrt(spp))
 // (sampler.rs:218,233; ray_differential.rs:26-35).  ro / rd: the main ray as k_gen made it.
-PT_DEV void camera_differentials(const PtScene& sc, V2 p_film, V2 u_lens, V3 ro, V3 rd, RayDiffs& out) {
+PT_DEV void camera_differentials(const PtScene& sc, V2 p_film, V2 u_lens, V3 ro, V3 rd, RayDiffs& out, float time = 0.0f) {
     const float* r2c = sc.cam.raster_to_camera;
     V3 p_camera = xform_point(r2c, mk3(p_film.x, p_film.y, 0.0f));
     V3 c0 = xform_point(r2c, mk3(0.0f, 0.0f, 0.0f));
@@ -321,7 +347,7 @@ PT_DEV void camera_differentials(const PtScene& sc, V2 p_film, V2 u_lens, V3 ro,
         rxd = normalize(p_camera + dx_camera);
         ryd = normalize(p_camera + dy_camera);
     }
-    const float* m = sc.cam.camera_to_world;
+    PT_CAMERA_MATRIX(time);
     rxo = xform_point(m, rxo); ryo = xform_point(m, ryo);
     rxd = xform_vector(m, rxd); ryd = xform_vector(m, ryd);
     const float scale = sqrtf(1.0f / (float)sc.sobol.spp);
@@ -577,8 +603,14 @@ struct LaneRay {
     int32_t best;
     uint32_t best_inst;          // INST kernels: instance index + 1 of `best` (0 = a world primitive)
     uint32_t cur_inst;           // k_trace_inst: instance index + 1 of the object tree this ray is walking right now (0 = the world's)
+#if PT_MOTION
+    float time;                  // Ray::time: what an animated instance's transform is interpolated at
+#endif
 };
-PT_DEV void ray_begin(const PtScene& sc, LaneRay& r, V3 o, V3 d, float t_max) {
+PT_DEV void ray_begin(const PtScene& sc, LaneRay& r, V3 o, V3 d, float t_max, float time = 0.0f) {
+#if PT_MOTION
+    r.time = time;
+#endif
     r.o = o;
     r.d = d;
     r.idir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
@@ -595,8 +627,8 @@ PT_DEV void ray_begin(const PtScene& sc, LaneRay& r, V3 o, V3 d, float t_max) {
 }
 // The same for the pooled-leaf kernels: `sa` stack (root kept in `top` only: nothing lies above it when it is popped) and the
 // per-ray constants of node_step_lean.
-PT_DEV void ray_begin_fs(const PtScene& sc, LaneRay& r, const TravCtx& c, V3 o, V3 d, float t_max) {
-    ray_begin(sc, r, o, d, t_max);
+PT_DEV void ray_begin_fs(const PtScene& sc, LaneRay& r, const TravCtx& c, V3 o, V3 d, float t_max, float time = 0.0f) {
+    ray_begin(sc, r, o, d, t_max, time);
     r.sa = c.lane_base + (r.top != PT_EMPTY_REF ? PT_SLOT : 0u);
     if (r.idir.x == 0.0f || r.idir.y == 0.0f || r.idir.z == 0.0f) r.sbits |= 8u;      // infinite direction component: 0 * inf in the slabs
     // rows of a node: 16-byte chunks 0..2 = bmin x / y / z, 3..5 = bmax x / y / z; near / far by the direction signs, as byte offsets
@@ -669,9 +701,30 @@ PT_DEV bool prim_test(const PtScene& sc, const TriVerts& tv, const LaneRay& r, b
     }
     return ok;
 }
+#if PT_MOTION
+// AnimatedTransform::interpolate (animated_transform.rs:63-81, pt_motion.h) for an instance's record, out of line: ONE instruction sequence
+// serves traversal (both entrances), the surface reconstruction and the camera, so that make_surf_inst re-intersects under bit for bit
+// the matrices the traversal used for the same (instance, time) and loses no hit.  The two clamped branches copy the stored matrices and
+// stored inverses, the ones a static instance uses; the interpolating one is lerp / slerp / to_matrix / product / Gauss-Jordan.
+struct InstXf { float m[12], minv[12]; };
+struct PtMotionPorts {          // glibc's acosf / sinf as pt_device_math.h restates them: the bits the host's libm gives motion_bounds
+    static PT_DEV float acos(float x) { return pt_acosf(x); }
+    static PT_DEV float sin(float x) { float s, c; pt_sincosf(x, &s, &c); return s; }
+};
+__device__ __noinline__ void animated_at(const PtMotion* rec, const float* m0, const float* minv0, float time, float* m, float* minv) {
+    pt_motion_at<PtMotionPorts>(*rec, m0, minv0, time, m, minv);
+}
+// TransformedPrimitive's primitive_to_world at the ray's time (transformed_primitive.rs:27): a static instance's own pair, untouched
+PT_DEV void instance_xf(const PtScene& sc, const PtInstance& in, float time, InstXf& x) {
+    if (in.motion1) animated_at(scene_motions(sc) + in.motion1, in.m, in.minv, time, x.m, x.minv);
+    else for (int i = 0; i < 12; i++) { x.m[i] = in.m[i]; x.minv[i] = in.minv[i]; }
+}
+#define PT_INSTANCE_XF(in, time) InstXf xf_; instance_xf(sc, in, time, xf_); const float* const xm = xf_.m; const float* const xinv = xf_.minv; (void)xm
+#else
+#define PT_INSTANCE_XF(in, time) const float* const xm = (in).m; const float* const xinv = (in).minv; (void)xm
+#endif
 // Transform::transform_ray with the instance's inverse (transformed_primitive.rs:27-29, transform.rs:184-203, :245-282)
-PT_DEV void instance_ray(const PtInstance& in, V3 ro, V3 rd, V3* o_out, V3* d_out) {
-    const float* m = in.minv;
+PT_DEV void instance_ray(const float* m, V3 ro, V3 rd, V3* o_out, V3* d_out) {
     V3 o = sph_point(m, ro);
     V3 oe = PT_GAMMA(3.0f) * mk3(fabsf(m[0] * ro.x) + fabsf(m[1] * ro.y) + fabsf(m[2] * ro.z) + fabsf(m[3]),
                                   fabsf(m[4] * ro.x) + fabsf(m[5] * ro.y) + fabsf(m[6] * ro.z) + fabsf(m[7]),
@@ -694,8 +747,12 @@ template <bool SPH, bool ALPHA = false>
 __device__ __noinline__ bool instance_rec_test(const PtScene& sc, uint32_t inst, const LaneRay& r, bool any_hit, TravCtx& c, float* t_out, int32_t* rec_out) {
     const PtInstance& in = sc.instances[inst];
     V3 o, d;
-    instance_ray(in, r.o, r.d, &o, &d);
+    PT_INSTANCE_XF(in, r.time);
+    instance_ray(xinv, r.o, r.d, &o, &d);
     LaneRay ri;
+#if PT_MOTION
+    ri.time = r.time;
+#endif
     ri.o = o; ri.d = d;
     ri.idir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     ri.sbits = (__float_as_uint(d.x) >> 31) | ((__float_as_uint(d.y) >> 31) << 1) | ((__float_as_uint(d.z) >> 31) << 2);
@@ -808,7 +865,8 @@ PT_DEV void ray_step_tri_enter(const PtScene& sc, LaneRay& r, bool any_hit, Trav
             const uint32_t inst = __float_as_uint(t0.p0.x);
             const PtInstance& in = sc.instances[inst];
             V3 o, d;
-            instance_ray(in, r.o, r.d, &o, &d);
+            PT_INSTANCE_XF(in, r.time);
+            instance_ray(xinv, r.o, r.d, &o, &d);
             LaneRay ri;
             ray_set_direction_state(ri, o, d);
             ri.ray_tmax = r.ray_tmax;
@@ -1085,9 +1143,9 @@ PT_DEV void node_step_coop(const PtScene& sc, LaneRay& r, TravCtx& c, bool w_nod
 
 // intersect_simd (qbvh_x86.rs:230-287): closest hit.  Returns record index or -1.
 template <bool SPH, bool INST, bool ALPHA = false>
-PT_DEV int32_t trace_closest(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c, float* t_out, uint32_t* inst_out) {
+PT_DEV int32_t trace_closest(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c, float* t_out, uint32_t* inst_out, float time = 0.0f) {
     LaneRay r;
-    ray_begin(sc, r, o, d, t_max);
+    ray_begin(sc, r, o, d, t_max, time);
     while (!ray_done(r)) ray_step<SPH, INST, ALPHA>(sc, r, false, c);
     *t_out = r.ray_tmax;
     *inst_out = r.best_inst;
@@ -1095,9 +1153,9 @@ PT_DEV int32_t trace_closest(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx
 }
 // intersect_simd_p (qbvh_x86.rs:289-343): any hit
 template <bool SPH, bool INST, bool ALPHA = false>
-PT_DEV bool trace_any(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c) {
+PT_DEV bool trace_any(const PtScene& sc, V3 o, V3 d, float t_max, TravCtx& c, float time = 0.0f) {
     LaneRay r;
-    ray_begin(sc, r, o, d, t_max);
+    ray_begin(sc, r, o, d, t_max, time);
     while (!ray_done(r)) ray_step<SPH, INST, ALPHA>(sc, r, true, c);
     return r.best >= 0;
 }
@@ -1383,11 +1441,16 @@ PT_DEV void trace_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                 float4 ro, rd;
                 ro.x = __shfl(pf_o.x, src, 64); ro.y = __shfl(pf_o.y, src, 64); ro.z = __shfl(pf_o.z, src, 64); ro.w = __shfl(pf_o.w, src, 64);
                 rd.x = __shfl(pf_d.x, src, 64); rd.y = __shfl(pf_d.y, src, 64); rd.z = __shfl(pf_d.z, src, 64);
+#if PT_MOTION
+                rd.w = __shfl(pf_d.w, src, 64);          // the motion build: a ray's time rides in the w lane of its direction, whatever its kind
+#else
+                rd.w = 0.0f;
+#endif
                 if (kind == 0 && rank < take) {
                     p = np; kind = nk;
                     if (nk == 2) shadow++; else regular++;
-                    if constexpr (DIST) ray_begin_fs(sc, r, c, f4_3(ro), mk3(rd.x, rd.y, rd.z), ro.w);
-                    else ray_begin(sc, r, f4_3(ro), mk3(rd.x, rd.y, rd.z), ro.w);
+                    if constexpr (DIST) ray_begin_fs(sc, r, c, f4_3(ro), mk3(rd.x, rd.y, rd.z), ro.w, rd.w);
+                    else ray_begin(sc, r, f4_3(ro), mk3(rd.x, rd.y, rd.z), ro.w, rd.w);
                 }
                 pf_used += take;
                 if (pf_used == pf_count) pf_stage = 0;
@@ -1682,7 +1745,7 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK, 2) k_trace_sph(PtScene sc, PtPaths P,
 // ============================================================ hooks: plain ray batches
 template <bool SPH, bool INST = false, bool ALPHA = false>
 PT_DEV void trace_batch_body(const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, pt_hit* out, uint8_t* occ_out, int any_hit,
-                             uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
+                             uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err, const float* time = nullptr) {
     __shared__ uint32_t s_stack[PT_LDS_STACK * PT_BLOCK];
     __shared__ unsigned long long s_cnt[4];
     TravCtx c;
@@ -1698,14 +1761,19 @@ PT_DEV void trace_batch_body(const PtScene& sc, uint32_t n, const float* o, cons
         uint32_t i = base + (threadIdx.x & 63);
         if (i >= n) continue;
         V3 ro = ld3(o + 3 * (size_t)i), rd = ld3(d + 3 * (size_t)i);
+#if PT_MOTION
+        const float tm = time ? time[i] : 0.0f;          // Ray::default: time 0
+#else
+        const float tm = 0.0f;
+#endif
         if (any_hit) {
             shadow++;
-            occ_out[i] = trace_any<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c) ? 1 : 0;
+            occ_out[i] = trace_any<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c, tm) ? 1 : 0;
         } else {
             regular++;
             float t;
             uint32_t inst = 0;
-            int32_t rec = trace_closest<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c, &t, &inst);
+            int32_t rec = trace_closest<SPH, INST, ALPHA>(sc, ro, rd, tmax[i], c, &t, &inst, tm);
             pt_hit h;
             h.t = 0.0f; h.prim = -1; h.b0 = 0.0f; h.b1 = 0.0f;
             if (rec >= 0 && INST && inst) {          // the hit is reported as the instance's own world primitive
@@ -1747,6 +1815,25 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha(PtScene sc, uint3
                                                                           uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
     trace_batch_body<true, true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err);
 }
+#if PT_MOTION
+// pt_trace_closest_time / pt_trace_any_time: the instance-capable batch kernels with a time per ray
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_inst_time(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax, const float* time,
+                                                                              pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
+                                                                              uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
+    trace_batch_body<true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err, time);
+}
+PT_KERNEL void __launch_bounds__(PT_BLOCK) k_trace_batch_alpha_time(PtScene sc, uint32_t n, const float* o, const float* d, const float* tmax, const float* time,
+                                                                               pt_hit* out, uint8_t* occ_out, int any_hit, uint32_t* ticket, PtCounters* cnt,
+                                                                               uint32_t* spill, uint32_t spill_depth, uint32_t* err) {
+    trace_batch_body<true, true, true>(sc, n, o, d, tmax, out, occ_out, any_hit, ticket, cnt, spill, spill_depth, err, time);
+}
+hipError_t ptk_trace_batch_time(hipStream_t st, int grid, const PtScene& sc, uint32_t n, const float* o, const float* d, const float* tmax, const float* time,
+                                pt_hit* out, uint8_t* occ, int any_hit, uint32_t* ticket, PtCounters* cnt, uint32_t* spill, uint32_t spill_depth, uint32_t* err, int alpha) {
+    if (alpha) hipLaunchKernelGGL(k_trace_batch_alpha_time, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, time, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
+    else hipLaunchKernelGGL(k_trace_batch_inst_time, dim3(grid), dim3(PT_BLOCK), 0, st, sc, n, o, d, tmax, time, out, occ, any_hit, ticket, cnt, spill, spill_depth, err);
+    return hipGetLastError();
+}
+#endif
 
 // ============================================================ hook: caller rays through the wavefront's own traversal kernel
 // pt_trace_wavefront loads caller rays into the path pool as the three kinds of work items a bounce mixes in one launch and
@@ -1826,11 +1913,16 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_gen(PtScene sc, PtPaths P, PtQueues
         V2 uf = sm.get_2d(sc);
         V2 p_film = mk2((float)px + uf.x, (float)py + uf.y);
         V2 u_lens = sm.get_2d(sc);
+#if PT_MOTION
+        const float u_time = sm.get_1d(sc);
+        const float time = (1.0f - u_time) * sc.cam.shutter_open + u_time * sc.cam.shutter_close;      // lerp(sample.time, shutter_open, shutter_close), perspective.rs:111-117
+#else
         (void)sm.get_1d(sc);   // time
+#endif
         V3 o, d;
-        generate_camera_ray(sc, p_film, u_lens, &o, &d);
+        generate_camera_ray(sc, p_film, u_lens, &o, &d, PT_TIME_LANE(time));
         P.ray_o[i] = make_float4(o.x, o.y, o.z, PT_INF);
-        P.ray_d[i] = make_float4(d.x, d.y, d.z, 0.0f);
+        P.ray_d[i] = make_float4(d.x, d.y, d.z, PT_TIME_LANE(time));
         P.beta[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
         P.L[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         P.p_film[i] = make_float2(p_film.x, p_film.y);
@@ -2011,21 +2103,22 @@ PT_DEV bool make_surf_any(const PtScene& sc, V3 ro, V3 rd, uint32_t rec, Surf& s
 // A hit inside an object instance: Shape::intersect again in instance space, then Transform::transform_surface_interaction
 // back to the world (transformed_primitive.rs:30-38, transform.rs:299-323).
 template <bool SPH>
-PT_DEV bool make_surf_inst(const PtScene& sc, V3 ro, V3 rd, uint32_t rec, uint32_t inst1, Surf& s, float* t_out) {
+PT_DEV bool make_surf_inst(const PtScene& sc, V3 ro, V3 rd, uint32_t rec, uint32_t inst1, Surf& s, float* t_out, float time = 0.0f) {
     if (inst1 == 0) return make_surf_any<SPH>(sc, ro, rd, rec, s, t_out);
     const PtInstance& in = sc.instances[inst1 - 1u];
     V3 o, d;
-    instance_ray(in, ro, rd, &o, &d);
+    PT_INSTANCE_XF(in, time);           // (the motion build: the pair the traversal used for this instance at this time, bit for bit)
+    instance_ray(xinv, ro, rd, &o, &d);
     if (!make_surf_any<SPH>(sc, o, d, rec, s, t_out)) return false;
     V3 p = s.p, pe = s.p_error;
-    s.p = sph_point(in.m, p);
-    s.p_error = sph_point_abs_error(in.m, p, pe);
-    s.n = normalize(sph_normal(in.minv, s.n));
-    s.wo = normalize(sph_vector(in.m, s.wo));
-    s.dpdu = sph_vector(in.m, s.dpdu); s.dpdv = sph_vector(in.m, s.dpdv);
-    s.sh_n = normalize(sph_normal(in.minv, s.sh_n));
-    s.sh_dpdu = sph_vector(in.m, s.sh_dpdu); s.sh_dpdv = sph_vector(in.m, s.sh_dpdv);
-    s.sh_dndu = sph_normal(in.minv, s.sh_dndu); s.sh_dndv = sph_normal(in.minv, s.sh_dndv);
+    s.p = sph_point(xm, p);
+    s.p_error = sph_point_abs_error(xm, p, pe);
+    s.n = normalize(sph_normal(xinv, s.n));
+    s.wo = normalize(sph_vector(xm, s.wo));
+    s.dpdu = sph_vector(xm, s.dpdu); s.dpdv = sph_vector(xm, s.dpdv);
+    s.sh_n = normalize(sph_normal(xinv, s.sh_n));
+    s.sh_dpdu = sph_vector(xm, s.sh_dpdu); s.sh_dpdv = sph_vector(xm, s.sh_dpdv);
+    s.sh_dndu = sph_normal(xinv, s.sh_dndu); s.sh_dndv = sph_normal(xinv, s.sh_dndv);
     s.sh_n = face_forward(s.sh_n, s.n);
     s.light = -1;                                 // TransformedPrimitive::get_area_light is None
     return true;
@@ -3016,7 +3109,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
             Surf s;
             float thit;
             bool found;
-            if constexpr (INST) found = rec >= 0 && make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit);
+            if constexpr (INST) found = rec >= 0 && make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit, PT_TIME_LANE(rd4.w));
             else found = rec >= 0 && make_surf_any_rec<SPH>(sc, ro, rd, (uint32_t)rec, rec_a, rec_b, rec_c, s, &thit);
             PT_SHP(0);
             if (pf_lane) {                                   // pf_p has long arrived: the head of the next iteration's dependent chain, one iteration early
@@ -3065,7 +3158,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             V2 u_lens = mk2(0.0f, 0.0f);
                             if (sc.cam.lens_radius > 0.0f) u_lens = sl.get_2d(sc);
                             float2 pf = P.p_film[p];
-                            camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf);
+                            camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf, PT_TIME_LANE(P.ray_d[p].w));
                         }
                         compute_differentials(th, s.p, s.n, s.dpdu, s.dpdv, has_diff, rdf);
                         if constexpr (MIX) {
@@ -3196,7 +3289,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                         V3 target = offset_ray_origin(lp, lperr, ln, origin - lp);
                                         V3 sd = target - origin;
                                         s_stage[0][threadIdx.x] = make_float4(origin.x, origin.y, origin.z, 1.0f - PT_SHADOW_EPS);
-                                        s_stage[1][threadIdx.x] = make_float4(sd.x, sd.y, sd.z, 0.0f);
+                                        s_stage[1][threadIdx.x] = make_float4(sd.x, sd.y, sd.z, PT_TIME_LANE(rd4.w));
                                         if (Q.shadow_key) s_pkey[n_batch][threadIdx.x] = ray_sort_key(sc, origin, sd);
                                         wr |= 4u; PT_COMMIT_NOW(1);
                                         if (light_is_delta<DELTA>(lt)) A = f * li / lpdf;          // no power heuristic (sample_lights.rs:380-381)
@@ -3230,7 +3323,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                                 const V3 le = env_le(sc, e, wi2);
                                                 B = f * le * 1.0f * (weight / spdf2);
                                                 s_stage[2][threadIdx.x] = make_float4(po.x, po.y, po.z, PT_INF);
-                                                s_stage[3][threadIdx.x] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                                                s_stage[3][threadIdx.x] = make_float4(wi2.x, wi2.y, wi2.z, PT_TIME_LANE(rd4.w));
                                                 wr |= 8u; PT_COMMIT_NOW(2);
                                                 nee |= PT_NEE_PROBE;
                                             }
@@ -3259,7 +3352,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                                             V3 le = light_L(lt, ls.n, -wi2);
                                             B = f * le * 1.0f * (weight / spdf2);
                                             s_stage[2][threadIdx.x] = make_float4(po.x, po.y, po.z, PT_INF);
-                                            s_stage[3][threadIdx.x] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                                            s_stage[3][threadIdx.x] = make_float4(wi2.x, wi2.y, wi2.z, PT_TIME_LANE(rd4.w));
                                             wr |= 8u; PT_COMMIT_NOW(2);
                                             nee |= PT_NEE_PROBE;
                                         }
@@ -3332,7 +3425,11 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                             // inside the Russian-roulette branch (the sampler's table addressing) while wi.z is still waiting to be stored:
                             // hipcc 7.2 -O2 / -O3, the textured and instanced kernels with the stores held back -- survivors of the
                             // roulette continued with direction z = 0 (profiles/r03_deferred_store_miscompile.md)
+#if PT_MOTION
+                            o_ray_d = make_float4(wi.x, wi.y, wi.z, opaque_zero() + rd4.w);          // (the continuation ray inherits the time)
+#else
                             o_ray_d = make_float4(wi.x, wi.y, wi.z, opaque_zero());
+#endif
                             o_beta = make_float4(beta.x, beta.y, beta.z, eta_scale);
                             wr |= 3u; PT_COMMIT_NOW(4);
                             bounces++;
@@ -3428,7 +3525,7 @@ PT_DEV void tex_resolve_body(const PtScene& sc, const PtPaths& P, const PtQueues
             V2 u_lens = mk2(0.0f, 0.0f);
             if (sc.cam.lens_radius > 0.0f) u_lens = sl.get_2d(sc);
             const float2 pf = P.p_film[p];
-            camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf);
+            camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf, PT_TIME_LANE(P.ray_d[p].w));
         }
         compute_differentials(th, s.p, s.n, s.dpdu, s.dpdv, has_diff, rdf);
         PtMatParams mp;
@@ -3747,7 +3844,7 @@ PT_DEV void grid_mark_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
         Surf s;
         float thit;
         bool found;
-        if constexpr (INST) found = make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit);
+        if constexpr (INST) found = make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit, PT_TIME_LANE(P.ray_d[p].w));
         else found = make_surf_any<SPH>(sc, ro, rd, (uint32_t)rec, s, &thit);
         if (!found) continue;
         const uint32_t vox = grid_voxel_of(sc.grid, s.p);
@@ -3788,6 +3885,29 @@ PT_KERNEL void k_camera_rays(PtScene sc, uint32_t n, const int32_t* pixel_xy, co
         out_pf[2 * i] = pf.x; out_pf[2 * i + 1] = pf.y;
     }
 }
+#if PT_MOTION
+// pt_generate_camera_rays_time on a scene that moves: k_gen's ray, time included
+PT_KERNEL void k_camera_rays_time(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* out_o, float* out_d,
+                                              float* out_pf, float* out_time) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        int32_t px = pixel_xy[2 * i], py = pixel_xy[2 * i + 1];
+        Sampler sm;
+        sm.index = sampler_index(sc, sample_index[i], px, py);
+        sm.dim = 0; sm.px = px; sm.py = py;
+        V2 uf = sm.get_2d(sc);
+        V2 pf = mk2((float)px + uf.x, (float)py + uf.y);
+        V2 ul = sm.get_2d(sc);
+        const float u_time = sm.get_1d(sc);
+        const float time = (1.0f - u_time) * sc.cam.shutter_open + u_time * sc.cam.shutter_close;
+        V3 o, d;
+        generate_camera_ray(sc, pf, ul, &o, &d, time);
+        out_o[3 * i] = o.x; out_o[3 * i + 1] = o.y; out_o[3 * i + 2] = o.z;
+        out_d[3 * i] = d.x; out_d[3 * i + 1] = d.y; out_d[3 * i + 2] = d.z;
+        out_pf[2 * i] = pf.x; out_pf[2 * i + 1] = pf.y;
+        out_time[i] = time;
+    }
+}
+#endif
 PT_KERNEL void k_sobol_samples(PtScene sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, const uint32_t* dim, float* out) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         int32_t px = pixel_xy[2 * i], py = pixel_xy[2 * i + 1];
@@ -3939,9 +4059,9 @@ using RecNode = RecNodeT<false>;
 // FULL = false: the instantiation for scenes without spheres, instances and textured materials (the triangle-only test, no texture programs, no
 // per-hit lobe list in scratch): what `directlighting` / `whitted` run on BASELINE's scenes.  FULL = true: everything compiled in.
 template <bool FULL, bool MIX = false>
-PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t inst, bool has_diff, const RayDiffs& rdf, RecNodeT<MIX>& nd) {
+PT_DEV void rec_build(const PtScene& sc, V3 ro, V3 rd, int32_t rec, uint32_t inst, bool has_diff, const RayDiffs& rdf, RecNodeT<MIX>& nd, float time = 0.0f) {
     float thit;
-    if constexpr (FULL) nd.found = rec >= 0 && make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, nd.s, &thit);
+    if constexpr (FULL) nd.found = rec >= 0 && make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, nd.s, &thit, time);
     else nd.found = rec >= 0 && make_surf_any<false>(sc, ro, rd, (uint32_t)rec, nd.s, &thit);
     nd.has_bsdf = false;
     nd.bsdf_eta = 1.0f;
@@ -3984,7 +4104,7 @@ PT_DEV float4* rec_frame(const PtRec& R, uint32_t depth, uint32_t k, uint32_t p)
 // are combined by k_rec_next.  Returns the PT_NEE_* flags of the entry.
 // ENV: the scene has an infinite light (k_rec_enter_env): its map is sampled, B counts when the probe escapes (k_rec_next_env)
 template <bool FULL, bool ENV = false, bool MIX = false>
-PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const RecNodeT<MIX>& nd, uint32_t light_num, V2 u_light, V2 u_scat, uint32_t e, float divisor = 1.0f) {
+PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const RecNodeT<MIX>& nd, uint32_t light_num, V2 u_light, V2 u_scat, uint32_t e, float divisor = 1.0f, float time = 0.0f) {
     const Surf& s = nd.s;
     const PtLight& lt = sc.lights[light_num];
     const uint32_t kNoSpec = PT_BSDF_ALL & ~PT_BSDF_SPECULAR;
@@ -4004,7 +4124,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
                 V3 target = offset_ray_origin(lp, lperr, ln, origin - lp);
                 V3 sd = target - origin;
                 R.sh_o[e] = make_float4(origin.x, origin.y, origin.z, 1.0f - PT_SHADOW_EPS);
-                R.sh_d[e] = make_float4(sd.x, sd.y, sd.z, 0.0f);
+                R.sh_d[e] = make_float4(sd.x, sd.y, sd.z, PT_TIME_LANE(time));
                 if (light_is_delta<ENV>(lt)) A = f * li / lpdf;
                 else {
                     float weight = power_heuristic(lpdf, spdf);
@@ -4034,7 +4154,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
                         const V3 le = env_le(sc, en, wi2);
                         B = f * le * 1.0f * (weight / spdf2);
                         R.pr_o[e] = make_float4(po.x, po.y, po.z, PT_INF);
-                        R.pr_d[e] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                        R.pr_d[e] = make_float4(wi2.x, wi2.y, wi2.z, PT_TIME_LANE(time));
                         nee |= PT_NEE_PROBE;
                     }
                 }
@@ -4047,7 +4167,7 @@ PT_DEV uint32_t rec_estimate_direct(const PtScene& sc, const PtRec& R, const Rec
                     V3 le = light_L(lt, ls.n, -wi2);
                     B = f * le * 1.0f * (weight / spdf2);
                     R.pr_o[e] = make_float4(po.x, po.y, po.z, PT_INF);
-                    R.pr_d[e] = make_float4(wi2.x, wi2.y, wi2.z, 0.0f);
+                    R.pr_d[e] = make_float4(wi2.x, wi2.y, wi2.z, PT_TIME_LANE(time));
                     nee |= PT_NEE_PROBE;
                 }
             }
@@ -4071,7 +4191,7 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_rec_init(PtScene sc, PtPaths P, PtR
         if (sc.cam.lens_radius > 0.0f) u_lens = sl.get_2d(sc);
         const float2 pf = P.p_film[p];
         RayDiffs rdf;
-        camera_differentials(sc, mk2(pf.x, pf.y), u_lens, f4_3(P.ray_o[p]), f4_3(P.ray_d[p]), rdf);
+        camera_differentials(sc, mk2(pf.x, pf.y), u_lens, f4_3(P.ray_o[p]), f4_3(P.ray_d[p]), rdf, PT_TIME_LANE(P.ray_d[p].w));
         R.diff[p] = make_float4(rdf.rx_o.x, rdf.rx_o.y, rdf.rx_o.z, 0.0f);
         R.diff[(size_t)R.n_paths + p] = make_float4(rdf.ry_o.x, rdf.ry_o.y, rdf.ry_o.z, 0.0f);
         R.diff[2 * (size_t)R.n_paths + p] = make_float4(rdf.rx_d.x, rdf.rx_d.y, rdf.rx_d.z, 0.0f);
@@ -4111,7 +4231,10 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
         rdf.rx_o = rdf.ry_o = rdf.rx_d = rdf.ry_d = mk3(0.0f, 0.0f, 0.0f);
         if (has_diff) rdf = rec_load_diff(R, p);
         RecNodeT<MIX> nd;
-        rec_build<FULL, MIX>(sc, ro, rd, rec, inst, has_diff, rdf, nd);
+#if PT_MOTION
+        const float ray_time = P.ray_d[p].w;
+#endif
+        rec_build<FULL, MIX>(sc, ro, rd, rec, inst, has_diff, rdf, nd, PT_TIME_LANE(ray_time));
         uint32_t outcome = PT_REC_OUT_FRAME;
         if (!nd.found) outcome = PT_REC_OUT_RETURN0;              // the lights' le(ray) sum: zero for area lights
         else if (!nd.has_bsdf) {
@@ -4152,7 +4275,7 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                             V3 target = offset_ray_origin(lp, lperr, ln, origin - lp);
                             V3 sd = target - origin;
                             R.sh_o[e0 + j] = make_float4(origin.x, origin.y, origin.z, 1.0f - PT_SHADOW_EPS);
-                            R.sh_d[e0 + j] = make_float4(sd.x, sd.y, sd.z, 0.0f);
+                            R.sh_d[e0 + j] = make_float4(sd.x, sd.y, sd.z, PT_TIME_LANE(ray_time));
                             A = f * li * (abs_dot(wi, nd.n_before) / lpdf);
                             nee |= PT_NEE_SHADOW;
                         }
@@ -4177,13 +4300,13 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                                 for (uint32_t k = 0; k < n; k++) {
                                     const uint64_t idx = n == 1u ? sm.index : sampler_index(sc, sample_num * n + k, sm.px, sm.py);
                                     const V2 u = mk2(sample_dimension(sc, idx, 5u, sm.px, sm.py), sample_dimension(sc, idx, 6u, sm.px, sm.py));
-                                    rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u, u, e0 + off + k, (float)n);
+                                    rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u, u, e0 + off + k, (float)n, PT_TIME_LANE(ray_time));
                                 }
                             } else {
                                 arr = R.n_arrays;
                                 const V2 u_light = sm.get_2d(sc);
                                 const V2 u_scat = sm.get_2d(sc);
-                                rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f);
+                                rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, j, u_light, u_scat, e0 + off, 1.0f, PT_TIME_LANE(ray_time));
                                 for (uint32_t k = 1; k < n; k++) R.flags[e0 + off + k] = 0u;
                             }
                             off += n;
@@ -4196,7 +4319,7 @@ PT_DEV void rec_enter_body(const PtScene& sc, const PtPaths& P, const PtQueues& 
                         const float light_pdf = 1.0f / (float)sc.n_lights;
                         const V2 u_light = sm.get_2d(sc);
                         const V2 u_scat = sm.get_2d(sc);
-                        rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, light_num, u_light, u_scat, e0);
+                        rec_estimate_direct<FULL, ENV, MIX>(sc, R, nd, light_num, u_light, u_scat, e0, 1.0f, PT_TIME_LANE(ray_time));
                         float4 a = R.A[e0];
                         a.w = light_pdf;
                         R.A[e0] = a;
@@ -4289,7 +4412,10 @@ PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R
     rdf.rx_o = f4_3(*rec_frame(R, depth, 2, p)); rdf.ry_o = f4_3(*rec_frame(R, depth, 3, p));
     rdf.rx_d = f4_3(*rec_frame(R, depth, 4, p)); rdf.ry_d = f4_3(*rec_frame(R, depth, 5, p));
     RecNodeT<MIX> nd;
-    rec_build<FULL, MIX>(sc, ro, rd, rec, iw & 0x7fffffffu, has_diff, rdf, nd);
+#if PT_MOTION
+    const float ray_time = P.ray_d[p].w;          // (the current ray's, whichever node of the tree it belongs to: one time per camera sample)
+#endif
+    rec_build<FULL, MIX>(sc, ro, rd, rec, iw & 0x7fffffffu, has_diff, rdf, nd, PT_TIME_LANE(ray_time));
     const V2 u = sm.get_2d(sc);
     V3 f, wi;
     float pdf;
@@ -4303,7 +4429,7 @@ PT_DEV bool rec_sample_child(const PtScene& sc, const PtPaths& P, const PtRec& R
     if (!(pdf > 0.0f && !is_black(f) && wi_ns != 0.0f)) return false;
     const V3 no = offset_ray_origin(s.p, s.p_error, s.n, wi);
     P.ray_o[p] = make_float4(no.x, no.y, no.z, PT_INF);
-    P.ray_d[p] = make_float4(wi.x, wi.y, wi.z, 0.0f);
+    P.ray_d[p] = make_float4(wi.x, wi.y, wi.z, PT_TIME_LANE(ray_time));
     *child_flags = 0;
     if (has_diff) {
         const V3 rx_o = s.p + nd.th.dpdx, ry_o = s.p + nd.th.dpdy;
@@ -4571,12 +4697,12 @@ PT_DEV void aov_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, int3
                 if (sc.cam.lens_radius > 0.0f) u_lens = sl.get_2d(sc);
                 const float2 pf = P.p_film[p];
                 RayDiffs rdf;
-                camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf);
+                camera_differentials(sc, mk2(pf.x, pf.y), u_lens, ro, rd, rdf, PT_TIME_LANE(P.ray_d[p].w));
                 uint32_t inst = 0;
                 if constexpr (FULL) inst = sc.n_instances ? P.hit_inst[p] : 0u;
                 Surf sf;
                 float thit;
-                if constexpr (FULL) found = make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, sf, &thit);
+                if constexpr (FULL) found = make_surf_inst<true>(sc, ro, rd, (uint32_t)rec, inst, sf, &thit, PT_TIME_LANE(P.ray_d[p].w));
                 else found = make_surf_any<false>(sc, ro, rd, (uint32_t)rec, sf, &thit);
                 if (found) {
                     TexHit th;
@@ -4723,12 +4849,18 @@ PT_DEV void ao_rays_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, 
         bool found = false;
         Surf s;
         V3 rd = mk3(0.0f, 0.0f, 1.0f);
+#if PT_MOTION
+        float ray_time = 0.0f;
+#endif
         if (p < n_paths) {
             const V3 ro = f4_3(P.ray_o[p]);
             rd = f4_3(P.ray_d[p]);
+#if PT_MOTION
+            ray_time = P.ray_d[p].w;
+#endif
             const int32_t rec = P.hit_rec[p];
             float thit;
-            if constexpr (INST) found = rec >= 0 && make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit);
+            if constexpr (INST) found = rec >= 0 && make_surf_inst<SPH>(sc, ro, rd, (uint32_t)rec, P.hit_inst[p], s, &thit, PT_TIME_LANE(ray_time));
             else found = rec >= 0 && make_surf_any<SPH>(sc, ro, rd, (uint32_t)rec, s, &thit);
         }
         const uint64_t hits = __ballot(found);
@@ -4764,7 +4896,7 @@ PT_DEV void ao_rays_body(const PtScene& sc, const PtPaths& P, uint32_t n_paths, 
             const V3 o = offset_ray_origin(s.p, s.p_error, s.n, wi);
             const size_t r = r0 + k;
             ao_o[r] = make_float4(o.x, o.y, o.z, PT_INF);          // the record layout of a shadow work item (origin, t_max | direction)
-            ao_d[r] = make_float4(wi.x, wi.y, wi.z, 0.0f);
+            ao_d[r] = make_float4(wi.x, wi.y, wi.z, PT_TIME_LANE(ray_time));
             ao_w[r] = dot(wi, n) / (pdf * (float)n_s);
         }
     }
@@ -4940,6 +5072,13 @@ hipError_t ptk_camera_rays(hipStream_t st, const PtScene& sc, uint32_t n, const 
     hipLaunchKernelGGL(k_camera_rays, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, n, pixel_xy, sample_index, o, d, pf);
     return PT_LAUNCH_CHECK();
 }
+#if PT_MOTION
+hipError_t ptk_camera_rays_time(hipStream_t st, const PtScene& sc, uint32_t n, const int32_t* pixel_xy, const uint32_t* sample_index, float* o, float* d,
+                                float* pf, float* time) {
+    hipLaunchKernelGGL(k_camera_rays_time, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, n, pixel_xy, sample_index, o, d, pf, time);
+    return PT_LAUNCH_CHECK();
+}
+#endif
 hipError_t ptk_bsdf_eval(hipStream_t st, const PtScene& sc, uint32_t material, uint32_t n, const float* wo, const float* wi, uint32_t flags, float* f,
                          float* pdf) {
     if (scene_n_mix(sc)) hipLaunchKernelGGL(k_bsdf_eval_mix, dim3((n + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sc, material, n, wo, wi, flags, f, pdf);

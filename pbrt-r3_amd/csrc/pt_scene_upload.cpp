@@ -280,6 +280,13 @@ struct SceneChecks { std::vector<uint8_t> mesh_alpha; bool any_alpha = false; };
 struct WorldBuild {
     std::vector<PtSphere> sph;
     std::vector<PtInstance> dinst;
+    // motion (pt_scene_set_motion): entry 0 the camera's record, then one per instance that actually moves; per instance its entry (0 = static)
+    // and whether its AnimatedTransform has_rotation (motion_bounds' third branch)
+    std::vector<PtMotion> motion;
+    std::vector<uint32_t> inst_motion;
+    std::vector<uint32_t> inst_motion_rec;          // per instance: its pt_motion_instance in ctx->next_motion_inst (read where inst_motion is set)
+    std::vector<uint8_t> inst_has_rotation;
+    bool camera_moves = false, instances_move = false;
     std::vector<PtLight> lights;
     std::vector<PtTriInfo> tinfo;                   // host path: per leaf record (sphere / instance entries unused)
     std::vector<uint32_t> tri_flags;
@@ -316,6 +323,19 @@ pt_status check_scene(pt_context* ctx, const pt_scene_desc* d, SceneChecks& chk)
         if (in.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "instance before_triangle exceeds n_triangles");
         if (!affine(in.instance_to_world) || !affine(in.world_to_instance))
             return ctx->fail(PT_ERR_UNSUPPORTED, "object instance under a projective transform (last matrix row must be 0 0 0 1)");
+    }
+    if (ctx->next_has_motion) {
+        const pt_motion& mo = ctx->next_motion;
+        if (mo.camera_animated && !affine(mo.camera_to_world_end)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: the camera's end transform is projective (last matrix row must be 0 0 0 1)");
+        if (mo.camera_animated && !affine(d->camera_to_world)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: the camera's start transform is projective (last matrix row must be 0 0 0 1)");
+        std::vector<uint8_t> seen(d->n_instances, 0);
+        for (const pt_motion_instance& mi : ctx->next_motion_inst) {
+            if (mi.instance >= d->n_instances) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: instance index out of range");
+            if (seen[mi.instance]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: two records for one instance");
+            seen[mi.instance] = 1;
+            if (!affine(mi.instance_to_world_end) || !affine(mi.world_to_instance_end))
+                return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: an instance's end transform is projective (last matrix row must be 0 0 0 1)");
+        }
     }
     if (d->n_triangles > 0 && (!d->P || !d->indices || !d->tri_mesh || !d->meshes)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "triangle arrays missing");
     if (d->n_spheres > 0 && !d->spheres) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "spheres array missing");
@@ -563,6 +583,49 @@ static inline PtLight sphere_light(const pt_scene_desc* d, uint32_t si, float ar
 
 // ---- BVH, records and nodes on the device --------------------------------
 // A world list of triangles only (no spheres, objects or instances) under the SAH or HLBVH split -- BASELINE's scenes -- never leaves the
+// AnimatedTransform::new (animated_transform.rs:23-61) for the camera and for every instance with a motion record: both ends decomposed, the record
+// the kernels interpolate from.  A pair whose ends are equal is not actually animated and stays what it was: no record, the kernels it ran before.
+// interpolate lerps the scale: a component that changes sign (or is zero at an end) passes through zero, M(t) is singular there and the
+// reference's Transform::from panics.  Such a pair is refused.
+bool scale_keeps_its_sign(const PtMotion& r) {
+    for (int i = 0; i < 3; i++) if (!(r.S[0][i] * r.S[1][i] > 0.0f)) return false;
+    return true;
+}
+pt_status build_motion_records(pt_context* ctx, const pt_scene_desc* d, WorldBuild& w) {
+    w.inst_motion.assign(d->n_instances, 0u);
+    w.inst_has_rotation.assign(d->n_instances, 0);
+    w.inst_motion_rec.assign(d->n_instances, 0u);
+    if (!ctx->next_has_motion) return PT_OK;
+    const pt_motion& mo = ctx->next_motion;
+    PtMotion cam;
+    std::memset(&cam, 0, sizeof(cam));
+    bool rot = false;
+    if (mo.camera_animated) {
+        // (the camera keeps no inverse: the same stand-in at both ends leaves the comparison to the matrices)
+        if (!ptmotion::make_record(d->camera_to_world, d->camera_to_world, mo.camera_to_world_end, d->camera_to_world, mo.transform_times, &cam, &rot))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: decompose failed on a camera transform");
+        w.camera_moves = cam.animated != 0;
+        if (w.camera_moves && !scale_keeps_its_sign(cam)) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: the camera's scale changes sign between the two times (the interpolated transform is singular on the way)");
+    }
+    w.motion.push_back(cam);
+    for (const pt_motion_instance& mi : ctx->next_motion_inst) {
+        const pt_instance& in = d->instances[mi.instance];
+        PtMotion rec;
+        if (!ptmotion::make_record(in.instance_to_world, in.world_to_instance, mi.instance_to_world_end, mi.world_to_instance_end, mo.transform_times, &rec, &rot))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: decompose failed on a transform of instance " + std::to_string(mi.instance));
+        if (!rec.animated) continue;
+        if (!scale_keeps_its_sign(rec))
+            return ctx->fail(PT_ERR_INVALID_ARGUMENT, "motion: the scale of instance " + std::to_string(mi.instance) + " changes sign between the two times (the interpolated transform is singular on the way)");
+        w.inst_motion[mi.instance] = (uint32_t)w.motion.size();
+        w.inst_motion_rec[mi.instance] = (uint32_t)(&mi - ctx->next_motion_inst.data());
+        w.inst_has_rotation[mi.instance] = rot ? 1 : 0;
+        w.motion.push_back(rec);
+        w.instances_move = true;
+    }
+    if (!w.camera_moves && !w.instances_move) w.motion.clear();
+    return PT_OK;
+}
+
 // device: vertices and indices go up, pt_sah.hip / pt_hlbvh.hip build the binary tree, pt_sah.hip writes the leaf and shading records in leaf order, collapses
 // the tree into the 4-wide node array in the reference's depth-first numbering and finishes it (breadth-first top, order tables, axis
 // bits, inverted empty slots).  Same arrays as the host path below, byte for byte (tests/test_gpu_hlbvh.py compares the digests).
@@ -788,6 +851,12 @@ pt_status build_lists_and_trees(pt_context* ctx, const pt_scene_desc* d, const S
             const pt_instance& in = d->instances[en.idx];
             const ObjectBvh& ob = objs[in.object];
             const float* m = in.instance_to_world;          // motion_bounds of a static transform = transform_bounds (transform.rs:134-182)
+            if (w.inst_motion[en.idx]) {                    // ... and of one that moves the sampled form (animated_transform.rs:154-187), whatever the split method
+                const pt_motion_instance& mi = ctx->next_motion_inst[w.inst_motion_rec[en.idx]];
+                ptmotion::motion_bounds(w.motion[w.inst_motion[en.idx]], w.inst_has_rotation[en.idx] != 0, m, mi.instance_to_world_end, ob.lo, ob.hi, prims[i].lo, prims[i].hi);
+                ptbvh::instance_record(en.idx, &prims[i].rec);
+                continue;
+            }
             for (int c = 0; c < 8; c++) {
                 const float x = (c & 4) ? ob.hi[0] : ob.lo[0], y = (c & 2) ? ob.hi[1] : ob.lo[1], z = (c & 1) ? ob.hi[2] : ob.lo[2];
                 float q[3] = {m[0] * x + m[1] * y + m[2] * z + m[3], m[4] * x + m[5] * y + m[6] * z + m[7], m[8] * x + m[9] * y + m[10] * z + m[11]};
@@ -853,6 +922,7 @@ pt_status build_lists_and_trees(pt_context* ctx, const pt_scene_desc* d, const S
             o.world_prim = wp;
             std::memcpy(o.m, in.instance_to_world, 48); std::memcpy(o.minv, in.world_to_instance, 48);
             o.root_ref = ob.res.root_ref; o.direct = ob.direct ? 1u : 0u;
+            o.motion1 = w.inst_motion[i];
             std::memcpy(o.root_lo, ob.lo, 12); std::memcpy(o.root_hi, ob.hi, 12);
         }
     }
@@ -1250,6 +1320,12 @@ pt_status upload_materials_and_lights(pt_context* ctx, const pt_scene_desc* d, M
     for (const PtLight& L : w.lights) ctx->light_samples_total += L.n_samples;
     if ((st = upload(ctx, ctx->d_lights, w.lights.data(), w.lights.size())) != PT_OK) return st;
     if (d->n_spheres) { if ((st = upload(ctx, ctx->d_spheres, w.sph.data(), w.sph.size())) != PT_OK) return st; } else ctx->d_spheres.release();
+    if (!w.motion.empty()) {          // the PtMotion records ride behind the instances (scene_motions)
+        std::vector<unsigned char> buf(w.dinst.size() * sizeof(PtInstance) + w.motion.size() * sizeof(PtMotion));
+        if (!w.dinst.empty()) std::memcpy(buf.data(), w.dinst.data(), w.dinst.size() * sizeof(PtInstance));
+        std::memcpy(buf.data() + w.dinst.size() * sizeof(PtInstance), w.motion.data(), w.motion.size() * sizeof(PtMotion));
+        if ((st = upload(ctx, ctx->d_instances, buf.data(), buf.size())) != PT_OK) return st;
+    } else
     if (d->n_instances) { if ((st = upload(ctx, ctx->d_instances, w.dinst.data(), w.dinst.size())) != PT_OK) return st; } else ctx->d_instances.release();
     return PT_OK;
 }
@@ -1327,7 +1403,9 @@ void fill_scene_record(pt_context* ctx, const pt_scene_desc* d, const SceneCheck
     sc.images = images_on_device ? ctx->d_images.as<PtImage>() : nullptr;
     sc.mat_params = mt.any_textured ? ctx->d_mat_params.as<PtMatParams>() : nullptr;
     sc.spheres = d->n_spheres ? ctx->d_spheres.as<PtSphere>() : nullptr;
-    sc.instances = d->n_instances ? ctx->d_instances.as<PtInstance>() : nullptr;
+    sc.instances = (d->n_instances || !w.motion.empty()) ? ctx->d_instances.as<PtInstance>() : nullptr;
+    ctx->motion_kernels = !w.motion.empty();
+    ctx->motion_instances = w.instances_move;
     sc.n_instances = d->n_instances;
     sc.n_spheres = d->n_spheres;
     if (d->n_spheres) sc.general_materials = 1;     // sphere scenes run the sphere-capable kernel instantiations (sorted shade queue)
@@ -1504,6 +1582,7 @@ pt_status setup_camera(pt_context* ctx, const pt_scene_desc* d) {
     std::memcpy(sc.cam.camera_to_world, d->camera_to_world, 64);
     sc.cam.lens_radius = d->lens_radius;
     sc.cam.focal_distance = d->focal_distance;
+    sc.cam.shutter_open = d->shutter_open; sc.cam.shutter_close = d->shutter_close;
     return PT_OK;
 }
 
@@ -1729,6 +1808,7 @@ pt_status scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     w.dev_build = ptbvh::DeviceBuild{ctx->stream, ctx->bvh_build_where, false, hipSuccess};
     w.max_node_prims = d->max_node_prims > 0 ? d->max_node_prims : 4;
     struct TrimBvh { pt_context* c; ~TrimBvh() { if (c->host_bvh.nodes.capacity() * sizeof(PtNode) > ((size_t)1 << 30)) c->host_bvh = ptbvh::Result(); } } trim_bvh{ctx};
+    if ((st = build_motion_records(ctx, d, w)) != PT_OK) return st;
     bool on_device = false;
     if ((st = build_world_on_device(ctx, d, chk, w, trace, &on_device)) != PT_OK) return st;
     if (!on_device) {
@@ -1774,6 +1854,8 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     ctx->map_lights.clear();
     ctx->alpha_masks.clear();
     ctx->disney_recs.clear();
+    ctx->next_has_motion = false;
+    ctx->next_motion_inst.clear();
     ctx->next_aov_target = PT_AOV_UV;
     ctx->next_aov_scale = 1.0f;
     return st;
@@ -1806,6 +1888,18 @@ pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_m
 pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* records) {
     if (!ctx || (n && !records)) return PT_ERR_INVALID_ARGUMENT;
     ctx->disney_recs.assign(records, records + n);
+    return PT_OK;
+}
+
+pt_status pt_scene_set_motion(pt_context* ctx, const pt_motion* motion) {
+    if (!ctx || (motion && motion->n_instances && !motion->instances)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->next_has_motion = motion != nullptr;
+    ctx->next_motion_inst.clear();
+    if (motion) {
+        ctx->next_motion = *motion;
+        ctx->next_motion_inst.assign(motion->instances, motion->instances + motion->n_instances);
+        ctx->next_motion.instances = nullptr;
+    }
     return PT_OK;
 }
 

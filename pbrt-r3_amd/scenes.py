@@ -298,6 +298,9 @@ class SceneBuilder:
         self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
         self.disney = []            # capi.pt_disney of the material_disney materials
         self.instances = []
+        self.motion_instances = []  # capi.pt_motion_instance of the instances given to_world_end=
+        self.times = (0.0, 1.0)     # TransformTimes (render_options.rs:65-66)
+        self.camera_to_world_end_m = None
         self.objects = {}           # name -> object index
         self.cur_object = 0         # 0 = world, k = inside ObjectBegin of object k - 1
         self.n_extra = 0            # creation counter of spheres and instances (ties at one before_triangle)
@@ -323,6 +326,34 @@ class SceneBuilder:
     # ---- options
     def look_at(self, eye, look, up):
         self.camera_to_world = camera_to_world_look_at(eye, look, up)
+
+    # ---- motion blur (pt_scene_set_motion): the camera and instances get a second transform, the one at transform_times[1]
+    def transform_times(self, start, end):
+        """TransformTimes (scene_context.rs:945-951)."""
+        self.times = (float(start), float(end))
+
+    def look_at_end(self, eye, look, up):
+        """The camera's LookAt under ActiveTransform EndTime."""
+        self.camera_to_world_end_m = camera_to_world_look_at(eye, look, up)
+
+    def camera_to_world_end(self, m):
+        self.camera_to_world_end_m = np.asarray(m, np.float32).reshape(-1)
+
+    def animated_shape_begin(self, to_world, to_world_end):
+        """An animated Shape (scene_context.rs:1233-1293): the shapes up to animated_shape_end() are built under the identity, without
+        the current area light, as one implicit object with one moving instance at this position of the world list."""
+        if self.cur_object:
+            raise ValueError("an animated shape inside an object definition is two levels of transforms")
+        self._anim = (to_world, to_world_end)
+        name = ("animated shape", len(self.objects))          # (a key no ObjectBegin name can be)
+        self.object_begin(name)
+        self.cur_area_light = -1
+        self._anim_name = name
+
+    def animated_shape_end(self):
+        to_world, to_world_end = self._anim
+        self.object_end()
+        self.object_instance(self._anim_name, to_world, to_world_end)
 
     def camera_perspective(self, fov=90.0, lensradius=0.0, focaldistance=1e6, screenwindow=None, frameaspectratio=None,
                            shutteropen=0.0, shutterclose=1.0):
@@ -898,8 +929,9 @@ class SceneBuilder:
         self.cur_object = 0
         self.cur_material, self.cur_area_light, self.reverse_orientation = self._saved_gstate
 
-    def object_instance(self, name, to_world=None):
-        """ObjectInstance under the CTM `to_world` = (m, m_inv)."""
+    def object_instance(self, name, to_world=None, to_world_end=None):
+        """ObjectInstance under the CTM `to_world` = (m, m_inv); to_world_end: the CTM's second slot (ActiveTransform EndTime), for an
+        instance that moves."""
         if self.cur_object:
             return                          # ignored inside an object definition (:1352-1357)
         it = capi.pt_instance()
@@ -911,6 +943,12 @@ class SceneBuilder:
         it.before_triangle = sum(len(i) for i in self.idx)
         it.order = self.n_extra
         self.n_extra += 1
+        if to_world_end is not None:
+            mi_rec = capi.pt_motion_instance()
+            mi_rec.instance = len(self.instances)
+            mi_rec.instance_to_world_end[:] = [float(v) for v in np.asarray(to_world_end[0], np.float32).reshape(-1)]
+            mi_rec.world_to_instance_end[:] = [float(v) for v in np.asarray(to_world_end[1], np.float32).reshape(-1)]
+            self.motion_instances.append(mi_rec)
         self.instances.append(it)
 
     # ---- tessellated shapes: the front end's tessellators (capi.tessellate_*), then create_triangle_mesh (triangle.rs:696-731).  No uv
@@ -1006,6 +1044,17 @@ class SceneBuilder:
         sd.alpha_masks = list(self.alpha_masks)
         sd.disney = list(self.disney)
         sd.aov = tuple(self.aov)
+        if self.motion_instances or self.camera_to_world_end_m is not None:
+            mo = capi.pt_motion()
+            mo.transform_times[:] = self.times
+            if self.camera_to_world_end_m is not None:
+                mo.camera_animated = 1
+                mo.camera_to_world_end[:] = [float(v) for v in self.camera_to_world_end_m]
+            if self.motion_instances:
+                arr = (capi.pt_motion_instance * len(self.motion_instances))(*self.motion_instances)
+                sd.buffers["motion_instances"] = arr
+                mo.n_instances, mo.instances = len(self.motion_instances), arr
+            sd.motion = mo
         d.split_method, d.max_node_prims = self.split_method, self.max_node_prims
         d.camera_to_world[:] = [float(v) for v in self.camera_to_world]
         d.fov = self.fov
