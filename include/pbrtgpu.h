@@ -137,10 +137,13 @@ typedef enum {
                                  * cycles, and a child may itself be a mix); anything else is PT_ERR_INVALID_ARGUMENT.  Every other field is
                                  * ignored: a mix has no bump map of its own, its shading frame and BSDF::eta are child 1's.  At most
                                  * PT_MIX_MAX_LEAVES leaves and PT_MIX_MAX_LOBES BxDFs per tree (PT_ERR_UNSUPPORTED beyond). */
-    PT_MATERIAL_DISNEY = 10     /* materials/disney.rs:644-841: "color" rides in kd / tex_kd, "eta" in eta / tex_eta, "roughness" in roughness /
+    PT_MATERIAL_DISNEY = 10,    /* materials/disney.rs:644-841: "color" rides in kd / tex_kd, "eta" in eta / tex_eta, "roughness" in roughness /
                                  * tex_roughness (never remapped), "bumpmap" in tex_bump; every other parameter rides in a pt_disney record
                                  * (pt_scene_set_disney), and a material without one takes create_disney_material's defaults.  Up to eight
                                  * BxDFs; usable as a child of a mix. */
+    PT_MATERIAL_FOURIER = 11    /* materials/fourier.rs:22-52: one FourierBSDF over a tabulated BSDF (a pt_fourier_table, named by the material's
+                                 * pt_fourier record: pt_scene_set_fourier); "bumpmap" in tex_bump, every other field is ignored.  A material
+                                 * without a record fails the upload.  One BxDF; usable as a child of a mix. */
 } pt_material_type;
 
 #define PT_MIX_MAX_LEAVES 4          /* leaf materials under one mix tree */
@@ -285,6 +288,27 @@ typedef struct {
     uint32_t tex_scatterdistance; /* index + 1 of its texture, 0 = constant */
     uint32_t reserved[6];
 } pt_disney;
+
+/* Material "fourier" (src/materials/fourier.rs, src/core/reflection/fourier.rs): a tabulated BSDF as FourierBSDFTable::read_body leaves
+ * it, and the record that names the table of a PT_MATERIAL_FOURIER material.  mu: n_mu zenith cosines, finite and never decreasing
+ * (n_mu >= 2; measured tables carry the node 0 twice: a repeated node must have the cdf column of its twin); cdf: n_mu * n_mu; offset_and_length: n_mu * n_mu pairs (offset, length) into a, with 0 <= length <= m_max, offset >= 0 and
+ * offset + n_channels * length <= n_coeffs; a: n_coeffs coefficients; n_channels 1 or 3.  The arrays are read during pt_scene_set_fourier
+ * only (copied).  Anything else fails the upload with PT_ERR_INVALID_ARGUMENT: the arrays need never have been a file.  Tables are shared:
+ * several records may name one.  Passed with pt_scene_set_fourier, not in pt_scene_desc.  64 / 16 bytes. */
+typedef struct {
+    int32_t n_mu, n_channels, m_max, n_coeffs;
+    float eta;
+    uint32_t reserved[3];
+    const float* mu;
+    const float* cdf;
+    const int32_t* offset_and_length;
+    const float* a;
+} pt_fourier_table;
+typedef struct {
+    uint32_t material;          /* index into pt_scene_desc.materials: a PT_MATERIAL_FOURIER material */
+    uint32_t table;             /* index into the tables handed over in the same call */
+    uint32_t reserved[2];
+} pt_fourier;
 
 /* TriangleMesh flags (src/shapes/triangle.rs:10-22). */
 #define PT_MESH_TWO_SIDED            1u  /* "twosided" shape param, default true (triangle.rs:707) */
@@ -498,7 +522,8 @@ typedef struct {
     double bvh_build_ms;
     double upload_ms;
     int32_t bvh_on_device;      /* ABI 5: 1 when the lower half of an HLBVH build ran on the GPU (pt_set_bvh_build) */
-    int32_t reserved;
+    int32_t fourier_capped;     /* (was reserved, 0) Material "fourier": samples since the upload whose inversion loops reached their iteration
+                                 * cap and were returned as "no sample" (pt_fourier.h); read from the device by pt_scene_info_get.  0 is expected */
 } pt_scene_info;
 
 /* ---- context ---------------------------------------------------------- */
@@ -534,6 +559,12 @@ pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_m
  * where a float texture belongs fails the upload with PT_ERR_INVALID_ARGUMENT.  A scene that holds a Disney material runs the *_mix
  * kernels of the build that knows Disney's BxDFs (pt_kernels_disney.hip); every other scene launches what it launched before. */
 pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* records);
+/* The tabulated BSDFs and the pt_fourier records of the NEXT pt_scene_upload only (deep copies; n_records = 0 clears them), consumed like
+ * the infinite lights.  Exactly one record per PT_MATERIAL_FOURIER material.  A table that breaks the rules of pt_fourier_table, a bad
+ * material or table index, a record for a material that is not PT_MATERIAL_FOURIER, two records for one material or a
+ * PT_MATERIAL_FOURIER material without a record fails the upload with PT_ERR_INVALID_ARGUMENT.  A scene that holds such a material runs
+ * the build of the kernels that knows FourierBSDF (PT_KERNELS_FOURIER); every other scene launches what it launched before. */
+pt_status pt_scene_set_fourier(pt_context* ctx, uint32_t n_tables, const pt_fourier_table* tables, uint32_t n_records, const pt_fourier* records);
 /* Integrator "aov": the target (a pt_aov_target) and the scale of the NEXT pt_scene_upload only, consumed like the infinite lights; read
  * when that upload's integrator is PT_INTEGRATOR_AOV.  Not called: target uv, scale 1 (create_aov_integrator's defaults, aov.rs:200-201).
  * A target outside the enum is PT_ERR_INVALID_ARGUMENT. */
@@ -667,6 +698,8 @@ pt_status pt_scene_bvh_digest(pt_context* ctx, uint64_t* nodes_digest, uint64_t*
 #define PT_KERNELS_MAP_LIGHT 3
 /* PT_KERNELS_MOTION (namespace ptv): a scene with an animated camera or at least one actually-animated instance (pt_scene_set_motion). */
 #define PT_KERNELS_MOTION 4
+/* PT_KERNELS_FOURIER (namespace ptf): a scene with a Material "fourier"; it knows everything the motion build knows. */
+#define PT_KERNELS_FOURIER 5
 pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out);
 
 /* Host-only utilities (no device, no context) of the motion path.  pt_motion_decompose: decompose() of core/transform/decompose.rs in

@@ -74,13 +74,20 @@ pt_status pth_parse_file_opts(const char* filename, const pth_options* opts, pth
  * list, built under the identity, with the warning "Ignoring currently set area light when creating animated shape" and no light; an
  * animated camera gives pt_motion.camera_to_world_end; TransformTimes arrives in pt_motion.transform_times (pth_scene_get_motion).  An
  * animated Shape inside ObjectBegin (two levels of transforms) and projective end transforms are refused by name.  Without the bit the
- * three kinds are refused as before, each with the same message.  pbrt_gpu sets all six. */
+ * three kinds are refused as before, each with the same message.
+ * PTH_FEATURE_FOURIER_MATERIAL: Material "fourier" and the MakeNamedMaterial type "fourier" (also as a child of a mix) become
+ * PT_MATERIAL_FOURIER records, each with a pt_fourier record that names its table (pth_scene_get_fourier); "bsdffile" resolves like an
+ * image map's file name and is read with pth_fourier_read, one table per file however many materials name it; "bumpmap" rides in
+ * tex_bump.  A file that is missing or that the reader refuses fails the parse with the file's name (create_fourier_material returns
+ * the error, materials/fourier.rs:46-52).  Without the bit the material is refused as before, with the same message.  pbrt_gpu sets
+ * all seven. */
 #define PTH_FEATURE_MIX_MATERIAL 1u
 #define PTH_FEATURE_DELTA_LIGHTS 2u
 #define PTH_FEATURE_QUADRIC_SHAPES 4u
 #define PTH_FEATURE_DISNEY_MATERIAL 8u
 #define PTH_FEATURE_POINT_LIGHTS 16u
 #define PTH_FEATURE_MOTION_BLUR 32u
+#define PTH_FEATURE_FOURIER_MATERIAL 64u
 pt_status pth_parse_file_features(const char* filename, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 pt_status pth_parse_string_features(const char* text, const char* work_dir, const pth_options* opts, uint32_t features, pth_scene** out, char* err, size_t err_cap);
 /* Parse scene text; work_dir is the base for Include (may be NULL). */
@@ -101,6 +108,9 @@ const pt_map_light* pth_scene_get_map_lights(const pth_scene* s, uint32_t* n);
 const pt_alpha_mask* pth_scene_get_alpha_masks(const pth_scene* s, uint32_t* n);
 /* The scene's Material "disney" records (for pt_scene_set_disney); *n receives their count.  Valid until pth_scene_free. */
 const pt_disney* pth_scene_get_disney(const pth_scene* s, uint32_t* n);
+/* The scene's tabulated BSDFs and Material "fourier" records, parsed with PTH_FEATURE_FOURIER_MATERIAL (for pt_scene_set_fourier);
+ * *n_tables and *n_records receive the counts, *records the records.  Valid until pth_scene_free. */
+const pt_fourier_table* pth_scene_get_fourier(const pth_scene* s, uint32_t* n_tables, const pt_fourier** records, uint32_t* n_records);
 /* The scene's motion, parsed with PTH_FEATURE_MOTION_BLUR (for pt_scene_set_motion): NULL when neither the camera nor an instance carries
  * a second transform.  Valid until pth_scene_free. */
 const pt_motion* pth_scene_get_motion(pth_scene* s);
@@ -122,6 +132,18 @@ pt_status pth_parse_to_log(const char* text, const char* work_dir, char* out, si
  * (src/core/spectrum/blackbody.rs:3-22; zero for t <= 0).  Exported so that the reference's own known-answer test
  * (tests/spectrum.rs:10-40) runs against this restatement. */
 void pth_blackbody(const double* lambda_nm, int n, double t_kelvin, double* out);
+
+/* ---- tabulated BSDFs: the "SCATFUN\x01" file behind Material "fourier", read as FourierBSDFTable::read_body reads it
+ * (src/core/reflection/fourier.rs:52-161): eight bytes of magic, then little-endian flags, n_mu, n_coeffs, m_max, n_channels, n_bases,
+ * three unused words, eta, four unused words, then mu, cdf, the (offset, length) pairs and the coefficients; whatever follows is ignored.
+ * Refused by name (PT_ERR_INVALID_ARGUMENT, the file's name in err): a file that cannot be opened, is truncated or has another magic;
+ * flags != 1, n_channels other than 1 or 3, n_bases != 1; and everything pt_scene_upload refuses in a pt_fourier_table (mu not finite or
+ * stepping back, a repeated node whose cdf column differs from its twin's, n_mu < 2, a length that is negative or above m_max, a negative offset, coefficients past the end of the
+ * array), which the reference leaves to its asserts.  On success *out holds the table; its arrays are valid until pth_fourier_free. */
+typedef struct pth_fourier_file pth_fourier_file;
+pt_status pth_fourier_read(const char* filename, pth_fourier_file** out, char* err, size_t err_cap);
+const pt_fourier_table* pth_fourier_table_of(const pth_fourier_file* f);
+void pth_fourier_free(pth_fourier_file* f);
 
 /* ---- tessellated shapes: "loopsubdiv" (shapes/loopsubdiv.rs), "nurbs" (shapes/nurbs.rs), "heightfield" (shapes/heightfield.rs).
  * Each returns the object-space arrays the reference hands to create_triangle_mesh (triangle.rs:696-731), in its vertex and face

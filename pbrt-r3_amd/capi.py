@@ -16,11 +16,13 @@ PT_MATERIAL_GLASS, PT_MATERIAL_METAL, PT_MATERIAL_UBER, PT_MATERIAL_SUBSTRATE = 
 PT_MATERIAL_TRANSLUCENT = 8
 PT_MATERIAL_MIX = 9
 PT_MATERIAL_DISNEY = 10
+PT_MATERIAL_FOURIER = 11
 (PT_DISNEY_METALLIC, PT_DISNEY_SPECULARTINT, PT_DISNEY_ANISOTROPIC, PT_DISNEY_SHEEN, PT_DISNEY_SHEENTINT, PT_DISNEY_CLEARCOAT,
  PT_DISNEY_CLEARCOATGLOSS, PT_DISNEY_SPECTRANS, PT_DISNEY_FLATNESS, PT_DISNEY_DIFFTRANS) = range(10)
 PT_MIX_MAX_LEAVES, PT_MIX_MAX_LOBES = 4, 16
 PTH_FEATURE_MIX_MATERIAL, PTH_FEATURE_DELTA_LIGHTS, PTH_FEATURE_QUADRIC_SHAPES, PTH_FEATURE_DISNEY_MATERIAL, PTH_FEATURE_POINT_LIGHTS = 1, 2, 4, 8, 16
 PTH_FEATURE_MOTION_BLUR = 32
+PTH_FEATURE_FOURIER_MATERIAL = 64
 PT_SHAPE_SPHERE, PT_SHAPE_CYLINDER, PT_SHAPE_DISK = 0, 1, 2
 PT_ROUGHNESS_UNSET = -1.0
 PT_MESH_TWO_SIDED, PT_MESH_REVERSE_ORIENTATION, PT_MESH_SWAPS_HANDEDNESS = 1, 2, 4
@@ -111,6 +113,68 @@ class pt_disney(C.Structure):
                 ("scatterdistance", C.c_float * 3), ("tex_scatterdistance", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
+class pt_fourier_table(C.Structure):
+    """Material "fourier": one tabulated BSDF as the C ABI takes it (the arrays stay the caller's)."""
+    _fields_ = [("n_mu", C.c_int32), ("n_channels", C.c_int32), ("m_max", C.c_int32), ("n_coeffs", C.c_int32), ("eta", C.c_float),
+                ("reserved", C.c_uint32 * 3), ("mu", C.POINTER(C.c_float)), ("cdf", C.POINTER(C.c_float)),
+                ("offset_and_length", C.POINTER(C.c_int32)), ("a", C.POINTER(C.c_float))]
+
+
+class pt_fourier(C.Structure):
+    """Material "fourier": which table a PT_MATERIAL_FOURIER material reads."""
+    _fields_ = [("material", C.c_uint32), ("table", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FourierTable:
+    """A tabulated BSDF in numpy arrays: mu [n_mu] f4, cdf [n_mu * n_mu] f4, offset_and_length [n_mu * n_mu, 2] i4, a [n_coeffs] f4.
+    Nothing is checked here: the upload (and read_fourier_table, for files) refuses a table the kernels could not read safely."""
+
+    def __init__(self, mu, cdf, offset_and_length, a, n_channels, m_max, eta, n_mu=None, n_coeffs=None):
+        self.mu = np.ascontiguousarray(mu, dtype=np.float32).reshape(-1)
+        self.cdf = np.ascontiguousarray(cdf, dtype=np.float32).reshape(-1)
+        self.offset_and_length = np.ascontiguousarray(offset_and_length, dtype=np.int32).reshape(-1)
+        self.a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        self.n_channels, self.m_max, self.eta = int(n_channels), int(m_max), float(eta)
+        self.n_mu = int(self.mu.size if n_mu is None else n_mu)              # (given: a header that disagrees with its arrays, for the refusal tests)
+        self.n_coeffs = int(self.a.size if n_coeffs is None else n_coeffs)
+
+    def as_struct(self):
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        t = pt_fourier_table()
+        t.n_mu, t.n_channels, t.m_max, t.n_coeffs, t.eta = self.n_mu, self.n_channels, self.m_max, self.n_coeffs, self.eta
+        t.mu, t.cdf = self.mu.ctypes.data_as(fp), self.cdf.ctypes.data_as(fp)
+        t.offset_and_length = self.offset_and_length.ctypes.data_as(ip)
+        t.a = self.a.ctypes.data_as(fp) if self.a.size else None
+        return t
+
+    @classmethod
+    def from_struct(cls, t):
+        """Copies of the arrays a pt_fourier_table points at (a table the library has accepted)."""
+        n2 = t.n_mu * t.n_mu
+        cp = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dt)
+        return cls(cp(t.mu, t.n_mu, np.float32), cp(t.cdf, n2, np.float32), cp(t.offset_and_length, 2 * n2, np.int32),
+                   cp(t.a, t.n_coeffs, np.float32), t.n_channels, t.m_max, t.eta)
+
+
+def read_fourier_table(filename, lib=None):
+    """pth_fourier_read: a "SCATFUN" file as a FourierTable; PtError (with the file's name) for a file the reader refuses."""
+    lib = lib or load_library()
+    lib.pth_fourier_read.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    lib.pth_fourier_table_of.argtypes = [C.c_void_p]
+    lib.pth_fourier_table_of.restype = C.POINTER(pt_fourier_table)
+    lib.pth_fourier_free.argtypes = [C.c_void_p]
+    lib.pth_fourier_free.restype = None
+    h = C.c_void_p()
+    err = C.create_string_buffer(2048)
+    st = lib.pth_fourier_read(str(filename).encode(), C.byref(h), err, 2048)
+    if st != 0:
+        raise PtError(st, err.value.decode())
+    try:
+        return FourierTable.from_struct(lib.pth_fourier_table_of(h).contents)
+    finally:
+        lib.pth_fourier_free(h)
+
+
 class pt_mesh(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("material", C.c_int32), ("area_light", C.c_int32), ("object", C.c_uint32)]
 
@@ -187,7 +251,7 @@ class pt_scene_info(C.Structure):
     _fields_ = [("sample_bounds", C.c_int32 * 4), ("cropped_bounds", C.c_int32 * 4), ("spp", C.c_int32),
                 ("n_lights", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("world_bound", C.c_float * 6), ("bvh_build_ms", C.c_double), ("upload_ms", C.c_double),
-                ("bvh_on_device", C.c_int32), ("reserved", C.c_int32)]
+                ("bvh_on_device", C.c_int32), ("fourier_capped", C.c_int32)]
 
 
 BVH_BUILD_AUTO, BVH_BUILD_HOST, BVH_BUILD_DEVICE = 0, 1, 2
@@ -214,9 +278,9 @@ SYMBOLS = [
     "pt_scene_set_infinite_lights", "pt_light_sample_li", "pt_light_pdf_li", "pt_light_pdf_from", "pt_light_le", "pt_scene_set_alpha_masks",
     "pt_scene_set_aov", "pt_scene_set_delta_lights", "pt_scene_set_disney", "pt_scene_set_map_lights", "pt_scene_kernel_set",
     "pt_scene_set_motion", "pt_trace_closest_time", "pt_trace_any_time", "pt_trace_wavefront_time", "pt_generate_camera_rays_time",
-    "pt_motion_decompose", "pt_motion_bounds",
+    "pt_motion_decompose", "pt_motion_bounds", "pt_scene_set_fourier",
 ]
-PT_KERNELS_BASE, PT_KERNELS_QUADRIC, PT_KERNELS_DISNEY, PT_KERNELS_MAP_LIGHT, PT_KERNELS_MOTION = 0, 1, 2, 3, 4
+PT_KERNELS_BASE, PT_KERNELS_QUADRIC, PT_KERNELS_DISNEY, PT_KERNELS_MAP_LIGHT, PT_KERNELS_MOTION, PT_KERNELS_FOURIER = 0, 1, 2, 3, 4, 5
 
 _lib = None
 
@@ -282,7 +346,8 @@ HOST_SYMBOLS = ["pth_parse_file", "pth_parse_file_opts", "pth_parse_string", "pt
                 "pth_scene_set_pixelsamples", "pth_scene_warnings", "pth_scene_free", "pth_write_pfm", "pth_write_image", "pth_parse_to_log",
                 "pth_display_connect", "pth_display_start", "pth_display_update", "pth_display_close", "pth_tev_create_packet", "pth_tev_update_packet", "pth_blackbody",
                 "pth_scene_get_infinite_lights", "pth_scene_get_alpha_masks", "pth_scene_get_aov", "pth_scene_get_delta_lights", "pth_scene_get_disney", "pth_scene_get_map_lights", "pth_scene_get_motion", "pth_parse_file_features", "pth_parse_string_features",
-                "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free"]
+                "pth_tessellate_loopsubdiv", "pth_tessellate_nurbs", "pth_tessellate_heightfield", "pth_tess_mesh_free",
+                "pth_scene_get_fourier", "pth_fourier_read", "pth_fourier_table_of", "pth_fourier_free"]
 
 
 class pth_options(C.Structure):
@@ -294,14 +359,16 @@ class ParsedScene:
     scenes.SceneDesc (has .desc), so it can be uploaded or handed to the oracle."""
 
     def __init__(self, text=None, filename=None, work_dir=None, lib=None, delta_lights=False, mix_materials=False, quadric_shapes=False,
-                 disney_materials=False, point_lights=False, motion_blur=False):
+                 disney_materials=False, point_lights=False, motion_blur=False, fourier_materials=False):
         """delta_lights: take LightSource "spot" / "distant" (pth_options.delta_lights); off, they are refused as before.
         mix_materials: take Material "mix" (PTH_FEATURE_MIX_MATERIAL through pth_parse_*_features); off, it is refused as before.
         quadric_shapes: take Shape "cylinder" and Shape "disk" (PTH_FEATURE_QUADRIC_SHAPES, the same way); off, they are refused as before.
         disney_materials: take Material "disney" (PTH_FEATURE_DISNEY_MATERIAL, the same way); off, it is refused as before.
         point_lights: take LightSource "goniometric", "projection" and "point" (PTH_FEATURE_POINT_LIGHTS, the same way); off, they are refused as before.
         motion_blur: take animated ObjectInstance, Shape and Camera transforms (PTH_FEATURE_MOTION_BLUR, the same way; .motion is then the
-        pt_motion record, or None when nothing moves); off, they are refused as before."""
+        pt_motion record, or None when nothing moves); off, they are refused as before.
+        fourier_materials: take Material "fourier" (PTH_FEATURE_FOURIER_MATERIAL, the same way; .fourier_tables / .fourier are then the
+        tables read from the "bsdffile"s and the records that name them); off, it is refused as before."""
         self.lib = lib or load_library()
         L = self.lib
         L.pth_parse_file.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
@@ -322,11 +389,12 @@ class ParsedScene:
         feat_args = [C.POINTER(pth_options), C.c_uint32, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         features = (PTH_FEATURE_MIX_MATERIAL if mix_materials else 0) | (PTH_FEATURE_DELTA_LIGHTS if delta_lights else 0) | \
                    (PTH_FEATURE_QUADRIC_SHAPES if quadric_shapes else 0) | (PTH_FEATURE_DISNEY_MATERIAL if disney_materials else 0) | \
-                   (PTH_FEATURE_POINT_LIGHTS if point_lights else 0) | (PTH_FEATURE_MOTION_BLUR if motion_blur else 0)
-        if (mix_materials or quadric_shapes or disney_materials or point_lights or motion_blur) and filename is not None:
+                   (PTH_FEATURE_POINT_LIGHTS if point_lights else 0) | (PTH_FEATURE_MOTION_BLUR if motion_blur else 0) | \
+                   (PTH_FEATURE_FOURIER_MATERIAL if fourier_materials else 0)
+        if features & ~PTH_FEATURE_DELTA_LIGHTS and filename is not None:
             L.pth_parse_file_features.argtypes = [C.c_char_p] + feat_args
             st = L.pth_parse_file_features(filename.encode(), None, features, C.byref(self.h), err, 2048)
-        elif mix_materials or quadric_shapes or disney_materials or point_lights or motion_blur:
+        elif features & ~PTH_FEATURE_DELTA_LIGHTS:
             L.pth_parse_string_features.argtypes = [C.c_char_p, C.c_char_p] + feat_args
             st = L.pth_parse_string_features(text.encode(), (work_dir or ".").encode(), None, features, C.byref(self.h), err, 2048)
         elif filename is not None and delta_lights:
@@ -373,6 +441,12 @@ class ParsedScene:
         tgt, scl = C.c_int32(), C.c_float()
         L.pth_scene_get_aov(self.h, C.byref(tgt), C.byref(scl))
         self.aov = (tgt.value, scl.value)         # Integrator "aov": (pt_aov_target, scale)
+        L.pth_scene_get_fourier.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.POINTER(pt_fourier)), C.POINTER(C.c_uint32)]
+        L.pth_scene_get_fourier.restype = C.POINTER(pt_fourier_table)
+        n_ft, n_fr, frs = C.c_uint32(), C.c_uint32(), C.POINTER(pt_fourier)()
+        fts = L.pth_scene_get_fourier(self.h, C.byref(n_ft), C.byref(frs), C.byref(n_fr))
+        self.fourier_tables = [FourierTable.from_struct(fts[i]) for i in range(n_ft.value)]          # Material "fourier": the tables (copies) ...
+        self.fourier = [pt_fourier.from_buffer_copy(frs[i]) for i in range(n_fr.value)]               # ... and the records that name them
         self.motion = None
         if motion_blur:                           # the motion record (its instance records stay the parsed scene's, which this object keeps alive)
             L.pth_scene_get_motion.argtypes = [C.c_void_p]
@@ -566,6 +640,13 @@ class Context:
             dis_arr = (pt_disney * len(dis))(*dis)
             self.lib.pt_scene_set_disney.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_disney)]
             self._check(self.lib.pt_scene_set_disney(self.h, C.c_uint32(len(dis)), dis_arr))
+        frs = list(getattr(scene, "fourier", None) or [])
+        if frs:                      # Material "fourier": the tables and the records that name them (consumed by the upload, like the Disney records)
+            tabs = list(getattr(scene, "fourier_tables", None) or [])
+            tab_arr = (pt_fourier_table * max(1, len(tabs)))(*[t.as_struct() for t in tabs])
+            rec_arr = (pt_fourier * len(frs))(*frs)
+            self.lib.pt_scene_set_fourier.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(pt_fourier_table), C.c_uint32, C.POINTER(pt_fourier)]
+            self._check(self.lib.pt_scene_set_fourier(self.h, C.c_uint32(len(tabs)), tab_arr, C.c_uint32(len(frs)), rec_arr))
         aov = getattr(scene, "aov", None)
         if aov is not None:          # Integrator "aov": (target, scale); otherwise the upload takes the defaults (uv, 1)
             self._check(self.lib.pt_scene_set_aov(self.h, C.c_int32(int(aov[0])), C.c_float(float(aov[1]))))
@@ -584,7 +665,7 @@ class Context:
         self._check(self.lib.pt_set_bvh_build(self.h, int(where)))
 
     def kernel_set(self):
-        """Which build of the kernels renders the uploaded scene: 0 base, 1 quadric (ptq), 2 disney (ptd), 3 map light (ptm), 4 motion (ptv)."""
+        """Which build of the kernels renders the uploaded scene: 0 base, 1 quadric (ptq), 2 disney (ptd), 3 map light (ptm), 4 motion (ptv), 5 fourier (ptf)."""
         k = C.c_int32()
         self.lib.pt_scene_kernel_set.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         self._check(self.lib.pt_scene_kernel_set(self.h, C.byref(k)))

@@ -73,6 +73,9 @@ struct Rendezvous {
 
 static const pt_disney* g_disney = nullptr;   // Material "disney" records of the parsed scene (pth_scene_get_disney), handed to every upload
 static uint32_t g_n_disney = 0;
+static const pt_fourier_table* g_fourier_tables = nullptr;   // Material "fourier": tables and records of the parsed scene (pth_scene_get_fourier), handed to every upload
+static const pt_fourier* g_fourier = nullptr;
+static uint32_t g_n_fourier_tables = 0, g_n_fourier = 0;
 static const pt_map_light* g_map_lights = nullptr;   // LightSource "goniometric" / "projection" of the parsed scene (pth_scene_get_map_lights), handed to every upload
 static uint32_t g_n_map_lights = 0;
 static const pt_motion* g_motion = nullptr;   // the parsed scene's motion (pth_scene_get_motion; NULL: nothing moves), handed to every upload
@@ -116,6 +119,7 @@ static int render_multi_gpu(const pt_scene_desc* dsc, const pt_infinite_light* i
         if (!check(r, pt_scene_set_map_lights(ctxs[(size_t)r], g_n_map_lights, g_map_lights), "goniometric / projection lights")) return;
         if (!check(r, pt_scene_set_alpha_masks(ctxs[(size_t)r], n_am, am), "alpha masks")) return;
         if (!check(r, pt_scene_set_disney(ctxs[(size_t)r], g_n_disney, g_disney), "disney records")) return;
+        if (!check(r, pt_scene_set_fourier(ctxs[(size_t)r], g_n_fourier_tables, g_fourier_tables, g_n_fourier, g_fourier), "fourier records")) return;
         if (!check(r, pt_scene_set_aov(ctxs[(size_t)r], g_aov_target, g_aov_scale), "aov target")) return;
         if (!check(r, pt_scene_set_motion(ctxs[(size_t)r], g_motion), "motion")) return;
         check(r, pt_scene_upload(ctxs[(size_t)r], dsc), "scene upload");
@@ -224,7 +228,7 @@ int main(int argc, char** argv) {
     opts.delta_lights = 1;           // LightSource "spot" / "distant" render here (pt_scene_set_delta_lights below)
     char err[1024] = {0};
     pth_scene* scene = nullptr;
-    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS | PTH_FEATURE_QUADRIC_SHAPES | PTH_FEATURE_DISNEY_MATERIAL | PTH_FEATURE_POINT_LIGHTS | PTH_FEATURE_MOTION_BLUR, &scene, err, sizeof(err));      // Material "mix" renders here
+    pt_status st = pth_parse_file_features(input.c_str(), &opts, PTH_FEATURE_MIX_MATERIAL | PTH_FEATURE_DELTA_LIGHTS | PTH_FEATURE_QUADRIC_SHAPES | PTH_FEATURE_DISNEY_MATERIAL | PTH_FEATURE_POINT_LIGHTS | PTH_FEATURE_MOTION_BLUR | PTH_FEATURE_FOURIER_MATERIAL, &scene, err, sizeof(err));      // Material "mix" renders here
     if (st != PT_OK) { std::fprintf(stderr, "pbrt_gpu: %s\n", err); return 1; }
     if (!quiet && pth_scene_warnings(scene)[0]) std::fprintf(stderr, "%s", pth_scene_warnings(scene));
     uint32_t n_inf_lights = 0;
@@ -235,6 +239,7 @@ int main(int argc, char** argv) {
     const pt_alpha_mask* alpha_masks = pth_scene_get_alpha_masks(scene, &n_alpha_masks);
     pth_scene_get_aov(scene, &g_aov_target, &g_aov_scale);
     g_disney = pth_scene_get_disney(scene, &g_n_disney);
+    g_fourier_tables = pth_scene_get_fourier(scene, &g_n_fourier_tables, &g_fourier, &g_n_fourier);
     g_map_lights = pth_scene_get_map_lights(scene, &g_n_map_lights);
     g_motion = pth_scene_get_motion(scene);
     if (outfile.empty()) {
@@ -279,6 +284,7 @@ int main(int argc, char** argv) {
     if (pt_scene_set_delta_lights(ctx, n_delta_lights, delta_lights) != PT_OK) return fail("delta lights");
     if (pt_scene_set_alpha_masks(ctx, n_alpha_masks, alpha_masks) != PT_OK) return fail("alpha masks");
     if (pt_scene_set_disney(ctx, g_n_disney, g_disney) != PT_OK) return fail("disney records");
+    if (pt_scene_set_fourier(ctx, g_n_fourier_tables, g_fourier_tables, g_n_fourier, g_fourier) != PT_OK) return fail("fourier records");
     if (pt_scene_set_map_lights(ctx, g_n_map_lights, g_map_lights) != PT_OK) return fail("goniometric / projection lights");
     if (pt_scene_set_aov(ctx, g_aov_target, g_aov_scale) != PT_OK) return fail("aov target");
     if (pt_scene_set_motion(ctx, g_motion) != PT_OK) return fail("motion");

@@ -26,6 +26,7 @@
 #include "pth_texture_image.h"
 #include "pth_spectrum.h"
 #include "pth_tessellate.h"
+#include "pth_fourier.h"
 
 namespace pth {
 
@@ -156,6 +157,11 @@ public:
     bool accept_mix = false;                     // PTH_FEATURE_MIX_MATERIAL: Material "mix" is taken (off: refused, as before)
     bool accept_disney = false;                  // PTH_FEATURE_DISNEY_MATERIAL: Material "disney" is taken (off: refused, as before)
     std::vector<pt_disney> disney_records;                              // one per Material "disney" of `materials` (for pt_scene_set_disney)
+    bool accept_fourier = false;                 // PTH_FEATURE_FOURIER_MATERIAL: Material "fourier" is taken (off: refused, as before)
+    std::vector<std::unique_ptr<pth_fourier_file>> fourier_files;       // the "bsdffile"s read so far, one per resolved file name
+    std::vector<std::string> fourier_file_names;
+    std::vector<pt_fourier_table> fourier_tables;                       // their tables, in the same order (for pt_scene_set_fourier)
+    std::vector<pt_fourier> fourier_records;                            // one per Material "fourier" of `materials`
     bool accept_point_lights = false;            // PTH_FEATURE_POINT_LIGHTS: LightSource "goniometric", "projection" and "point" are taken (off: refused, as before)
     bool accept_delta_lights = false;            // pth_options.delta_lights: LightSource "spot" / "distant" are taken (off: refused, as before)
     int32_t aov_target = PT_AOV_UV;                                     // Integrator "aov": "target" and "scale" (for pt_scene_set_aov)
@@ -770,6 +776,7 @@ public:
         pt_disney dr;                                            // Material "disney": what pt_material has no field for
         std::memset(&dr, 0, sizeof(dr));
         bool is_disney = false;
+        int fourier_table = -1;                                  // Material "fourier": index of its table among fourier_tables
         auto set3 = [](float* c, float v) { c[0] = c[1] = c[2] = v; };
         set3(m.opacity, 1.0f);
         m.eta = 1.5f;
@@ -857,6 +864,22 @@ public:
                      "finish (todo!(), disney.rs:712): outside the accelerated path");
                 return -1;
             }
+        } else if (mi.name == "fourier" && accept_fourier) {        // fourier.rs:46-52: "bsdffile" (find_filename) and "bumpmap" (below); a file that cannot be read fails the scene
+            m.type = PT_MATERIAL_FOURIER;
+            std::string file = geom.find_one_string("bsdffile", ""), base = geom.base_dir;
+            if (file.empty()) { file = mp.find_one_string("bsdffile", ""); base = mp.base_dir; }
+            if (!file.empty() && file[0] != '/' && !base.empty()) file = base + "/" + file;
+            for (size_t k = 0; k < fourier_file_names.size() && fourier_table < 0; k++)
+                if (fourier_file_names[k] == file) fourier_table = (int)k;      // the same file named twice is one table
+            if (fourier_table < 0) {
+                pth_fourier_file* ff = nullptr;
+                char why[1024] = {0};
+                if (pth_fourier_read(file.c_str(), &ff, why, sizeof(why)) != PT_OK) { fail("Material \"fourier\": " + std::string(why)); return -1; }
+                fourier_files.emplace_back(ff);
+                fourier_file_names.push_back(file);
+                fourier_tables.push_back(ff->table);
+                fourier_table = (int)fourier_tables.size() - 1;
+            }
         } else if (mi.name == "mix" && accept_mix) {                // mix.rs:98-104, scene_context.rs:446-452
             // The children: the ones the directive found; a shape that may set material parameters creates the material again, with its
             // parameters in front, among the named materials current at the shape (scene_context.rs:269-287).
@@ -906,6 +929,17 @@ public:
             dr.material = (uint32_t)materials.size() - 1u;
             disney_records.push_back(dr);
             return (int)dr.material;
+        }
+        if (fourier_table >= 0) {                                // the same material twice: equal record, same table
+            for (const pt_fourier& r : fourier_records)
+                if (r.table == (uint32_t)fourier_table && std::memcmp(&materials[r.material], &m, sizeof(m)) == 0) return (int)r.material;
+            materials.push_back(m);
+            pt_fourier fr;
+            std::memset(&fr, 0, sizeof(fr));
+            fr.material = (uint32_t)materials.size() - 1u;
+            fr.table = (uint32_t)fourier_table;
+            fourier_records.push_back(fr);
+            return (int)fr.material;
         }
         for (size_t i = 0; i < materials.size(); i++)
             if (std::memcmp(&materials[i], &m, sizeof(m)) == 0) return (int)i;
@@ -1410,6 +1444,7 @@ pt_status pth_parse_file_features(const char* filename, const pth_options* opts,
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
+    s->ctx.accept_fourier = (features & PTH_FEATURE_FOURIER_MATERIAL) != 0;
     s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
     s->ctx.accept_motion = (features & PTH_FEATURE_MOTION_BLUR) != 0;
     std::string perr;
@@ -1424,6 +1459,7 @@ pt_status pth_parse_string_features(const char* text, const char* work_dir, cons
     if (features & PTH_FEATURE_DELTA_LIGHTS) s->ctx.accept_delta_lights = true;
     s->ctx.accept_quadrics = (features & PTH_FEATURE_QUADRIC_SHAPES) != 0;
     s->ctx.accept_disney = (features & PTH_FEATURE_DISNEY_MATERIAL) != 0;
+    s->ctx.accept_fourier = (features & PTH_FEATURE_FOURIER_MATERIAL) != 0;
     s->ctx.accept_point_lights = (features & PTH_FEATURE_POINT_LIGHTS) != 0;
     s->ctx.accept_motion = (features & PTH_FEATURE_MOTION_BLUR) != 0;
     std::string perr;
@@ -1478,6 +1514,12 @@ const pt_motion* pth_scene_get_motion(pth_scene* s) {
     s->ctx.motion.n_instances = (uint32_t)s->ctx.motion_instances.size();
     s->ctx.motion.instances = s->ctx.motion_instances.empty() ? nullptr : s->ctx.motion_instances.data();
     return &s->ctx.motion;
+}
+const pt_fourier_table* pth_scene_get_fourier(const pth_scene* s, uint32_t* n_tables, const pt_fourier** records, uint32_t* n_records) {
+    if (n_tables) *n_tables = s ? (uint32_t)s->ctx.fourier_tables.size() : 0u;
+    if (n_records) *n_records = s ? (uint32_t)s->ctx.fourier_records.size() : 0u;
+    if (records) *records = (s && !s->ctx.fourier_records.empty()) ? s->ctx.fourier_records.data() : nullptr;
+    return (s && !s->ctx.fourier_tables.empty()) ? s->ctx.fourier_tables.data() : nullptr;
 }
 void pth_scene_get_aov(const pth_scene* s, int32_t* target, float* scale) {
     if (target) *target = s ? s->ctx.aov_target : (int32_t)PT_AOV_UV;

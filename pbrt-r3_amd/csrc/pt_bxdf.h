@@ -400,9 +400,16 @@ __device__ __noinline__ bool disney_sample_f(const PtLobe& l, V3 wo, V2 u, V3* f
 }
 #endif
 
+#if PT_FOURIER
+#include "pt_fourier.h"          // Material "fourier": compiled into the kernels of pt_kernels_fourier.hip only
+#endif
+
 __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
     const V3 zero = mk3(0.0f, 0.0f, 0.0f);
     switch (l.kind) {
+#if PT_FOURIER
+        case PT_LOBE_FOURIER: return fourier_f(l, wo, wi);
+#endif
         case PT_LOBE_LAMBERT: return ld3(l.r) * PT_INV_PI;
         case PT_LOBE_OREN_NAYAR: {
             float sti = bx_sin_theta(wi), sto = bx_sin_theta(wo);
@@ -462,6 +469,9 @@ __device__ __noinline__ V3 globe_f(const PtLobe& l, V3 wo, V3 wi) {
 
 __device__ __noinline__ float globe_pdf(const PtLobe& l, V3 wo, V3 wi) {
     switch (l.kind) {
+#if PT_FOURIER
+        case PT_LOBE_FOURIER: return fourier_pdf(l, wo, wi);
+#endif
         // LambertianTransmission (lambertian.rs:80-86) is PT_LOBE_LAMBERT with the transmission bit: the other hemisphere, and no INV_PI
         case PT_LOBE_LAMBERT: case PT_LOBE_OREN_NAYAR: {
             const bool trans = (l.type & PT_BSDF_TRANSMISSION) != 0;
@@ -502,6 +512,9 @@ __device__ __noinline__ float globe_pdf(const PtLobe& l, V3 wo, V3 wi) {
 __device__ __noinline__ bool globe_sample_f(const PtLobe& l, V3 wo, V2 u, V3* f, V3* wi_out, float* pdf, uint32_t* sampled_type) {
     *sampled_type = 0;
     switch (l.kind) {
+#if PT_FOURIER
+        case PT_LOBE_FOURIER: return fourier_sample_f(l, wo, u, f, wi_out, pdf);          // the returned type is 0: the lobe's own (fourier.rs:405)
+#endif
         case PT_LOBE_LAMBERT: case PT_LOBE_OREN_NAYAR: {
             V3 wi = cosine_sample_hemisphere(u);
             if ((l.type & PT_BSDF_TRANSMISSION) ? wo.z > 0.0f : wo.z < 0.0f) wi.z *= -1.0f;      // lambertian.rs:68-71: transmission leaves on the far side

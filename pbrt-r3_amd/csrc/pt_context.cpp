@@ -138,6 +138,15 @@ pt_status pt_scene_info_get(const pt_context* ctx, pt_scene_info* out) {
     if (!ctx || !out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return PT_ERR_NO_SCENE;
     *out = ctx->info;
+    if (ctx->n_fourier_tables) {          // Material "fourier": the samples the kernels turned away at an iteration cap, summed over the tables
+        (void)hipSetDevice(ctx->device);
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return PT_ERR_DEVICE;
+        std::vector<PtFourierTable> tabs(ctx->n_fourier_tables);
+        if (hipMemcpy(tabs.data(), ctx->d_fourier.p, tabs.size() * sizeof(PtFourierTable), hipMemcpyDeviceToHost) != hipSuccess) return PT_ERR_DEVICE;
+        uint64_t capped = 0;
+        for (const PtFourierTable& t : tabs) capped += t.capped;
+        out->fourier_capped = (int32_t)std::min<uint64_t>(capped, 0x7fffffffu);
+    }
     return PT_OK;
 }
 
@@ -653,7 +662,7 @@ static pt_status render_tiles(pt_context* ctx, const pt_tile* tiles, uint32_t n_
 #endif
     {   // diagnostic build -DPT_PROFILE_SHADE: where a shading wave's clocks go
         unsigned long long sp[16];
-        if (ctx->motion_kernels ? ptv::ptk_shade_prof_read(sp) : ctx->maplight_kernels ? ptm::ptk_shade_prof_read(sp) : ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
+        if (ctx->fourier_kernels ? ptf::ptk_shade_prof_read(sp) : ctx->motion_kernels ? ptv::ptk_shade_prof_read(sp) : ctx->maplight_kernels ? ptm::ptk_shade_prof_read(sp) : ctx->disney_kernels ? ptd::ptk_shade_prof_read(sp) : ctx->quadric_kernels ? ptq::ptk_shade_prof_read(sp) : ptk_shade_prof_read(sp)) {       // (each set of kernels counts into its own g_shade_prof)
             double tot = 0;
             for (int k = 0; k < 16; k++) if (k != 12) tot += (double)sp[k];
             static const char* names[16] = {"surface", "emit+bsdf setup", "grid+pick light", "u_light,u_scat", "light sample+f", "bsdf MIS+probe", "pend stores",
@@ -1138,7 +1147,7 @@ pt_status pt_set_bvh_build(pt_context* ctx, int where) {
 pt_status pt_scene_kernel_set(pt_context* ctx, int32_t* set_out) {
     if (!ctx || !set_out) return PT_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return ctx->fail(PT_ERR_NO_SCENE, "no scene uploaded");
-    *set_out = ctx->motion_kernels ? PT_KERNELS_MOTION : ctx->maplight_kernels ? PT_KERNELS_MAP_LIGHT : (ctx->disney_kernels ? PT_KERNELS_DISNEY : (ctx->quadric_kernels ? PT_KERNELS_QUADRIC : PT_KERNELS_BASE));
+    *set_out = ctx->fourier_kernels ? PT_KERNELS_FOURIER : ctx->motion_kernels ? PT_KERNELS_MOTION : ctx->maplight_kernels ? PT_KERNELS_MAP_LIGHT : (ctx->disney_kernels ? PT_KERNELS_DISNEY : (ctx->quadric_kernels ? PT_KERNELS_QUADRIC : PT_KERNELS_BASE));
     return PT_OK;
 }
 

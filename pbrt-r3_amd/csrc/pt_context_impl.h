@@ -64,6 +64,11 @@ struct pt_context {
     std::vector<pt_map_light> map_lights;           // pt_scene_set_map_lights: the next upload's goniometric / projection lights
     std::vector<pt_alpha_mask> alpha_masks;         // pt_scene_set_alpha_masks: the next upload's alpha masks
     std::vector<pt_disney> disney_recs;             // pt_scene_set_disney: the next upload's Disney parameter records
+    // pt_scene_set_fourier: the next upload's tabulated BSDFs (deep copies; `refusal` is what pt_fourier_table.h said about the caller's
+    // arrays, empty for a table fit to upload) and the records that name them
+    struct FourierTable { int32_t n_mu = 0, n_channels = 0, m_max = 0, n_coeffs = 0; float eta = 1.0f; std::vector<float> mu, cdf, a; std::vector<int32_t> offset_and_length; std::string refusal; };
+    std::vector<FourierTable> fourier_tables;
+    std::vector<pt_fourier> fourier_recs;
     bool next_has_motion = false;                   // pt_scene_set_motion: the next upload's motion (the instance records copied)
     pt_motion next_motion{};
     std::vector<pt_motion_instance> next_motion_inst;
@@ -75,8 +80,11 @@ struct pt_context {
     bool disney_kernels = false;                    // the uploaded scene holds a Material "disney": it runs the kernels of namespace ptd (pt_kernels_disney.hip)
     bool maplight_kernels = false;                  // the uploaded scene holds a goniometric or a projection light: it runs the kernels of namespace ptm (pt_kernels_maplight.hip)
     bool motion_kernels = false;                    // the uploaded scene's camera or one of its instances moves: it runs the kernels of namespace ptv (pt_kernels_motion.hip)
+    bool fourier_kernels = false;                   // the uploaded scene holds a Material "fourier": it runs the kernels of namespace ptf (pt_kernels_fourier.hip)
+    uint32_t n_fourier_tables = 0;                  // ... and that many PtFourierTable records lie at the head of d_fourier
     bool motion_instances = false;                  // ... an instance does (the trace hooks with a time need their own batch kernel then)
     bool scene_alpha = false;                       // the uploaded scene has a mask: every ray runs the alpha traversal kernels
+    DevBuf d_fourier;                               // the PtFourierTable records, then their arrays
     DevBuf d_env_tabs;                              // their Distribution2D tables (the PtEnvLight records ride behind the lights in d_lights)
     DevBuf d_nodes, d_tris, d_tri_info, d_spheres, d_instances, d_hit_inst, d_textures, d_tex_prog, d_mat_params, d_images, d_image_texels, d_N, d_S, d_UV, d_materials, d_lights, d_m32, d_vdc, d_vdc_inv, d_grid, d_bytetab, d_hdims, d_hperms;
     std::vector<uint32_t> sobol_m32;
@@ -157,9 +165,11 @@ struct pt_context {
 // pt_kernels_disney.hip), which knows both the shapes and Disney's BxDFs.  A scene that holds a goniometric or a projection light runs the fourth (namespace
 // ptm, pt_kernels_maplight.hip), which knows all of that and the two lights' image lookup.  A scene whose camera or instances move runs the fifth (namespace ptv,
 // pt_kernels_motion.hip), which knows all of that and AnimatedTransform::interpolate; its k_gen keeps the time sample, so ray generation is dispatched as well.
+// A scene that holds a Material "fourier" runs the sixth (namespace ptf, pt_kernels_fourier.hip), which knows all of that and FourierBSDF.
 #define PTK_BY_SCENE(fn)                                                                                            \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->fourier_kernels) return ptf::fn(std::forward<A>(a)...);                                            \
         if (ctx->motion_kernels) return ptv::fn(std::forward<A>(a)...);                                             \
         if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         if (ctx->disney_kernels) return ptd::fn(std::forward<A>(a)...);                                             \
@@ -187,6 +197,7 @@ PTK_BY_SCENE(ptk_camera_rays)
 #define PTK_BY_MATERIAL(fn)                                                                                         \
     template <class... A>                                                                                           \
     static hipError_t fn##_any(const pt_context* ctx, A&&... a) {                                                   \
+        if (ctx->fourier_kernels) return ptf::fn(std::forward<A>(a)...);                                            \
         if (ctx->motion_kernels) return ptv::fn(std::forward<A>(a)...);                                             \
         if (ctx->maplight_kernels) return ptm::fn(std::forward<A>(a)...);                                           \
         return ctx->disney_kernels ? ptd::fn(std::forward<A>(a)...) : ::fn(std::forward<A>(a)...);                  \

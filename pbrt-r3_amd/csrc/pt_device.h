@@ -98,7 +98,10 @@ enum { PT_LOBE_LAMBERT = 0, PT_LOBE_OREN_NAYAR = 1, PT_LOBE_SPEC_REFL = 2, PT_LO
        PT_LOBE_MF_REFL = 5, PT_LOBE_MF_TRANS = 6, PT_LOBE_FRESNEL_BLEND = 7,
        // Material "disney" (materials/disney.rs:44-323), known to the kernels of pt_kernels_disney.hip only: R in `r`; FakeSS / Retro keep their
        // roughness in `oa`; Clearcoat keeps its weight in `oa` and its gloss in `ob`
-       PT_LOBE_DISNEY_DIFFUSE = 8, PT_LOBE_DISNEY_FAKE_SS = 9, PT_LOBE_DISNEY_RETRO = 10, PT_LOBE_DISNEY_SHEEN = 11, PT_LOBE_DISNEY_CLEARCOAT = 12 };
+       PT_LOBE_DISNEY_DIFFUSE = 8, PT_LOBE_DISNEY_FAKE_SS = 9, PT_LOBE_DISNEY_RETRO = 10, PT_LOBE_DISNEY_SHEEN = 11, PT_LOBE_DISNEY_CLEARCOAT = 12,
+       // Material "fourier" (core/reflection/fourier.rs:178-465), known to the kernels of pt_kernels_fourier.hip only: the device address of the
+       // material's PtFourierTable rides as bits in t[0] (low word) and t[1] (high word), which no other field of the lobe depends on
+       PT_LOBE_FOURIER = 13 };
 // (LambertianTransmission, lambertian.rs:49-99, is PT_LOBE_LAMBERT whose `type` carries BSDF_TRANSMISSION instead of BSDF_REFLECTION: pt_bxdf.h)
 // PT_FR_DISNEY: DisneyFresnel (disney.rs:330-345): r0 in `t`, metallic in fr_eta_i, eta in fr_eta_t
 enum { PT_FR_NOOP = 0, PT_FR_DIELECTRIC = 1, PT_FR_CONDUCTOR = 2, PT_FR_DISNEY = 3 };
@@ -195,6 +198,24 @@ struct PtDisneyParams {
     uint32_t prog_bump;
 };
 static_assert(sizeof(PtDisneyParams) <= sizeof(PtLobe) * PT_MAX_LOBES, "the Disney parameter block lives in PtMaterial::lobes");
+
+// Material "fourier": one tabulated BSDF (FourierBSDFTable, core/reflection/fourier.rs:30-41) in HBM, shared by every material that names
+// it.  The upload has checked every (offset, length) pair against the coefficient array (pt_fourier_table.h).  A PT_LOBE_FOURIER lobe
+// carries this record's address, so PtScene, PtMaterial and PtLobe keep their sizes and no kernel argument changes.
+struct PtFourierTable {          // 80 bytes
+    const float* mu;             // [n_mu]
+    const float* cdf;            // [n_mu * n_mu]
+    const float* a0;             // [n_mu * n_mu]: a[offset] where length > 0, else 0
+    const float* a;              // [n_coeffs]
+    const float* recip;          // [max(m_max, 1)]: inf, then 1 / k
+    const int32_t* m;            // [n_mu * n_mu]: lengths
+    const int32_t* a_offset;     // [n_mu * n_mu]
+    uint32_t n_mu, n_channels, m_max;
+    float eta;
+    uint32_t capped;             // samples whose inversion reached its iteration cap (pt_fourier.h); the kernels add, pt_scene_info_get reads
+    uint32_t pad;
+};
+static_assert(sizeof(PtFourierTable) == 80, "PtFourierTable records lie back to back at the head of the table buffer");
 
 // One DiffuseAreaLight (one emissive triangle).
 struct PtLight {

@@ -37,7 +37,9 @@
 // PT_MAPLIGHT set as well and PT_KERNEL_NS ptm: the image lookup of the goniometric and projection lights inside delta_sample_li, on top
 // of the third build, for the scenes that hold such a light.  pt_kernels_motion.hip includes it a fifth time, with PT_MOTION set as well and
 // PT_KERNEL_NS ptv: a time per camera sample and AnimatedTransform::interpolate where a transform that moves is read (animated_at), on top
-// of the fourth build, for the scenes whose camera or instances move.
+// of the fourth build, for the scenes whose camera or instances move.  pt_kernels_fourier.hip includes it a sixth time, with PT_FOURIER set as
+// well and PT_KERNEL_NS ptf: FourierBSDF over a tabulated BSDF (pt_fourier.h) among the lobes, on top of the fifth build, for the scenes that
+// hold a Material "fourier".
 #if PT_QUADRIC
 #define PT_KERNEL __global__
 #ifndef PT_KERNEL_NS
@@ -2711,6 +2713,18 @@ PT_KERNEL void __launch_bounds__(PT_BLOCK) k_sort_local(PtScene sc, PtPaths P, P
 // build_lobes (pt_lobes.h, shared with the host) as a call: inlined into textured_lobes it made that function the register peak of
 // the textured shading kernel
 __device__ __noinline__ void build_lobes_call(const pt_material& in, float a_r, float a_u, float a_v, PtMaterial& m) { build_lobes(in, a_r, a_u, a_v, m); }
+#if PT_FOURIER
+// Material "fourier" with a bump map: build_lobes knows no such type and leaves an empty BSDF; the one lobe, which does not depend on the
+// hit, is the one the upload wrote into the material's own record (FourierMaterial::compute_scattering_functions, materials/fourier.rs:23-43)
+PT_DEV void fourier_hit_lobe(const PtScene& sc, int32_t material, PtMaterial& m) {
+    const PtMaterial& src = sc.materials[material];
+    if (src.type != PT_MATERIAL_FOURIER) return;
+    m.lobes[0] = src.lobes[0];
+    m.n_lobes = 1; m.nonspecular = 1;
+}
+#else
+#define fourier_hit_lobe(sc, material, m) do { } while (0)
+#endif
 // textured_params: the per-hit half -- the bump map bends the frame, every programmed parameter is evaluated into `mp`, the roughness
 // values are remapped into a3 = {a_r, a_u, a_v}.  k_tex_resolve stops here and hands the values to k_shade_general_res (PtTexRes).
 template <bool INL>
@@ -2780,6 +2794,7 @@ __device__ __noinline__ void textured_lobes(const PtScene& sc, int32_t material,
     float a3[3];
     textured_params(sc, material, th, mp, a3, n, uv, sh_n, sh_dpdu, sh_dpdv, sh_dndu, sh_dndv);
     build_lobes_call(mp.m, a3[0], a3[1], a3[2], *out);
+    fourier_hit_lobe(sc, material, *out);
 }
 // Material "mix" with a textured "amount" or a textured leaf: the tree's lobe list and scale chains at this hit (constant trees: built once at
 // upload, PtMix).  "amount" is evaluated on the interaction as it arrives (mix.rs:62-63); the leftmost leaf's bump map bends the caller's frame
@@ -3181,6 +3196,7 @@ PT_DEV void shade_body(const PtScene& sc, const PtPaths& P, const PtQueues& Q, P
                         mp.m.metal_eta[0] = r4.x; mp.m.metal_eta[1] = r4.y; mp.m.metal_eta[2] = r4.z; mp.m.metal_k[0] = r4.w; mp.m.metal_k[1] = r5.x; mp.m.metal_k[2] = r5.y;
                         mp.m.uroughness = r5.z; mp.m.vroughness = r5.w; mp.m.eta = r6.x;
                         build_lobes_call(mp.m, r6.y, r6.z, r6.w, tm);
+                        fourier_hit_lobe(sc, s.material, tm);
                         s.sh_n = mk3(r7.x, r7.y, r7.z); s.sh_dpdu = mk3(r7.w, r8.x, r8.y);
                         use_tm = true;
                         no_bsdf = tm.has_bsdf == 0;

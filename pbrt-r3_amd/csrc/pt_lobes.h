@@ -31,6 +31,7 @@ PT_HD inline PtLobe* push_lobe(PtMaterial& m, uint32_t kind, uint32_t type, cons
 PT_HD inline uint32_t pt_lobes_most(int32_t type) {
     switch (type) {
         case PT_MATERIAL_MATTE: case PT_MATERIAL_MIRROR: case PT_MATERIAL_METAL: case PT_MATERIAL_SUBSTRATE: return 1;
+        case PT_MATERIAL_FOURIER: return 1;                        // (not from build_lobes: the upload writes its one lobe, pt_scene_upload.cpp)
         case PT_MATERIAL_PLASTIC: case PT_MATERIAL_GLASS: return 2;
         case PT_MATERIAL_TRANSLUCENT: return 4;
         case PT_MATERIAL_UBER: return 5;

@@ -2,6 +2,7 @@
 // SceneContext::make_scene + make_integrator, src/core/api/scene_context/scene_context.rs:675-729).  scene_upload() at the end of the file is the
 // list of stages; each stage above it is a function of the context, the description and what it reads.
 #include "pt_context_impl.h"
+#include "pt_fourier_table.h"
 
 namespace {
 
@@ -363,7 +364,7 @@ pt_status check_scene(pt_context* ctx, const pt_scene_desc* d, SceneChecks& chk)
         if (d->meshes[m].area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "area light index out of range");
 
         int32_t mi = d->meshes[m].material;
-        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_DISNEY))
+        if (mi >= 0 && (d->materials[mi].type < PT_MATERIAL_NONE || d->materials[mi].type > PT_MATERIAL_FOURIER))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
     }
     for (uint32_t i = 0; i < d->n_materials; i++) {
@@ -404,7 +405,7 @@ pt_status check_scene(pt_context* ctx, const pt_scene_desc* d, SceneChecks& chk)
         const std::string shape = sp.kind == PT_SHAPE_CYLINDER ? "cylinder" : (sp.kind == PT_SHAPE_DISK ? "disk" : "sphere");
         if (sp.material >= (int32_t)d->n_materials || sp.material >= 65535) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " material index out of range");
         if (sp.area_light >= (int32_t)d->n_area_lights) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " area light index out of range");
-        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_DISNEY))
+        if (sp.material >= 0 && (d->materials[sp.material].type < PT_MATERIAL_NONE || d->materials[sp.material].type > PT_MATERIAL_FOURIER))
             return ctx->fail(PT_ERR_UNSUPPORTED, "material type not on the accelerated path");
         if (sp.before_triangle > d->n_triangles) return ctx->fail(PT_ERR_INVALID_ARGUMENT, shape + " before_triangle exceeds n_triangles");
         if (sp.kind != PT_SHAPE_SPHERE) {
@@ -504,6 +505,21 @@ pt_status check_scene(pt_context* ctx, const pt_scene_desc* d, SceneChecks& chk)
                 if (t && !is_float[t - 1]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "disney: a colour texture behind a float parameter");
         }
     }
+    {   // Material "fourier": exactly one record per such material, each naming a table that keeps the rules of pt_fourier_table.h
+        std::vector<uint8_t> seen(d->n_materials, 0);
+        for (const pt_fourier& r : ctx->fourier_recs) {
+            if (r.material >= d->n_materials) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: material index out of range");
+            if (d->materials[r.material].type != PT_MATERIAL_FOURIER) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: a record for a material that is not a Fourier material");
+            if (seen[r.material]) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: two records for one material");
+            if (r.table >= ctx->fourier_tables.size()) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: table index out of range");
+            seen[r.material] = 1;
+        }
+        for (size_t t = 0; t < ctx->fourier_tables.size(); t++)
+            if (!ctx->fourier_tables[t].refusal.empty()) return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: table " + std::to_string(t) + ": " + ctx->fourier_tables[t].refusal);
+        for (uint32_t i = 0; i < d->n_materials; i++)
+            if (d->materials[i].type == PT_MATERIAL_FOURIER && !seen[i])
+                return ctx->fail(PT_ERR_INVALID_ARGUMENT, "fourier: material " + std::to_string(i) + " has no record (pt_scene_set_fourier names its table)");
+    }
     chk.any_alpha = false;
     for (uint8_t m : mesh_alpha) chk.any_alpha |= m != 0;
     // integrator-specific refusals come after the index range checks above (they dereference materials[])
@@ -595,7 +611,14 @@ pt_status build_motion_records(pt_context* ctx, const pt_scene_desc* d, WorldBui
     w.inst_motion.assign(d->n_instances, 0u);
     w.inst_has_rotation.assign(d->n_instances, 0);
     w.inst_motion_rec.assign(d->n_instances, 0u);
-    if (!ctx->next_has_motion) return PT_OK;
+    // The build of the kernels that knows Material "fourier" contains the motion build: it reads the camera's record whatever the scene does, so a
+    // scene that holds such a material and does not move gets that one record, not animated (pt_motion_at hands back the stored transforms)
+    bool fourier = false;
+    for (uint32_t i = 0; i < d->n_materials; i++) fourier |= d->materials[i].type == PT_MATERIAL_FOURIER;
+    if (!ctx->next_has_motion) {
+        if (fourier) { PtMotion still; std::memset(&still, 0, sizeof(still)); w.motion.push_back(still); }
+        return PT_OK;
+    }
     const pt_motion& mo = ctx->next_motion;
     PtMotion cam;
     std::memset(&cam, 0, sizeof(cam));
@@ -622,7 +645,10 @@ pt_status build_motion_records(pt_context* ctx, const pt_scene_desc* d, WorldBui
         w.motion.push_back(rec);
         w.instances_move = true;
     }
-    if (!w.camera_moves && !w.instances_move) w.motion.clear();
+    if (!w.camera_moves && !w.instances_move) {
+        w.motion.clear();
+        if (fourier) { std::memset(&cam, 0, sizeof(cam)); w.motion.push_back(cam); }
+    }
     return PT_OK;
 }
 
@@ -1121,7 +1147,70 @@ pt_status build_disney_material(pt_context* ctx, const pt_scene_desc* d, uint32_
     return PT_OK;
 }
 
-// Fills `mt` (empty on entry), ctx->per_hit_lobes and ctx->disney_kernels
+// Material "fourier": the tables of this upload in one device buffer -- the PtFourierTable records first, then each table's arrays as
+// FourierBSDFTable::read_body leaves them (a0 and recip computed here, fourier.rs:130-146) -- and per table the device address of its record.
+pt_status upload_fourier_tables(pt_context* ctx, std::vector<uint64_t>& table_addr) {
+    const size_t n = ctx->fourier_tables.size();
+    table_addr.assign(n, 0);
+    ctx->n_fourier_tables = 0;
+    if (n == 0) { ctx->d_fourier.release(); return PT_OK; }
+    auto pad = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
+    size_t total = pad(n * sizeof(PtFourierTable));
+    struct Layout { size_t mu, cdf, a0, a, recip, m, off; };
+    std::vector<Layout> lay(n);
+    for (size_t t = 0; t < n; t++) {
+        const pt_context::FourierTable& ft = ctx->fourier_tables[t];
+        const size_t n2 = (size_t)ft.n_mu * ft.n_mu, nr = (size_t)std::max(ft.m_max, 1), na = (size_t)std::max(ft.n_coeffs, 1);
+        Layout& l = lay[t];
+        l.mu = total; total += pad(4 * (size_t)ft.n_mu);
+        l.cdf = total; total += pad(4 * n2);
+        l.a0 = total; total += pad(4 * n2);
+        l.a = total; total += pad(4 * na);
+        l.recip = total; total += pad(4 * nr);
+        l.m = total; total += pad(4 * n2);
+        l.off = total; total += pad(4 * n2);
+    }
+    PT_HIP(ctx->d_fourier.alloc(total));
+    std::vector<unsigned char> buf(total, 0);
+    unsigned char* base = ctx->d_fourier.as<unsigned char>();
+    for (size_t t = 0; t < n; t++) {
+        const pt_context::FourierTable& ft = ctx->fourier_tables[t];
+        const size_t n2 = (size_t)ft.n_mu * ft.n_mu;
+        const Layout& l = lay[t];
+        std::memcpy(buf.data() + l.mu, ft.mu.data(), 4 * ft.mu.size());
+        std::memcpy(buf.data() + l.cdf, ft.cdf.data(), 4 * n2);
+        if (!ft.a.empty()) std::memcpy(buf.data() + l.a, ft.a.data(), 4 * ft.a.size());
+        float* a0 = reinterpret_cast<float*>(buf.data() + l.a0);
+        int32_t* m = reinterpret_cast<int32_t*>(buf.data() + l.m);
+        int32_t* off = reinterpret_cast<int32_t*>(buf.data() + l.off);
+        for (size_t i = 0; i < n2; i++) {
+            off[i] = ft.offset_and_length[2 * i];
+            m[i] = ft.offset_and_length[2 * i + 1];
+            a0[i] = m[i] > 0 ? ft.a[(size_t)off[i]] : 0.0f;
+        }
+        float* recip = reinterpret_cast<float*>(buf.data() + l.recip);
+        recip[0] = INFINITY;
+        for (int32_t k = 1; k < ft.m_max; k++) recip[k] = 1.0f / (float)k;
+        PtFourierTable rec;
+        std::memset(&rec, 0, sizeof(rec));
+        rec.mu = reinterpret_cast<const float*>(base + l.mu);
+        rec.cdf = reinterpret_cast<const float*>(base + l.cdf);
+        rec.a0 = reinterpret_cast<const float*>(base + l.a0);
+        rec.a = reinterpret_cast<const float*>(base + l.a);
+        rec.recip = reinterpret_cast<const float*>(base + l.recip);
+        rec.m = reinterpret_cast<const int32_t*>(base + l.m);
+        rec.a_offset = reinterpret_cast<const int32_t*>(base + l.off);
+        rec.n_mu = (uint32_t)ft.n_mu; rec.n_channels = (uint32_t)ft.n_channels; rec.m_max = (uint32_t)ft.m_max;
+        rec.eta = ft.eta;
+        std::memcpy(buf.data() + t * sizeof(PtFourierTable), &rec, sizeof(rec));
+        table_addr[t] = (uint64_t)(uintptr_t)(base + t * sizeof(PtFourierTable));
+    }
+    PT_HIP(hipMemcpy(ctx->d_fourier.p, buf.data(), total, hipMemcpyHostToDevice));
+    ctx->n_fourier_tables = (uint32_t)n;
+    return PT_OK;
+}
+
+// Fills `mt` (empty on entry), ctx->per_hit_lobes, ctx->disney_kernels and ctx->fourier_kernels
 pt_status build_materials(pt_context* ctx, const pt_scene_desc* d, const SceneChecks& chk, MaterialTables& mt) {
     mt.mats.resize(std::max<uint32_t>(d->n_materials, 1));
     std::memset(mt.mats.data(), 0, mt.mats.size() * sizeof(PtMaterial));
@@ -1134,8 +1223,28 @@ pt_status build_materials(pt_context* ctx, const pt_scene_desc* d, const SceneCh
     std::vector<const pt_disney*> disney_of(mt.mats.size(), nullptr);
     for (const pt_disney& r : ctx->disney_recs) disney_of[r.material] = &r;
     ctx->disney_kernels = false;
+    ctx->fourier_kernels = false;
+    std::vector<uint64_t> fourier_addr;
+    std::vector<int32_t> fourier_of(mt.mats.size(), -1);
+    for (const pt_fourier& r : ctx->fourier_recs) fourier_of[r.material] = (int32_t)r.table;
+    for (uint32_t i = 0; i < d->n_materials; i++) ctx->fourier_kernels |= d->materials[i].type == PT_MATERIAL_FOURIER;
+    if (ctx->fourier_kernels) { const pt_status st = upload_fourier_tables(ctx, fourier_addr); if (st != PT_OK) return st; }
+    else { ctx->d_fourier.release(); ctx->n_fourier_tables = 0; }
     for (uint32_t i = 0; i < d->n_materials; i++) {
         build_lobes(d->materials[i], mt.mats[i]);
+        if (d->materials[i].type == PT_MATERIAL_FOURIER) {
+            // Material "fourier" (materials/fourier.rs:23-43): one FourierBSDF, added whenever the table has channels (every table the upload
+            // takes has), in a BSDF allocated with eta 1.  build_lobes knows no such type (the kernels of the other builds compile it too, and keep
+            // their code); the lobe is written here, its table's device address as bits in t[0] / t[1] (pt_device.h).  Of the material's own
+            // fields only "bumpmap" is read, below, like any other material's.
+            PtMaterial& mm = mt.mats[i];
+            const float zero[3] = {0.0f, 0.0f, 0.0f};
+            PtLobe* l = push_lobe(mm, PT_LOBE_FOURIER, kRefl | kTrans | kGlossy, zero);
+            const uint64_t addr = fourier_addr[(size_t)fourier_of[i]];
+            const uint32_t lo = (uint32_t)addr, hi = (uint32_t)(addr >> 32);
+            std::memcpy(&l->t[0], &lo, 4); std::memcpy(&l->t[1], &hi, 4);
+            mm.nonspecular = 1; mm.spec_mask = 0; mm.bsdf_eta = 1.0f; mm.has_bsdf = 1;
+        }
         if (d->materials[i].type == PT_MATERIAL_DISNEY) {
             const pt_status st = build_disney_material(ctx, d, i, disney_of[i], mt, disney_lobes[i], n_general_bins);
             if (st != PT_OK) return st;
@@ -1172,7 +1281,7 @@ pt_status build_materials(pt_context* ctx, const pt_scene_desc* d, const SceneCh
                     return;
                 }
                 const uint32_t j = n_leaves++;
-                if (in.type < PT_MATERIAL_NONE || (in.type > PT_MATERIAL_TRANSLUCENT && in.type != PT_MATERIAL_DISNEY)) {
+                if (in.type < PT_MATERIAL_NONE || (in.type > PT_MATERIAL_TRANSLUCENT && in.type != PT_MATERIAL_DISNEY && in.type != PT_MATERIAL_FOURIER)) {
                     if (refusal.empty()) refusal = "child material " + std::to_string(mi) + " has a material type that is not on the accelerated path";
                     return;
                 }
@@ -1243,7 +1352,7 @@ pt_status build_materials(pt_context* ctx, const pt_scene_desc* d, const SceneCh
             mp.m = in;
             material_alphas(in, &mp.a_r, &mp.a_u, &mp.a_v);
             for (int k = 0; k < 13; k++) {
-                if (!refs[k] || in.type == PT_MATERIAL_NONE) continue;
+                if (!refs[k] || in.type == PT_MATERIAL_NONE || (in.type == PT_MATERIAL_FOURIER && k != 8)) continue;
                 mp.prog[k] = add_program(d, mt.tex_prog, refs[k] - 1);
                 if (!mp.prog[k]) return ctx->fail(PT_ERR_UNSUPPORTED, "a material parameter's texture graph needs more than 12 nodes");
                 mt.mats[i].textured = 1;
@@ -1404,7 +1513,7 @@ void fill_scene_record(pt_context* ctx, const pt_scene_desc* d, const SceneCheck
     sc.mat_params = mt.any_textured ? ctx->d_mat_params.as<PtMatParams>() : nullptr;
     sc.spheres = d->n_spheres ? ctx->d_spheres.as<PtSphere>() : nullptr;
     sc.instances = (d->n_instances || !w.motion.empty()) ? ctx->d_instances.as<PtInstance>() : nullptr;
-    ctx->motion_kernels = !w.motion.empty();
+    ctx->motion_kernels = w.camera_moves || w.instances_move;
     ctx->motion_instances = w.instances_move;
     sc.n_instances = d->n_instances;
     sc.n_spheres = d->n_spheres;
@@ -1788,7 +1897,7 @@ void fill_info(pt_context* ctx, const WorldBuild& w, double t0, double t2) {
     inf.bvh_build_ms = w.t1 - t0;
     inf.upload_ms = t2 - w.t1;
     inf.bvh_on_device = w.dev_build.used ? 1 : 0;
-    inf.reserved = 0;
+    inf.fourier_capped = 0;
 }
 
 // The stages in order.  The first refusal or device error ends the upload: have_scene stays false and no buffer of the half-made scene is observable.
@@ -1854,6 +1963,8 @@ pt_status pt_scene_upload(pt_context* ctx, const pt_scene_desc* d) {
     ctx->map_lights.clear();
     ctx->alpha_masks.clear();
     ctx->disney_recs.clear();
+    ctx->fourier_tables.clear();
+    ctx->fourier_recs.clear();
     ctx->next_has_motion = false;
     ctx->next_motion_inst.clear();
     ctx->next_aov_target = PT_AOV_UV;
@@ -1888,6 +1999,25 @@ pt_status pt_scene_set_alpha_masks(pt_context* ctx, uint32_t n, const pt_alpha_m
 pt_status pt_scene_set_disney(pt_context* ctx, uint32_t n, const pt_disney* records) {
     if (!ctx || (n && !records)) return PT_ERR_INVALID_ARGUMENT;
     ctx->disney_recs.assign(records, records + n);
+    return PT_OK;
+}
+
+pt_status pt_scene_set_fourier(pt_context* ctx, uint32_t n_tables, const pt_fourier_table* tables, uint32_t n_records, const pt_fourier* records) {
+    if (!ctx || (n_tables && !tables) || (n_records && !records)) return PT_ERR_INVALID_ARGUMENT;
+    ctx->fourier_tables.assign(n_tables, pt_context::FourierTable());
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const pt_fourier_table& in = tables[t];
+        pt_context::FourierTable& o = ctx->fourier_tables[t];
+        o.n_mu = in.n_mu; o.n_channels = in.n_channels; o.m_max = in.m_max; o.n_coeffs = in.n_coeffs; o.eta = in.eta;
+        o.refusal = pt_fourier_table_refusal(in);          // (it looks at the counts before it reads an array)
+        if (!o.refusal.empty()) continue;                   // the upload reports it
+        const size_t n2 = (size_t)in.n_mu * (size_t)in.n_mu;
+        o.mu.assign(in.mu, in.mu + in.n_mu);
+        o.cdf.assign(in.cdf, in.cdf + n2);
+        o.offset_and_length.assign(in.offset_and_length, in.offset_and_length + 2 * n2);
+        if (in.n_coeffs) o.a.assign(in.a, in.a + in.n_coeffs);
+    }
+    ctx->fourier_recs.assign(records, records + n_records);
     return PT_OK;
 }
 

@@ -271,6 +271,8 @@ class SceneDesc:
         self.buffers = {}
         self.alpha_masks = []       # capi.pt_alpha_mask, one per masked mesh (uploaded beside the descriptor, like infinite_lights)
         self.disney = []            # capi.pt_disney, one per Material "disney" (uploaded beside the descriptor too)
+        self.fourier_tables = []    # capi.FourierTable, and capi.pt_fourier, one per Material "fourier" (uploaded beside the descriptor too)
+        self.fourier = []
         self.aov = (capi.PT_AOV_UV, 1.0)      # Integrator "aov": (pt_aov_target, scale), uploaded beside the descriptor too
 
     def _set(self, name, arr, ctype):
@@ -297,6 +299,9 @@ class SceneBuilder:
         self.map_lights = []        # capi.pt_map_light (goniometric, projection), in directive order
         self.alpha_masks = []       # capi.pt_alpha_mask of the meshes given alpha= / shadowalpha=
         self.disney = []            # capi.pt_disney of the material_disney materials
+        self.fourier_tables = []    # capi.FourierTable of the material_fourier materials (one per file or object, however many materials name it)
+        self.fourier_keys = []      # ... what each was made from (a file name, or the id of a FourierTable)
+        self.fourier = []           # capi.pt_fourier of the material_fourier materials
         self.instances = []
         self.motion_instances = []  # capi.pt_motion_instance of the instances given to_world_end=
         self.times = (0.0, 1.0)     # TransformTimes (render_options.rs:65-66)
@@ -679,6 +684,22 @@ class SceneBuilder:
         r.tex_scatterdistance = scatterdistance.index + 1 if isinstance(scatterdistance, Tex) else 0
         self.disney.append(r)
 
+    def material_fourier(self, bsdffile=None, table=None, bumpmap=None):
+        """materials/fourier.rs:46-52: a tabulated BSDF from a "SCATFUN" file (bsdffile: read with capi.read_fourier_table, which raises
+        for a file the reader refuses) or from arrays (table: a capi.FourierTable).  The same file, or the same object, named by several
+        materials is one table.  The material record carries "bumpmap" alone; the table travels in a pt_fourier record beside the
+        descriptor.  Usable as a child of material_mix."""
+        if (bsdffile is None) == (table is None):
+            raise ValueError("material_fourier: give bsdffile or table")
+        key = ("file", str(bsdffile)) if table is None else ("table", id(table))
+        if key not in self.fourier_keys:
+            self.fourier_tables.append(capi.read_fourier_table(bsdffile) if table is None else table)
+            self.fourier_keys.append(key)
+        self.cur_material = self._add_material(capi.PT_MATERIAL_FOURIER, bump=bumpmap)
+        r = capi.pt_fourier()
+        r.material, r.table = self.cur_material, self.fourier_keys.index(key)
+        self.fourier.append(r)
+
     def material_none(self):
         self.cur_material = -1
 
@@ -1043,6 +1064,7 @@ class SceneBuilder:
         sd.map_lights = list(self.map_lights)
         sd.alpha_masks = list(self.alpha_masks)
         sd.disney = list(self.disney)
+        sd.fourier_tables, sd.fourier = list(self.fourier_tables), list(self.fourier)
         sd.aov = tuple(self.aov)
         if self.motion_instances or self.camera_to_world_end_m is not None:
             mo = capi.pt_motion()
