@@ -426,8 +426,9 @@ def _coordinate_system(v1):
     return v2, v3 / np.linalg.norm(v3)
 
 
-def light_truth(scene, light, ref_p, u):
+def light_truth(scene, light, ref_p, u, solid_angle=True):
     """DiffuseAreaLight::sample_li of light `light` for reference points ref_p (one, or one per u) and samples u, in float64.
+    solid_angle=False leaves the solid angle out (NaN): it is one arctangent per reference point, in a Python loop.
     Returns a dict: p (the sampled point), wi, pdf (0 where the reference returns None), li, valid, p_bound (how far the float32
     point may lie from p), pdf_rel (the relative bound on pdf), solid_angle (per reference point; NaN where not defined: inside
     a sphere), branch ("triangle", "inside", "cone", "cone_small")."""
@@ -470,7 +471,7 @@ def light_truth(scene, light, ref_p, u):
             # of wi and n (a few ulp each) and weighs 1 / |cos|; the point's own error moves dist by p_bound
             pdf_rel = gamma(24) + gamma(8) / np.abs(cos) + 4.0 * p_bound / np.sqrt(dist2) / np.abs(cos)
             out_branch[:] = "triangle"
-            for i in range(n):
+            for i in range(n if solid_angle else 0):
                 sa[i] = sa[i - 1] if i and np.array_equal(ref[i], ref[i - 1]) else triangle_solid_angle(ref[i], p0, p1, p2)
         else:
             sp = sc.spheres[idx]

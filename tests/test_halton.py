@@ -7,51 +7,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from halton_ref import Pcg32, primes, shuffle
 from helpers import scenes
-
-
-class Pcg32:
-    """core/rng.rs:8-67 (scalar; only used for the small shuffles below)."""
-    M = (1 << 64) - 1
-
-    def __init__(self, seq=None):
-        self.state, self.inc = 0x853c49e6748fea9b, 0xda3e39cb94b95bdb
-        if seq is not None:
-            self.state, self.inc = 0, ((seq << 1) | 1) & self.M
-            self.u32()
-            self.state = (self.state + 0x853c49e6748fea9b) & self.M
-            self.u32()
-
-    def u32(self):
-        old = self.state
-        self.state = (old * 0x5851f42d4c957f2d + self.inc) & self.M
-        xs = (((old >> 18) ^ old) >> 27) & 0xffffffff
-        rot = old >> 59
-        return ((xs >> rot) | (xs << ((-rot) & 31))) & 0xffffffff
-
-    def below(self, b):
-        threshold = ((1 << 32) - b) % b
-        while True:
-            r = self.u32()
-            if r >= threshold:
-                return r % b
-
-
-def shuffle(a, rng):
-    """shuffle_array with one dimension (core/sampling/sampling.rs:4-15)."""
-    n = len(a)
-    for i in range(n):
-        other = i + rng.below(n - i)
-        a[i], a[other] = a[other], a[i]
-
-
-def primes(n):
-    out, c = [], 2
-    while len(out) < n:
-        if all(c % p for p in out if p * p <= c):
-            out.append(c)
-        c += 1
-    return out
 
 
 @pytest.fixture(scope="module")
